@@ -20,12 +20,25 @@ Workloads (--workload):
   deit_base  BASELINE.json configs[3]: the DeiT-Base supernet (deit_h12_l12) under the AutoProg search mix -- one (l, r) per step
           drawn from l in {6, 9, 12} x r in {128, 160, 192, 224} (main_prog.py:1824-1836), soft-target CE, per-GPU batch 128
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line.  A plain run does only what its headline needs: set-up, the pre-warm, the counted --warmup steps, the
+--steps timed steps and the line (`metric`, `value`, `unit`, `ms_per_step`, ...).  --full adds everything else the benchmark measures,
+each behind its own --no-* switch as before: the box `calibration`, the forward+loss+backward-only steps (`fwd_loss_bwd_only_ms_per_step`),
+the stand-alone gradient all-reduce of N > 1 (`allreduce_ms_standalone`) and two objects:
   roofline     dominant kernel (k_gemm_nt): algorithmic FLOPs and bytes of its launches in one step / their summed duration,
                measured with HIP events on the launch stream; `bound` follows from the launches' arithmetic intensity against
                the ridge (2.5 PFLOP/s / 8 TB/s = 312 FLOP/B), the other roof's fraction is reported beside it
   cpu_baseline the CPU oracle (oracle/ref_cpu.py, kind "port") timed on this host on bounded samples: the VOLO-D1 step at batch 8
                and BASELINE.json configs[0] (DeiT-Tiny, depth-4 sub-net, batch 32, soft-target CE); rank 0 at N=1 only.
+Without --full these fields read null.
+
+--dump-outputs DIR (rank 0) writes what the last timed step computed, as float32 .npy files: the loss, the model's outputs (logits) and,
+after the optimizer step, the fp32 parameters, their gradients and the slowest EMA copy -- arrays of more than DUMP_SAMPLE elements as a
+fixed, seeded sample of that many (64 MB at most in all).  The step runs its default kernels (AP_DETERMINISTIC as the environment sets it).
+The inputs and weights are seeded, but the default weight gradients are fp32 atomic sums whose rounding varies from run to run, and Adam
+would carry it from step to step; so the state the set-up leaves (weights, Adam moments, EMA copies, buffers, fp8 scales, RNG streams) is
+kept and written back, in place, in front of the LAST timed step (SeededState): that step computes from the same state in every run, and
+two runs differ by one step's rounding.  The write-back is one pass over the optimizer slabs inside the timed region of such a run.
+With --graph the model outputs stay inside the graph: the dump then holds the loss, parameters, gradients and EMA copy only.
 """
 import argparse
 import json
@@ -44,6 +57,62 @@ PEAK_BF16_TFLOPS = 2500.0       # MI355X dense bf16 MFMA peak (/opt/skills/guide
 PEAK_FP8_TFLOPS = 5000.0        # ... dense fp8 (e4m3 / e5m2) MFMA peak, same table
 PEAK_HBM_TBS = 8.0              # HBM3E peak
 STAGES = [(9, 128, 0.0), (12, 160, 0.0333), (15, 192, 0.0667), (18, 224, 0.1)]      # prog/progressive.py:4-31 with scripts/train_autoprog.sh
+DUMP_SAMPLE = 1 << 21           # --dump-outputs: larger arrays are written as a seeded sample of this many elements (8 MB in float32)
+
+
+class SeededState:
+    """--dump-outputs: the training state as the set-up leaves it, before any step -- fp32 weights, Adam moments and step count, EMA copies,
+    the model's buffers, the RNG streams (DropPath masks, mix-token box, (l, r) draws) -- written back in place by restore(), so a step run
+    after it computes from the same state in every run (the state after several steps differs by the atomics' accumulated rounding)."""
+
+    def __init__(self, model, opt, device):
+        self.model, self.opt, self.device = model, opt, device
+        tensors = [opt.p, opt.m, opt.v] + list(opt.ema) + [b for bufs in opt.ema_buffers for b in bufs] + list(model.buffers())
+        self.tensors = [(t, t.detach().clone()) for t in tensors]
+        self.step_count = opt.step_count
+        self.rng = (torch.get_rng_state(), torch.cuda.get_rng_state(device), np.random.get_state(), random.getstate())
+
+    def restore(self):
+        from autoprog_amd import functional as AF
+        with torch.no_grad():
+            for dst, src in self.tensors:
+                dst.copy_(src)
+        self.opt.step_count = self.step_count
+        self.opt.resync()                    # the bf16 / transposed weight copies, and the weight caches keyed by the update generation
+        if AF.FP8_LINEAR:
+            AF.reset_fp8_state()             # delayed fp8 scales: as before the first step
+        torch.set_rng_state(self.rng[0])
+        torch.cuda.set_rng_state(self.rng[1], self.device)
+        np.random.set_state(self.rng[2])
+        random.setstate(self.rng[3])
+
+
+def dump_outputs(path, loss, out, opt, reducer):
+    """--dump-outputs: the last timed step's loss, model outputs and post-step parameters / gradients / slowest EMA copy as float32 .npy"""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss}
+    if isinstance(out, torch.Tensor):
+        arrays["logits"] = out
+    elif isinstance(out, (tuple, list)):
+        for name, t in zip(("logits_cls", "logits_aux"), out):
+            if isinstance(t, torch.Tensor):
+                arrays[name] = t
+    n = reducer.flat.numel()
+    arrays["params"] = opt.p[:n]
+    arrays["grads"] = reducer.flat
+    if opt.ema:
+        arrays["ema_last"] = opt.ema[-1][:n]
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach().reshape(1) if t.dim() == 0 else t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(1234).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            name += "_sample"
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+    assert total <= 64 << 20, total
 
 
 def default_batch(workload):
@@ -420,7 +489,16 @@ def main():
                     help="seconds of the SAME step run in front of the counted --warmup steps (reported as prewarm_s): a fresh lease starts "
                          "with cold clocks and allocator pools, and 5 warm-up steps are 60 ms; never part of the timed region")
     ap.add_argument("--no-calibration", action="store_true", help="skip the in-process box calibration (copy / MFMA loop / one GEMM)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: calibration, forward+loss+backward-only steps, the stand-alone "
+                         "all-reduce, roofline and CPU baseline (each still off with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, outputs, parameters, gradients and EMA copy to DIR/<name>.npy (float32); that step "
+                         "starts from the set-up's seeded state (written back in front of it), so runs of the same arguments agree to one "
+                         "step's rounding.  With --graph the outputs stay inside the graph: loss, parameters, gradients and EMA only")
     args = ap.parse_args()
+    if not args.full:
+        args.no_calibration = args.no_roofline = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher.  Nothing in this process has touched the GPU yet; the ranks are
@@ -454,6 +532,7 @@ def main():
     from autoprog_amd.models import create_model
     from autoprog_amd.loss import TokenLabelCrossEntropy
     from autoprog_amd.dist import GradientBucketReducer
+    from autoprog_amd import ops
 
     torch.manual_seed(42 + rank)
     np.random.seed(42 + rank)
@@ -488,6 +567,8 @@ def main():
 
     B, res = args.batch, args.res
     gen = torch.Generator().manual_seed(42 + rank)
+    keep_out = args.dump_outputs is not None and rank == 0
+    last_out = [None]                  # --dump-outputs: the model outputs of the latest eager step
     images = torch.randn(B, 3, res, res, generator=gen).to(dev)
     if args.workload == "deit_base":
         target = torch.softmax(torch.randn(B, 1000, generator=gen) * 3, dim=-1).to(dev)
@@ -499,7 +580,10 @@ def main():
             reducer.zero_grad()
             # the reference resizes the loader's batch to the step's resolution inside the step (main_prog.py:973-974)
             xr = images if r == res else torch.nn.functional.interpolate(images, size=(r, r), mode="bilinear", align_corners=False)
-            loss = loss_fn(model(xr), target)
+            out = model(xr)
+            if keep_out:
+                last_out[0] = out
+            loss = loss_fn(out, target)
             loss.backward()
             reducer.finish()
             if not args.no_optimizer:
@@ -528,7 +612,10 @@ def main():
             model.set_sample_config(dict(layer_num=l, min_layer_num=l_list[0], max_layer_num=l_list[-1], input_size=r))
             model.set_drop_path_rate(dp)
             reducer.zero_grad()
-            loss = loss_fn(model(images), targets[r])       # the 224-px batch is resized to r by the stem's first kernel
+            out = model(images)                             # the 224-px batch is resized to r by the stem's first kernel
+            if keep_out:
+                last_out[0] = out
+            loss = loss_fn(out, targets[r])
             loss.backward()
             reducer.finish()
             if not args.no_optimizer:
@@ -542,6 +629,8 @@ def main():
         def step():
             reducer.zero_grad()
             out = model(images)
+            if keep_out:
+                last_out[0] = out
             loss = loss_fn(out, target)
             loss.backward()
             reducer.finish()
@@ -549,6 +638,10 @@ def main():
                 opt.step()
             return loss
 
+    seeded = SeededState(model, opt, dev) if args.dump_outputs is not None else None     # (before any step: graph capture runs some)
+    if keep_out and args.graph:
+        print("bench.py --dump-outputs --graph: the model outputs stay inside the graph; dumping loss, parameters, gradients and EMA only",
+              file=sys.stderr, flush=True)
     eager_step = step
     if args.graph:
         if world > 1 or args.no_optimizer or args.workload not in ("d1", "stages"):
@@ -617,6 +710,8 @@ def main():
     t0 = time.perf_counter()
     step_ev[0].record()
     for i_ in range(args.steps):
+        if seeded is not None and i_ == args.steps - 1:
+            seeded.restore()             # --dump-outputs: the last timed step starts from the set-up's state (on every rank)
         loss = step()
         step_ev[i_ + 1].record()
     torch.cuda.synchronize()
@@ -630,12 +725,15 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     final_loss = float(loss.detach())
+    if keep_out:                       # (before the --full measurements below run further steps)
+        dump_outputs(args.dump_outputs, loss, last_out[0], opt, reducer)
+        last_out[0] = None
 
     # SURVEY.md section 8(d) M1 asks for the optimizer + EMA share separately: time a few fwd+loss+bwd-only steps as well
     # (reported under config, never part of `value`)
     fwd_bwd_ms = None
     allreduce_ms = None
-    if not args.no_optimizer and args.workload in ("d1", "d5"):        # (the other workloads change (l, r) per step)
+    if args.full and not args.no_optimizer and args.workload in ("d1", "d5"):        # (the other workloads change (l, r) per step)
         def step_nb():
             reducer.zero_grad()
             loss_fn(model(images), target).backward()
@@ -649,7 +747,7 @@ def main():
             step_nb()
         torch.cuda.synchronize()
         fwd_bwd_ms = (time.perf_counter() - t1) / n_extra * 1e3
-    if world > 1:
+    if world > 1 and args.full:
         # the gradient exchange on its own (not overlapped with anything): what backward has to hide
         torch.cuda.synchronize()
         dist.barrier()
@@ -738,7 +836,7 @@ def main():
                   else "images/sec/GPU (fwd+bwd) DeiT-Base AutoProg search-mix step" if args.workload == "deit_base"
                   else "images/sec/GPU (fwd+bwd) VOLO-D1 224px AutoProg step")
         line = {"metric": metric, "value": round(value, 2), "unit": "images/sec",
-                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3),
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full, "ms_per_step": round(ms_step, 3),
                 "ms_per_step_min": round(step_ms[0], 3), "ms_per_step_median": round(step_ms[len(step_ms) // 2], 3), "ms_per_step_max": round(step_ms[-1], 3),
                 "ms_per_step_how": "value / ms_per_step: wall clock over the timed steps; min / median / max: HIP events recorded behind every step on the launch stream (rank 0)",
                 "prewarm_s": round(prewarm_s, 2), "prewarm_steps": prewarm_steps, "calibration": calibration,
@@ -754,7 +852,7 @@ def main():
                            "target": ("soft-target [B,1000]" if args.workload == "deit_base" else
                                       "dense fp32 [B,1000,2+N]" if args.dense_target else
                                       "top-5 label maps [B,2+N,5] + smoothing 0.1, densified inside the CE kernel (== the dense tensor of main_prog.py:994-1004)"),
-                           "final_loss": round(final_loss, 4),
+                           "final_loss": round(final_loss, 4), "deterministic": bool(ops.deterministic),
                            "fwd_loss_bwd_only_ms_per_step": None if fwd_bwd_ms is None else round(fwd_bwd_ms, 3)},
                 "roofline": roofline, "cpu_baseline": cpu}
         print(json.dumps(line), flush=True)

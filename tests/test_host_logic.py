@@ -186,15 +186,19 @@ def test_driver_batch_splits_follow_the_reference_rule():
     assert AutoProgDriver(None, None, None, None, None, [64], [3], [0.0], [0], 1).splits_for(3, 64) == 1      # default: no splits
 
 
-def test_driver_search_after_a_stage_with_batch_splits():
+def test_driver_search_after_a_stage_with_batch_splits(monkeypatch):
     """a search that follows a training stage run at k >= 2 micro-batches per update.  `_time` used to close its passes as
     accumulating micro-batches (no exchange, `_micro` left at 1) and the first training step of the search then died in
     set_accumulate_steps.  Real GradientBucketReducer + the real driver on a CPU stand-in model: the timed passes are updates of one
     micro-batch, every batch of the search has the reference's search size (original_batch_splits, main_prog.py:807-810), and the
-    reducer ends between updates."""
+    reducer ends between updates.  The driver's clock is a stand-in too: a forward pass advances it by l * r^2 (the cost of the active
+    candidate), so the loss-vs-time fit of the search sees the same step times on every host instead of timer noise."""
     import contextlib
     from autoprog_amd.dist import GradientBucketReducer
+    from autoprog_amd.prog import driver as driver_mod
     from autoprog_amd.prog.driver import AutoProgDriver
+    clock = [0.0]
+    monkeypatch.setattr(driver_mod, "time", types.SimpleNamespace(perf_counter=lambda: clock[0]))
 
     class Net(torch.nn.Module):
         def __init__(self):
@@ -209,6 +213,8 @@ def test_driver_search_after_a_stage_with_batch_splits():
             pass
 
         def forward(self, x):
+            l, r = self.configs[-1]
+            clock[0] += 1e-8 * l * r * r
             return self.fc(x)
 
     class Opt:

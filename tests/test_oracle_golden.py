@@ -137,7 +137,7 @@ def test_stem_train_and_eval():
 def test_stem64_train_and_eval(fixture):
     """the BASELINE-width stem (64 channels: the shapes the HIP convolution kernels are written for) against the reference
     vectors of tests/golden/stem64.npz -- the oracle side of tests/test_gpu_blocks.py::test_hip_stem64_vs_reference_golden; round 5:
-    the same for the 128-wide stem of VOLO-D4 / D5 (stem128.npz, csrc/conv128.hip)"""
+    the same for the 128-wide stem of VOLO-D4 / D5 (stem128.*.npz, csrc/conv128.hip)"""
     d = load(fixture)
     p = _params(d, "train")
     x = torch.from_numpy(d["train.x"]).double().requires_grad_(True)
@@ -163,7 +163,7 @@ def test_pos_interp():
 
 @pytest.mark.parametrize("tag,variant", [("h2_l3", "volo_h2_l3"), ("h2_l6", "volo_h2_l6"), ("h2_l3_s64", "volo_h2_l3")])
 def test_volo_full_train_eval(tag, variant):
-    """whole networks of the reference: volo_full.npz (16-wide stem, batch 2) and -- round 5 -- volo_full64.npz: the SHIPPED 64-wide stem
+    """whole networks of the reference: volo_full.*.npz (16-wide stem, batch 2) and -- round 5 -- volo_full64.*.npz: the SHIPPED 64-wide stem
     at batch 8 (tools/gen_golden.py::gen_volo_full64)"""
     d = load("volo_full64" if tag.endswith("_s64") else "volo_full")
     arch = R.variant_arch(variant)
@@ -254,7 +254,7 @@ def test_loss_curve_five_adamw_steps():
 
 
 def test_loss_curve_realistic_init_ten_adamw_steps():
-    """the realistic-init pin (tests/golden/step_curve_init.npz: reference volo_h4_l6 run in fp64, weights with the statistics
+    """the realistic-init pin (tests/golden/step_curve_init.*.npz: reference volo_h4_l6 run in fp64, weights with the statistics
     of the reference's own _init_weights regenerated from a seed, 10 AdamW steps): fp64 oracle losses <= 1e-8 abs, first-step
     gradients of the sampled tensors <= 1e-6 rel (stored as fp32), gradient norms of ALL tensors <= 1e-9 rel."""
     from tests._initweights import init_state_dict
@@ -327,7 +327,7 @@ def _late_state_reference(d):
 
 
 def test_late_state_outputs_loss_and_gradients():
-    """the oracle on a TRAINED state (tests/golden/late_state.npz: the reference's volo_h4_l6 after 300 fp64 AdamW steps, evaluated by
+    """the oracle on a TRAINED state (tests/golden/late_state.*.npz: the reference's volo_h4_l6 after 300 fp64 AdamW steps, evaluated by
     the reference in fp64): logits <= 1e-9 rel, loss <= 1e-9, every parameter gradient <= 2e-3 rel (the fixture stores gradients as fp16
     mantissas with a per-tensor scale) and all gradients as one vector <= 5e-4."""
     d = load("late_state")

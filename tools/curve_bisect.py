@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Where does the realistic-init loss curve (tests/golden/step_curve_init.npz) lose precision?  Runs the 10 AdamW steps of the
+"""Where does the realistic-init loss curve (tests/golden/step_curve_init.*.npz) lose precision?  Runs the 10 AdamW steps of the
 GPU test with one part of the network switched to fp32 at a time and prints |loss - reference(fp64)| per step and the first-step
 gradient errors of the sampled tensors.  GPU box only:  python tools/curve_bisect.py [bf16|stem32] [repeat]"""
 import os

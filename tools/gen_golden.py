@@ -3,7 +3,7 @@
 
 Run in the build container only (the reference tree does not exist on the GPU box):
 
-    python tools/gen_golden.py            # rewrites tests/golden/*.npz
+    python tools/gen_golden.py            # rewrites tests/golden/*.npz (a fixture over 1 MiB as NAME.0.npz, NAME.1.npz, ...)
 
 Fixtures are data only: inputs, weights (flat name -> array), outputs and gradients of the
 reference modules on small seeded problems.  No reference
@@ -51,9 +51,11 @@ def randomize_(module, gen, scale=0.5):
 
 
 def save(name, **arrs):
-    path = os.path.join(OUT, name + ".npz")
-    np.savez_compressed(path, **arrs)
-    print("wrote %-28s %8.1f KB  (%d arrays)" % (name + ".npz", os.path.getsize(path) / 1024, len(arrs)))
+    sys.path.insert(0, os.path.dirname(HERE))
+    from tests._golden import save_parts          # NAME.npz, or NAME.0.npz, NAME.1.npz, ... under 1 MiB each
+    for path in save_parts(OUT, name, arrs):
+        print("wrote %-28s %8.1f KB" % (os.path.basename(path), os.path.getsize(path) / 1024))
+    print("      %-28s (%d arrays)" % (name, len(arrs)))
 
 
 # ----------------------------------------------------------------------------------------------
