@@ -35,6 +35,12 @@ class TnProblem(Structure):
                 ("M", c_int), ("N1", c_int), ("N2", c_int), ("alpha", c_float), ("colsum_A", c_void_p), ("colsum_weight", c_void_p), ("colsum_scale", c_float), ("b_patch", c_void_p), ("b_bn", c_void_p)]
 
 
+class Tn8Problem(Structure):
+    """ap_tn8_problem (include/autoprog_hip.h)"""
+    _fields_ = [("A", c_void_p), ("lda", c_int), ("B", c_void_p), ("ldb", c_int), ("C", c_void_p), ("ldc", c_int),
+                ("M", c_int), ("N1", c_int), ("N2", c_int), ("a_fmt", c_int), ("alpha", c_float), ("dq_a", c_void_p), ("dq_b", c_void_p)]
+
+
 class BnInput(Structure):
     """ap_bn_input (include/autoprog_hip.h)"""
     _fields_ = [("mean", c_void_p), ("rstd", c_void_p), ("gamma", c_void_p), ("beta", c_void_p)]
@@ -52,6 +58,8 @@ class PatchMap(Structure):
 
 TN_MAX_GROUP = 32          # AP_TN_MAX_GROUP
 TN_MAX_GROUP_DET = 8       # the deterministic mode (workspace) takes 8
+BF8_COLSUM_SPLITS = 64     # AP_BF8_COLSUM_SPLITS: rows of the deterministic column-sum workspace of ap_quantize_bf8
+FP8_E4M3, FP8_E5M2 = 0, 1  # AP_FP8_E4M3 / AP_FP8_E5M2
 LN_MAX_BATCH = 12          # AP_LN_MAX_BATCH
 _P, _I, _L, _F = c_void_p, c_int, c_int64, c_float
 _SIGNATURES = {
@@ -111,6 +119,10 @@ _SIGNATURES["ap_layernorm_bwd_partial"] = (_I, [_P, _P, _P, _P, _P, _P, _P, _L, 
 _SIGNATURES["ap_layernorm_bwd_reduce_batched"] = (_I, [_P, _I, _P])
 _SIGNATURES["ap_quantize_fp8"] = (_I, [_P, _P, _L, _P, _P, _P])
 _SIGNATURES["ap_quantize_fp8_multi"] = (_I, [_P, _I, _P, _P, _P])
+_SIGNATURES["ap_quantize_bf8"] = (_I, [_P, _P, _L, _P, _P, _P, _I, _I, _P, _F, _P, _P])
+_SIGNATURES["ap_gemm_tn8_grouped_workspace"] = (ctypes.c_size_t, [_P, _I])
+_SIGNATURES["ap_gemm_tn8_acc_grouped"] = (_I, [_P, _I, _P, ctypes.c_size_t, _P])
+_SIGNATURES["ap_gemm_tn8_acc_grouped_ln"] = (_I, [_P, _I, _P, _I, _P, ctypes.c_size_t, _P])
 _SIGNATURES["ap_debug_poison_lds"] = (_I, [ctypes.c_uint, _P, _P])
 _SIGNATURES["ap_conv3x3_c64_bn"] = (_I, [_P, POINTER(BnInput), _P, _P, _I, _I, _I, _P, _P])
 _SIGNATURES["ap_conv3x3_c64_wgrad_bn"] = (_I, [_P, POINTER(BnInput), _P, _P, _I, _I, _I, _P, ctypes.c_size_t, _P])

@@ -366,6 +366,96 @@ k_quantize_fp8_multi(const ap_fp8_job* __restrict__ jobs, const float* __restric
     }
 }
 
+// ---------------------------------------------------------------------------- fp8 (OCP e5m2) quantisation of output gradients
+// 16 values -> 16 e5m2 bytes, y = sat(g * sc) (|.| <= 57344; v_cvt_pk_bf8_f32 rounds to nearest even); mx = max(mx, max |g|)
+__device__ __forceinline__ u32x4 bf8_pack16(const float* f, float sc, float& mx) {
+    u32x4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { mx = fmaxf(mx, fabsf(f[4 * k + e])); v[e] = fminf(fmaxf(f[4 * k + e] * sc, -57344.f), 57344.f); }
+        int w = 0;
+        w = __builtin_amdgcn_cvt_pk_bf8_f32(v[0], v[1], w, false);
+        w = __builtin_amdgcn_cvt_pk_bf8_f32(v[2], v[3], w, true);
+        o[k] = (unsigned)w;
+    }
+    return o;
+}
+// amax[0] = max(amax[0], max over the workgroup) (one atomic per workgroup, only when it raises the value); blockDim.x == 256
+__device__ __forceinline__ void bf8_amax(float mx, float* amax, float* smx) {
+    mx = group_max<64>(mx);
+    if ((threadIdx.x & 63) == 0) smx[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float m = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
+        if (__float_as_int(m) > *reinterpret_cast<volatile int*>(amax)) atomicMax(reinterpret_cast<int*>(amax), __float_as_int(m));
+    }
+}
+__global__ void __launch_bounds__(256)
+k_quantize_bf8(const bf16_t* __restrict__ x, unsigned char* __restrict__ y, int64_t n16, const float* __restrict__ scale, float* __restrict__ amax) {
+    const float sc = scale[0];
+    float mx = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (int64_t)gridDim.x * 256) {
+        float f[16];
+        unpack8(ld16(x + i * 16), f);
+        unpack8(ld16(x + i * 16 + 8), f + 8);
+        st16(y + i * 16, bf8_pack16(f, sc, mx));
+    }
+    __shared__ float smx[4];
+    if (amax) bf8_amax(mx, amax, smx);
+}
+// the same with the bias gradient of the un-quantised g [rows, cols] in the same pass: workgroup (x, y) = 16 16-column chunks x row
+// split y (AP_BF8_COLSUM_SPLITS contiguous row ranges), 16 threads per chunk stride over the split's rows (a row's 16 chunks = 512
+// contiguous bytes per wave-quarter).  The split's column sums leave as fp32 atomics (ws == nullptr) or are stored to ws[y][cols] for
+// k_bf8_colsum_reduce (split order: reproducible).
+__global__ void __launch_bounds__(256)
+k_quantize_bf8_colsum(const bf16_t* __restrict__ x, unsigned char* __restrict__ y, int rows, int cols, const float* __restrict__ scale,
+                      float* __restrict__ amax, float* __restrict__ colsum, const bf16_t* __restrict__ w, float cs_scale, float* __restrict__ ws) {
+    const float sc = scale[0];
+    const int nch = cols >> 4, ch = blockIdx.x * 16 + (threadIdx.x & 15), ry = threadIdx.x >> 4;
+    const int rps = (rows + gridDim.y - 1) / gridDim.y, r0 = blockIdx.y * rps, r1 = min(rows, r0 + rps);
+    float mx = 0.f, s[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) s[e] = 0.f;
+    if (ch < nch) {
+        for (int r = r0 + ry; r < r1; r += 16) {
+            const int64_t off = (int64_t)r * cols + ch * 16;
+            float f[16];
+            unpack8(ld16(x + off), f);
+            unpack8(ld16(x + off + 8), f + 8);
+            const float wr = w ? bf2f(w[r]) : 1.f;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) s[e] = fmaf(wr, f[e], s[e]);
+            st16(y + off, bf8_pack16(f, sc, mx));
+        }
+    }
+    __shared__ float red[16][16][17];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) red[ry][threadIdx.x & 15][e] = s[e];
+    __shared__ float smx[4];
+    if (amax) bf8_amax(mx, amax, smx);
+    __syncthreads();
+    // thread t sums column e = t & 15 of chunk c = t >> 4 over the 16 row lanes in order
+    const int c = threadIdx.x >> 4, e = threadIdx.x & 15;
+    if (blockIdx.x * 16 + c < nch) {
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) t += red[k][c][e];
+        const int col = (blockIdx.x * 16 + c) * 16 + e;
+        if (ws) ws[(int64_t)blockIdx.y * cols + col] = t;
+        else atomicAdd(colsum + col, t * cs_scale);
+    }
+}
+__global__ void __launch_bounds__(256)
+k_bf8_colsum_reduce(const float* __restrict__ ws, int splits, int cols, float* __restrict__ colsum, float cs_scale) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= cols) return;
+    float t = 0.f;
+    for (int z = 0; z < splits; ++z) t += ws[(int64_t)z * cols + c];
+    colsum[c] += t * cs_scale;
+}
+
 // ---------------------------------------------------------------------------- test aid: poison the LDS of every CU
 // every workgroup fills all 160 KB of its CU's LDS with `pattern` (e.g. 0x7FC07FC0 = bf16 NaN pairs, 0xFFFFFFFF = fp32 NaN) and spins
 // until `min_wgs` workgroups have arrived, so that the fill lands on many CUs: a kernel that reads LDS words it never wrote (padded
@@ -507,6 +597,28 @@ int ap_quantize_fp8_multi(const ap_fp8_job* jobs_device, int njobs, const float*
     if (njobs == 0) return AP_OK;
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_quantize_fp8_multi, dim3(32, njobs), dim3(256), 0, (hipStream_t)stream, jobs_device, scales, amax);
+    return ap_check_launch();
+}
+
+int ap_quantize_bf8(const ap_bf16* g, unsigned char* y, int64_t n, const float* scale, float* amax, float* colsum, int rows, int cols,
+                    const ap_bf16* colsum_weight, float colsum_scale, float* colsum_ws, ap_stream_t stream) {
+    if (!g || !y || !scale) return AP_ERR_NULL;
+    if (n < 0 || (n & 15)) return AP_ERR_SHAPE;
+    if (colsum && (rows <= 0 || cols <= 0 || (cols & 15) || (int64_t)rows * cols != n)) return AP_ERR_SHAPE;
+    if (n == 0) return AP_OK;
+    (void)hipGetLastError();
+    const bf16_t* x = reinterpret_cast<const bf16_t*>(g);
+    if (!colsum) {
+        hipLaunchKernelGGL(k_quantize_bf8, dim3(grid_for(n / 16)), dim3(256), 0, (hipStream_t)stream, x, y, n / 16, scale, amax);
+        return ap_check_launch();
+    }
+    const float css = colsum_weight ? colsum_scale : 1.0f;
+    const dim3 grid((unsigned)((cols / 16 + 15) / 16), AP_BF8_COLSUM_SPLITS);
+    hipLaunchKernelGGL(k_quantize_bf8_colsum, grid, dim3(256), 0, (hipStream_t)stream, x, y, rows, cols, scale, amax, colsum,
+                       reinterpret_cast<const bf16_t*>(colsum_weight), css, colsum_ws);
+    if (colsum_ws)
+        hipLaunchKernelGGL(k_bf8_colsum_reduce, dim3((cols + 255) / 256), dim3(256), 0, (hipStream_t)stream, colsum_ws, (int)AP_BF8_COLSUM_SPLITS,
+                           cols, colsum, css);
     return ap_check_launch();
 }
 

@@ -21,12 +21,15 @@
 // LDS tiles; the chunk swizzle f(row) keeps those transposed reads conflict free.  The token range
 // is split across blockIdx.z and partial tiles are added with fp32 atomics (few MB per call).
 #include <mutex>
+#include <algorithm>
+#include <cstring>
 #include "common.h"
 #include <type_traits>
 #include "gemm_epi.h"
 #include "gemm8p.h"
 #include "gemm_ws.h"
 #include "gemm_tn8p.h"
+#include "gemm_tn_fp8.h"
 // (the measured-and-rejected kernels of rounds 1 and 2 -- LDS-DMA rings, persistent 256-row tiles, the ring weight-gradient kernel -- and
 // their AP_GEMM_NT_P / _RING / _DMA, AP_GEMM_TN_RING switches live under tools/gemm_lab/rejected/, outside the product library)
 #include <cstdlib>
@@ -726,6 +729,19 @@ k_gemm_tn_8p(T8Group grp, T8Map map, TnLn ln) {
     const int pi = e >> T8_MAP_SHIFT, idx = e & ((1u << T8_MAP_SHIFT) - 1u), tiles = grp.tiles[pi];
     t8_item(grp.p[pi], idx % tiles, idx / tiles, t8_smem);
 }
+// its fp8 flavour (gemm_tn8p.h, FP8): the same placement table and riders; AF = the format of A (every problem of a launch)
+struct T8GroupF8 { T8ItemF8 p[AP_TN_MAX_GROUP]; int tiles[AP_TN_MAX_GROUP]; };
+static_assert(sizeof(T8GroupF8) + sizeof(T8Map) + sizeof(TnLn) <= 4096, "kernel arguments of k_gemm_tn_8p_fp8");
+template <int AF>
+__global__ void __launch_bounds__(512, 2)
+k_gemm_tn_8p_fp8(T8GroupF8 grp, T8Map map, TnLn ln) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char t8_smem[];
+    if ((int)blockIdx.x >= ln.first) { tn_ln_role(ln, (int)blockIdx.x - ln.first, reinterpret_cast<float*>(t8_smem)); return; }
+    const unsigned e = map.e[blockIdx.x];
+    if (e == TN_MAP_IDLE) return;
+    const int pi = e >> T8_MAP_SHIFT, idx = e & ((1u << T8_MAP_SHIFT) - 1u), tiles = grp.tiles[pi];
+    t8_item<true, AF>(grp.p[pi], idx % tiles, idx / tiles, t8_smem);
+}
 
 // one weight gradient whose B rows are patches of an NHWC feature map (PatchMap): a k x k / stride k convolution's dW
 template <bool BBN>
@@ -757,6 +773,24 @@ k_tn_reduce(TnGroup grp) {
             }
         }
     }
+}
+
+
+// the fp8 weight-gradient kernel (gemm_tn_fp8.h): workgroups [start, start + tiles * splits) of the launch belong to problem i (split-major),
+// the LayerNorm riders behind them
+struct TfGroup { TfItem p[AP_TN_MAX_GROUP]; int count; };
+static_assert(sizeof(TfGroup) + sizeof(TnLn) <= 4096, "kernel arguments of k_gemm_tn_fp8");
+__global__ void __launch_bounds__(256)
+k_gemm_tn_fp8(TfGroup grp, TnLn ln) {
+    __shared__ __attribute__((aligned(16))) unsigned char tf_smem[32768];
+    if ((int)blockIdx.x >= ln.first) { tn_ln_role(ln, (int)blockIdx.x - ln.first, reinterpret_cast<float*>(tf_smem)); return; }
+    int pi = 0;
+    for (int i = 1; i < AP_TN_MAX_GROUP; ++i)
+        if (i < grp.count && (int)blockIdx.x >= grp.p[i].start) pi = i;
+    const TfItem& it = grp.p[pi];
+    const int local = (int)blockIdx.x - it.start;
+    if (it.a_fmt == AP_FP8_E5M2) tf_tile<AP_FP8_E5M2>(it, local % it.tiles, local / it.tiles, tf_smem);
+    else tf_tile<AP_FP8_E4M3>(it, local % it.tiles, local / it.tiles, tf_smem);
 }
 
 
@@ -1487,6 +1521,184 @@ static int tn_grouped_128(const ap_tn_problem* problems, int count, const ap_ln_
         if (rc2 != AP_OK) return rc2;
     }
     if (workspace) hipLaunchKernelGGL(k_tn_reduce, dim3(1024), dim3(256), 0, (hipStream_t)stream, grp);
+    return ap_check_launch();
+}
+
+// ---- fp8 weight gradients (gemm_tn_fp8.h)
+static int tf_plan(const ap_tn8_problem* problems, int count, TfGroup& grp, int& blocks, size_t& slab_floats) {
+    if (!problems) return AP_ERR_NULL;
+    if (count <= 0 || count > AP_TN_MAX_GROUP) return AP_ERR_SHAPE;
+    for (int i = 0; i < count; ++i) {
+        const ap_tn8_problem& q = problems[i];
+        if (!q.A || !q.B || !q.C || !q.dq_a || !q.dq_b) return AP_ERR_NULL;
+        if (q.M <= 0 || q.N1 <= 0 || q.N2 <= 0) return AP_ERR_SHAPE;
+        if ((q.lda & 15) || (q.ldb & 15) || q.lda < q.N1 || q.ldb < q.N2 || q.ldc < q.N2) return AP_ERR_SHAPE;
+        if ((reinterpret_cast<uintptr_t>(q.A) & 15) || (reinterpret_cast<uintptr_t>(q.B) & 15)) return AP_ERR_SHAPE;
+        if (q.N1 % 128 || q.N2 % 128 || (q.a_fmt != AP_FP8_E5M2 && q.a_fmt != AP_FP8_E4M3)) return AP_ERR_UNSUPPORTED;
+    }
+    // resident capacity: two 256-thread workgroups per CU (32 KB of LDS each); the smallest K-steps per workgroup (>= 4) that fits it once
+    static int capacity = 0;
+    if (capacity == 0) {
+        int dev = 0; (void)hipGetDevice(&dev); hipDeviceProp_t pr;
+        capacity = 2 * ((hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256);
+    }
+    int max_k = 1;
+    for (int i = 0; i < count; ++i) max_k = std::max(max_k, (problems[i].M + 127) / 128);
+    auto blocks_at = [&](int sps) {
+        int64_t nb = 0;
+        for (int i = 0; i < count; ++i) {
+            const ap_tn8_problem& q = problems[i];
+            nb += (int64_t)(q.N1 / 128) * (q.N2 / 128) * (((q.M + 127) / 128 + sps - 1) / sps);
+        }
+        return nb;
+    };
+    // K-steps per workgroup: the smallest time in rounds of resident workgroups, ceil(blocks / capacity) * (sps + 4) (the 4: a partial tile's
+    // epilogue and its atomics in K-step units) -- a launch with more tiles than resident slots is cut along the tokens too, so its last
+    // round is not a nearly empty second wave of whole-axis workgroups
+    int lo = 4;
+    int64_t best = -1;
+    for (int sps = 4; sps <= std::max(max_k, 4); ++sps) {
+        const int64_t nb = blocks_at(sps), cost = ((nb + capacity - 1) / capacity) * (sps + 4);
+        if (best < 0 || cost < best) { best = cost; lo = sps; }
+    }
+    grp.count = count;
+    int start = 0;
+    slab_floats = 0;
+    for (int i = 0; i < count; ++i) {
+        const ap_tn8_problem& q = problems[i];
+        TfItem& t = grp.p[i];
+        const int ksteps = (q.M + 127) / 128;
+        int splits = (ksteps + lo - 1) / lo;
+        const int sps = (ksteps + splits - 1) / splits;
+        splits = (ksteps + sps - 1) / sps;
+        t.A = q.A; t.B = q.B; t.C = q.C; t.slab = nullptr; t.dq_a = q.dq_a; t.dq_b = q.dq_b;
+        t.lda = q.lda; t.ldb = q.ldb; t.ldc = q.ldc; t.M = q.M; t.N1 = q.N1; t.N2 = q.N2;
+        t.t2 = q.N2 / 128; t.ksteps = ksteps; t.ksps = sps; t.splits = splits; t.tiles = (q.N1 / 128) * (q.N2 / 128);
+        t.start = start; t.alpha = q.alpha != 0.0f ? q.alpha : 1.0f; t.a_fmt = q.a_fmt;
+        t.shared_out = 0;
+        for (int j = 0; j < count; ++j)
+            if (j != i && problems[j].C == q.C) t.shared_out = 1;
+        slab_floats += (size_t)splits * q.N1 * q.N2;
+        start += t.tiles * splits;
+    }
+    for (int i = count; i < AP_TN_MAX_GROUP; ++i) { grp.p[i] = grp.p[0]; grp.p[i].start = 0x7fffffff; }
+    blocks = start;
+    return AP_OK;
+}
+
+size_t ap_gemm_tn8_grouped_workspace(const ap_tn8_problem* problems, int count) {
+    TfGroup grp; int blocks = 0; size_t fl = 0;
+    if (tf_plan(problems, count, grp, blocks, fl) != AP_OK) return 0;
+    return fl * sizeof(float);
+}
+
+int ap_gemm_tn8_acc_grouped(const ap_tn8_problem* problems, int count, void* workspace, size_t ws_bytes, ap_stream_t stream) {
+    return ap_gemm_tn8_acc_grouped_ln(problems, count, nullptr, 0, workspace, ws_bytes, stream);
+}
+
+// the 8-phase fp8 flavour: widths multiples of 192, whole 128-token K-tiles, M >= 4096, one A format per launch (AP_GEMM_TN_8P=0: off)
+static bool tf8_fits(const ap_tn8_problem& q, int a_fmt) {
+    static int enabled = -1;
+    if (enabled < 0) { const char* e = getenv("AP_GEMM_TN_8P"); enabled = e ? atoi(e) : 1; }
+    return enabled && q.a_fmt == a_fmt && q.N1 % 192 == 0 && q.N2 % 192 == 0 && q.M % 128 == 0 && q.M >= 4096;
+}
+// as tn8_plan: the token axis cut into ranges of ksps 128-token K-tiles, the smallest that leaves at most one item per CU and fits t8_place
+static bool tf8_plan(const ap_tn8_problem* problems, int count, int n_cu, T8GroupF8& g8, T8Map& map, int& mblocks) {
+    int64_t work = 0; int max_k = 1;
+    for (int i = 0; i < count; ++i) {
+        const ap_tn8_problem& q = problems[i];
+        if (!tf8_fits(q, problems[0].a_fmt)) return false;
+        work += (int64_t)(q.N1 / 192) * (q.N2 / 192) * (q.M / 128);
+        max_k = std::max(max_k, q.M / 128);
+    }
+    int ksps = std::max(4, (int)((work + n_cu - 1) / n_cu));
+    T8Plan pl[AP_TN_MAX_GROUP];
+    for (; ksps <= max_k; ++ksps) {
+        int64_t items = 0;
+        for (int i = 0; i < count; ++i) {
+            const int ksteps = problems[i].M / 128;
+            pl[i].tiles = (problems[i].N1 / 192) * (problems[i].N2 / 192); pl[i].splits = (ksteps + ksps - 1) / ksps;
+            items += (int64_t)pl[i].tiles * pl[i].splits;
+        }
+        if (items <= n_cu && t8_place(pl, count, n_cu / 8, map, mblocks)) break;
+    }
+    if (ksps > max_k) return false;
+    for (int i = 0; i < count; ++i) {
+        const ap_tn8_problem& q = problems[i];
+        T8ItemF8& t = g8.p[i];
+        t.A = q.A; t.B = q.B; t.C = q.C; t.dq_a = q.dq_a; t.dq_b = q.dq_b;
+        t.lda = q.lda; t.ldb = q.ldb; t.ldc = q.ldc; t.M = q.M; t.t2 = q.N2 / 192; t.ksteps = q.M / 128; t.ksps = ksps;
+        t.alpha = q.alpha != 0.0f ? q.alpha : 1.0f;
+        g8.tiles[i] = pl[i].tiles;
+        t.shared_out = 0;
+        for (int j = 0; j < count; ++j)
+            if (j != i && problems[j].C == q.C) t.shared_out = 1;
+    }
+    for (int i = count; i < AP_TN_MAX_GROUP; ++i) { g8.p[i] = g8.p[0]; g8.tiles[i] = 1; }
+    return true;
+}
+
+int ap_gemm_tn8_acc_grouped_ln(const ap_tn8_problem* problems, int count, const ap_ln_reduce* ln_items, int ln_count,
+                               void* workspace, size_t ws_bytes, ap_stream_t stream) {
+    if (ln_count < 0 || ln_count > AP_LN_MAX_BATCH || (ln_count > 0 && !ln_items)) return AP_ERR_SHAPE;
+    for (int i = 0; i < ln_count; ++i) {
+        if (!ln_items[i].partial || !ln_items[i].dgamma || !ln_items[i].dbeta) return AP_ERR_NULL;
+        if (ln_items[i].n_partial <= 0 || ln_items[i].C <= 0) return AP_ERR_SHAPE;
+    }
+    TfGroup grp; int blocks = 0; size_t fl = 0;
+    const int rc = tf_plan(problems, count, grp, blocks, fl);         // (validates every problem)
+    if (rc != AP_OK) return rc;
+    TnLn ln;
+    int lblocks = 0;
+    for (int i = 0; i < AP_LN_MAX_BATCH; ++i) {
+        if (i < ln_count) {
+            const ap_ln_reduce& q = ln_items[i];
+            ln.it[i] = TnLnItem{q.partial, q.dgamma, q.dbeta, q.n_partial, q.C}; lblocks += (2 * q.C + 31) / 32;
+        } else ln.it[i] = TnLnItem{nullptr, nullptr, nullptr, 0, 0};
+    }
+    ln.count = ln_count;
+    if (!workspace) {                                 // atomic mode: the 8-phase flavour when every problem fits it
+        static int n_cu = 0;
+        if (n_cu == 0) {
+            int dev = 0; (void)hipGetDevice(&dev); hipDeviceProp_t pr;
+            n_cu = (hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256;
+            (void)hipFuncSetAttribute((const void*)k_gemm_tn_8p_fp8<AP_FP8_E4M3>, hipFuncAttributeMaxDynamicSharedMemorySize, T8_LDS_BYTES);
+            (void)hipFuncSetAttribute((const void*)k_gemm_tn_8p_fp8<AP_FP8_E5M2>, hipFuncAttributeMaxDynamicSharedMemorySize, T8_LDS_BYTES);
+            (void)hipGetLastError();
+        }
+        T8GroupF8 g8; T8Map map8; int mb8 = 0;
+        if (tf8_plan(problems, count, n_cu, g8, map8, mb8)) {
+            ln.first = mb8;
+            (void)hipGetLastError();
+            if (problems[0].a_fmt == AP_FP8_E5M2)
+                hipLaunchKernelGGL(k_gemm_tn_8p_fp8<AP_FP8_E5M2>, dim3(mb8 + lblocks), dim3(512), T8_LDS_BYTES, (hipStream_t)stream, g8, map8, ln);
+            else
+                hipLaunchKernelGGL(k_gemm_tn_8p_fp8<AP_FP8_E4M3>, dim3(mb8 + lblocks), dim3(512), T8_LDS_BYTES, (hipStream_t)stream, g8, map8, ln);
+            return ap_check_launch();
+        }
+    }
+    if (workspace) {                                  // deterministic: stored partial tiles + ordered reduce instead of fp32 atomics
+        if (ws_bytes < fl * sizeof(float)) return AP_ERR_SHAPE;
+        float* w = reinterpret_cast<float*>(workspace);
+        for (int i = 0; i < count; ++i) { grp.p[i].slab = w; w += (size_t)grp.p[i].splits * grp.p[i].N1 * grp.p[i].N2; }
+    }
+    ln.first = blocks;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_gemm_tn_fp8, dim3(blocks + lblocks), dim3(256), 0, (hipStream_t)stream, grp, ln);
+    if (workspace) {                                  // the ordered sum of the splits: k_tn_reduce, TN_MAX_GROUP problems per launch
+        for (int i0 = 0; i0 < count; i0 += TN_MAX_GROUP) {
+            TnGroup rg;
+            rg.count = std::min(TN_MAX_GROUP, count - i0);
+            for (int i = 0; i < TN_MAX_GROUP; ++i) {
+                const TfItem& t = grp.p[i0 + std::min(i, rg.count - 1)];
+                TnArgs& a = rg.p[i];
+                memset(&a, 0, sizeof(a));
+                a.C = t.C; a.ldc = t.ldc; a.N1 = t.N1; a.N2 = t.N2; a.slab = t.slab; a.splits = t.splits; a.colsum = nullptr;
+                a.start = i < rg.count ? 0 : 0x7fffffff;
+            }
+            hipLaunchKernelGGL(k_tn_reduce, dim3(1024), dim3(256), 0, (hipStream_t)stream, rg);
+        }
+    }
     return ap_check_launch();
 }
 

@@ -44,6 +44,30 @@ struct T8Item {            // one problem of a grouped launch
     float alpha, cs_scale;
     int shared_out;                                  // another problem of the launch adds to the same C / column sum: atomics even when unsplit
 };
+// the fp8 flavour's problem (weight gradients of configs[4]: A = dL/dy as e5m2 / e4m3 bytes, B = the layer input as e4m3 bytes): the same
+// fields without the column sum (ap_quantize_bf8 forms the bias gradient) and with the two device dequantisation scalars
+struct T8ItemF8 {
+    const unsigned char* A; const unsigned char* B; float* C; const float* dq_a; const float* dq_b;
+    int lda, ldb, ldc, M, t2, ksteps, ksps;          // ksteps: 128-token K-tiles
+    float alpha;
+    int shared_out;
+};
+__device__ __forceinline__ float* t8_colsum(const T8Item& it) { return it.colsum; }
+__device__ __forceinline__ float* t8_colsum(const T8ItemF8&) { return nullptr; }
+__device__ __forceinline__ const bf16_t* t8_csw(const T8Item& it) { return it.cs_weight; }
+__device__ __forceinline__ const bf16_t* t8_csw(const T8ItemF8&) { return nullptr; }
+__device__ __forceinline__ float t8_cs_scale(const T8Item& it) { return it.cs_scale; }
+__device__ __forceinline__ float t8_cs_scale(const T8ItemF8&) { return 1.f; }
+__device__ __forceinline__ float t8_alpha(const T8Item& it) { return it.alpha; }
+__device__ __forceinline__ float t8_alpha(const T8ItemF8& it) { return it.alpha * it.dq_a[0] * it.dq_b[0]; }
+// FP8 (T8ItemF8): the same ring, LDS budget, DMA pieces and schedule on bytes.  A K-tile is 128 tokens (= the bytes of a 64-token bf16
+// K-tile), a part 64 tokens, a column block 64 columns = 64 bytes per token, a piece [16 tok][64 B]; inside a piece, 16-byte chunk c of
+// token row r sits at position c ^ f8(t), f8(t) = ((r >> 2) & 1) | ((piece & 1) << 1) (the 16 rows one half-wave's ds_read_b64_tr_b8
+// reads land in 16 different bank slots).  A lane group reads tokens 16 g + (0..15) of a part (two transposed 8-token reads); the even
+// part's 16 bytes are held, the odd part's complete the 32 bytes of one v_mfma_scale_f32_16x16x128_f8f6f4 (A format AF, B e4m3, unit
+// scales): the MFMAs run in every second phase, twice the tokens per MFMA cycle of the bf16 form.
+typedef int __attribute__((ext_vector_type(8))) t8_i32x8;
+#define T8_READ8(lo, hi, addr, off) asm volatile("ds_read_b64_tr_b8 %0, %2 offset:%3\n\tds_read_b64_tr_b8 %1, %2 offset:%4" : "=&v"(lo), "=&v"(hi) : "v"(addr), "i"(off), "i"((off) + 512) : "memory")
 
 // The transposed reads are inline asm: behind a pending LDS-DMA hipcc guards every LDS read it can see with s_waitcnt vmcnt(0)
 // (it did so in front of the first ds_read_b64_tr_b16 of every phase), which drains the ring.  lgkmcnt is counted by hand.
@@ -54,7 +78,8 @@ __device__ __forceinline__ bf16x8 t8_join(const u32x2& lo, const u32x2& hi) {
 }
 
 // it: the problem; tile, split: which 192 x 192 tile and which token range
-__device__ __forceinline__ void t8_item(const T8Item& it, int tile, int split, unsigned char* smem) {
+template <bool FP8 = false, int AF = 0, class Item = T8Item>
+__device__ __forceinline__ void t8_item(const Item& it, int tile, int split, unsigned char* smem) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int w1 = wave >> 2, w2 = wave & 3;
@@ -66,31 +91,35 @@ __device__ __forceinline__ void t8_item(const T8Item& it, int tile, int split, u
     const int nparts = 2 * nkt;
 
     // ---- DMA source: this wave's pieces are token rows 8 * (wave & 3) + rr of a part, all three column blocks of ONE operand
-    const int rr = lane >> 3, pt = wave & 3;
-    const int f_src = ((((rr >> 1) & 1) | ((pt & 1) << 1)) << 1);
-    const int chunk = (lane & 7) ^ f_src;
+    // (FP8: token rows 16 * (wave & 3) + rr of a 64-token part, 64 bytes per row and column block)
+    constexpr int ES = FP8 ? 1 : 2;                                                // bytes per element
+    const int rr = FP8 ? lane >> 2 : lane >> 3, pt = wave & 3;
+    const int f_src = FP8 ? (((rr >> 2) & 1) | ((pt & 1) << 1)) : ((((rr >> 1) & 1) | ((pt & 1) << 1)) << 1);
+    const int chunk = FP8 ? ((lane & 3) ^ f_src) : ((lane & 7) ^ f_src);
     const bool opB = w1 != 0;
     const int64_t ld = opB ? it.ldb : it.lda;
-    const bf16_t* src = (opB ? it.B + n2_0 : it.A + n1_0) + ((int64_t)kt_begin * 64 + pt * 8 + rr) * ld + chunk * 8;
-    const int64_t part_stride = 32 * ld;
+    const unsigned char* src = reinterpret_cast<const unsigned char*>(opB ? (const void*)it.B : (const void*)it.A) +
+                               ((int64_t)(opB ? n2_0 : n1_0) + ((int64_t)kt_begin * (FP8 ? 128 : 64) + pt * (FP8 ? 16 : 8) + rr) * ld) * ES + chunk * 16;
+    const int64_t part_stride = (FP8 ? 64 : 32) * ld * ES;
+    constexpr int CB = 64 * ES;                                                    // bytes of a column block per token
     unsigned char* const dst0 = smem + (opB ? 24576 : 0) + pt * 1024;             // + slot*49152 + kb*4096 + cb*8192
     // per-token weights of a fused, masked column sum: the waves that own a column sum bring their part's 32 weights into a corner
-    const bool cs_wave = it.colsum != nullptr && i2 == 0 && w2 == 0;
-    const bool cs_w = cs_wave && it.cs_weight != nullptr;
+    const bool cs_wave = t8_colsum(it) != nullptr && i2 == 0 && w2 == 0;
+    const bool cs_w = cs_wave && t8_csw(it) != nullptr;
     unsigned char* const wcorner = smem + T8_RING + w1 * 1536;
     const unsigned smem_a = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
     const unsigned wcorner_a = smem_a + T8_RING + w1 * 1536;
-    const bf16_t* wsrc = it.cs_weight ? it.cs_weight + (int64_t)kt_begin * 64 + min(2 * lane, 30) : nullptr;
+    const bf16_t* wsrc = t8_csw(it) ? t8_csw(it) + (int64_t)kt_begin * 64 + min(2 * lane, 30) : nullptr;
     // the running source pointer of the part that goes out next; ring slot of part P = P % 6 (K-tile slot (P % 6) >> 1, k-step P & 1)
-    const bf16_t* nsrc = src;
+    const unsigned char* nsrc = src;
     const bf16_t* nwsrc = wsrc;
     int issued = 0;
     auto issue_to = [&](int slot, bool with_w) {
         if (!(T8_ABL & 4)) {
             unsigned char* d = dst0 + (slot >> 1) * 49152 + (slot & 1) * 4096;
             __builtin_amdgcn_global_load_lds(T8_GLB(nsrc), T8_LDS(d), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds(T8_GLB(nsrc + 64), T8_LDS(d + 8192), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds(T8_GLB(nsrc + 128), T8_LDS(d + 16384), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(T8_GLB(nsrc + CB), T8_LDS(d + 8192), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(T8_GLB(nsrc + 2 * CB), T8_LDS(d + 16384), 16, 0, 0);
             if (with_w) __builtin_amdgcn_global_load_lds(T8_GLB(nwsrc), T8_LDS(wcorner + slot * 256), 4, 0, 0);
         }
         nsrc += part_stride; nwsrc += 32;
@@ -103,10 +132,22 @@ __device__ __forceinline__ void t8_item(const T8Item& it, int tile, int split, u
     const int lane_rd = g * 1024 + q * 128 + p * 8;
     // two address registers per fragment: K-tile slots 0 / 1 are immediates away from the first (ds offsets are 16 bits), slot 2 from the second
     unsigned offA[6], offB[3], offA2[6], offB2[3];
+    if constexpr (FP8) {
+        // lane = 16 g + 2 q + p reads token row q (+ 8: the second read) of piece g, bytes 8 p .. 8 p + 7 of a 16-column chunk
+        const int q8 = (lane >> 1) & 7, p8 = lane & 1;
+        const int f8 = ((q8 >> 2) & 1) | ((g & 1) << 1);                          // f8 of rows q8 and q8 + 8 of piece g
+        const int lane8 = g * 1024 + q8 * 64 + p8 * 8;
 #pragma unroll
-    for (int t = 0; t < 6; ++t) { const int T = w1 * 6 + t; offA[t] = smem_a + (T >> 2) * 8192 + ((((T & 3) * 2) ^ f_rd) << 4) + lane_rd; offA2[t] = offA[t] + 98304; }
+        for (int t = 0; t < 6; ++t) { const int T = w1 * 6 + t; offA[t] = smem_a + (T >> 2) * 8192 + (((T & 3) ^ f8) << 4) + lane8; offA2[t] = offA[t] + 98304; }
 #pragma unroll
-    for (int t = 0; t < 3; ++t) { const int T = w2 * 3 + t; offB[t] = smem_a + 24576 + (T >> 2) * 8192 + ((((T & 3) * 2) ^ f_rd) << 4) + lane_rd; offB2[t] = offB[t] + 98304; }
+        for (int t = 0; t < 3; ++t) { const int T = w2 * 3 + t; offB[t] = smem_a + 24576 + (T >> 2) * 8192 + (((T & 3) ^ f8) << 4) + lane8; offB2[t] = offB[t] + 98304; }
+    } else {
+#pragma unroll
+        for (int t = 0; t < 6; ++t) { const int T = w1 * 6 + t; offA[t] = smem_a + (T >> 2) * 8192 + ((((T & 3) * 2) ^ f_rd) << 4) + lane_rd; offA2[t] = offA[t] + 98304; }
+#pragma unroll
+        for (int t = 0; t < 3; ++t) { const int T = w2 * 3 + t; offB[t] = smem_a + 24576 + (T >> 2) * 8192 + ((((T & 3) * 2) ^ f_rd) << 4) + lane_rd; offB2[t] = offB[t] + 98304; }
+    }
+    u32x4 ha[6], hb[3];                       // FP8: the even part's half of each fragment, held for the odd part's MFMA
 
     f32x4 acc[6][3], csum[6];
 #pragma unroll
@@ -137,6 +178,11 @@ __device__ __forceinline__ void t8_item(const T8Item& it, int tile, int split, u
             for (int t = 0; t < 3; ++t) { blo[t] = u32x2{offB[t], 1u}; bhi[t] = u32x2{2u, offB[t]}; }
 #pragma unroll
             for (int t = 0; t < 6; ++t) { alo[t] = u32x2{offA[t], 3u}; ahi[t] = u32x2{4u, offA[t]}; }
+        } else if constexpr (FP8) {
+#pragma unroll
+            for (int t = 0; t < 3; ++t) T8_READ8(blo[t], bhi[t], (S >> 1) == 2 ? offB2[t] : offB[t], OFF);
+#pragma unroll
+            for (int t = 0; t < 6; ++t) T8_READ8(alo[t], ahi[t], (S >> 1) == 2 ? offA2[t] : offA[t], OFF);
         } else {
 #pragma unroll
             for (int t = 0; t < 3; ++t) T8_READ(blo[t], bhi[t], (S >> 1) == 2 ? offB2[t] : offB[t], OFF);
@@ -157,6 +203,42 @@ __device__ __forceinline__ void t8_item(const T8Item& it, int tile, int split, u
         for (int t = 0; t < 6; ++t) asm volatile("" : "+v"(alo[t]), "+v"(ahi[t]));
         asm volatile("" : "+v"(wv));
         T8_FENCE();
+        if constexpr (FP8) {
+            if constexpr ((S & 1) == 0) {           // the even part: hold the first 16 bytes, issue the DMA, no MFMA
+#pragma unroll
+                for (int t = 0; t < 3; ++t) hb[t] = u32x4{blo[t][0], blo[t][1], bhi[t][0], bhi[t][1]};
+#pragma unroll
+                for (int t = 0; t < 6; ++t) ha[t] = u32x4{alo[t][0], alo[t][1], ahi[t][0], ahi[t][1]};
+                T8_FENCE();
+                if constexpr (STEADY) issue_to((S + 4) % 6, false);
+                else { if (issued < nparts) issue_to((S + 4) % 6, false); }
+                T8_FENCE();
+                T8_BAR();
+                return;
+            }
+            t8_i32x8 af8[6], bf8[3];
+#pragma unroll
+            for (int t = 0; t < 3; ++t) bf8[t] = t8_i32x8{(int)hb[t][0], (int)hb[t][1], (int)hb[t][2], (int)hb[t][3], (int)blo[t][0], (int)blo[t][1], (int)bhi[t][0], (int)bhi[t][1]};
+#pragma unroll
+            for (int t = 0; t < 6; ++t) af8[t] = t8_i32x8{(int)ha[t][0], (int)ha[t][1], (int)ha[t][2], (int)ha[t][3], (int)alo[t][0], (int)alo[t][1], (int)ahi[t][0], (int)ahi[t][1]};
+            __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 3; ++b) acc[a][b] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af8[a], bf8[b], acc[a][b], AF, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+            T8_FENCE();
+            if constexpr (STEADY) issue_to((S + 4) % 6, false);
+            else { if (issued < nparts) issue_to((S + 4) % 6, false); }
+            T8_FENCE();
+#pragma unroll
+            for (int a = 2; a < 6; ++a)
+#pragma unroll
+                for (int b = 0; b < 3; ++b) acc[a][b] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af8[a], bf8[b], acc[a][b], AF, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+            __builtin_amdgcn_s_setprio(0);
+            T8_FENCE();
+            T8_BAR();
+            return;
+        }
         bf16x8 af[6], bfr[3];
 #pragma unroll
         for (int t = 0; t < 3; ++t) bfr[t] = t8_join(blo[t], bhi[t]);
@@ -218,7 +300,8 @@ __device__ __forceinline__ void t8_item(const T8Item& it, int tile, int split, u
     T8_FENCE();
     T8_BAR();
     if (w1 == 1) T8_BAR();                    // the second wave group runs one barrier behind the first
-    if (cs_w) run(Yes{}, Yes{}); else if (cs_wave) run(Yes{}, No{}); else run(No{}, No{});
+    if constexpr (FP8) run(No{}, No{});
+    else { if (cs_w) run(Yes{}, Yes{}); else if (cs_wave) run(Yes{}, No{}); else run(No{}, No{}); }
     if (w1 == 0) T8_BAR();
 
     // ---- partial tile -> C (4 rows x 64 bytes per wave-instruction)
@@ -231,7 +314,8 @@ __device__ __forceinline__ void t8_item(const T8Item& it, int tile, int split, u
         return;
     }
     float* const crow = it.C + (int64_t)(n1_0 + w1 * 96 + 4 * g) * it.ldc + n2_0 + w2 * 48 + fr;
-    const float sc = it.cs_weight ? it.cs_scale : 1.0f;
+    const float sc = t8_csw(it) ? t8_cs_scale(it) : 1.0f;
+    const float alpha = t8_alpha(it);
     if (it.ksps >= it.ksteps && !it.shared_out) {
         // the item is the problem's whole token axis: nobody else adds to this tile, so C += is a plain read-add-store (the chip adds
         // 1.3 TB/s of fp32 atomics against ~6 TB/s of stores, and a launch holds one 144 KB tile per CU whatever it is cut into)
@@ -245,13 +329,13 @@ __device__ __forceinline__ void t8_item(const T8Item& it, int tile, int split, u
 #pragma unroll
             for (int b = 0; b < 3; ++b)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) __builtin_nontemporal_store(fmaf(acc[a][b][r], it.alpha, old[b][r]), crow + (int64_t)(a * 16 + r) * it.ldc + b * 16);
+                for (int r = 0; r < 4; ++r) __builtin_nontemporal_store(fmaf(acc[a][b][r], alpha, old[b][r]), crow + (int64_t)(a * 16 + r) * it.ldc + b * 16);
         }
         if (cs_wave && fr == 0) {
 #pragma unroll
             for (int a = 0; a < 6; ++a)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { float* q = it.colsum + n1_0 + w1 * 96 + a * 16 + 4 * g + r; *q = fmaf(csum[a][r], sc, *q); }
+                for (int r = 0; r < 4; ++r) { float* q = t8_colsum(it) + n1_0 + w1 * 96 + a * 16 + 4 * g + r; *q = fmaf(csum[a][r], sc, *q); }
         }
         return;
     }
@@ -260,11 +344,11 @@ __device__ __forceinline__ void t8_item(const T8Item& it, int tile, int split, u
 #pragma unroll
         for (int b = 0; b < 3; ++b)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) atomicAdd(crow + (int64_t)(a * 16 + r) * it.ldc + b * 16, acc[a][b][r] * it.alpha);
+            for (int r = 0; r < 4; ++r) atomicAdd(crow + (int64_t)(a * 16 + r) * it.ldc + b * 16, acc[a][b][r] * alpha);
     if (cs_wave && fr == 0) {
 #pragma unroll
         for (int a = 0; a < 6; ++a)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) atomicAdd(it.colsum + n1_0 + w1 * 96 + a * 16 + 4 * g + r, csum[a][r] * sc);
+            for (int r = 0; r < 4; ++r) atomicAdd(t8_colsum(it) + n1_0 + w1 * 96 + a * 16 + 4 * g + r, csum[a][r] * sc);
     }
 }

@@ -397,15 +397,22 @@ def _gelu_side_buffer(rows, cols, device):
 
 
 def _linear_bwd(g, x_in, w, dw, db, n=None, dgelu_of=None, need_dx=True, row_scale=None, rows_per_scale=1, cs_weight=None, inv_keep=1.0, mul_by=None,
-                q8=None, g8=None):
+                q8=None, g8=None, x8=None):
     """shared backward of y = x W^T + b given g = dL/dy (bf16 [M, ld]); accumulates dw/db.
     DropPath (the branch output is scaled per sample by s = mask/keep and x_in has the rows of dropped samples zeroed): pass
     row_scale = s (the input gradient gets it in the GEMM epilogue), cs_weight = per-token 0/1 mask and inv_keep = 1/keep:
-    dW = inv_keep * g^T x_in and db = inv_keep * sum_m mask[m] g[m] -- g itself is never scaled."""
+    dW = inv_keep * g^T x_in and db = inv_keep * sum_m mask[m] g[m] -- g itself is never scaled.
+    x8 = (e4m3 bytes of x_in, dq) (FP8_WGRAD): the weight gradient on fp8 operands, g as e5m2 (x_in is not read and may be None)."""
     n = w.shape[0] if n is None else n
-    prob = (g, x_in, _g2(dw), n, _g2(dw).shape[1], db)
-    if cs_weight is not None:
-        prob = prob + (cs_weight, inv_keep, inv_keep)
+    if x8 is not None:
+        if g.shape[1] != n:
+            raise AutoProgHipError("fp8 weight gradient: dL/dy must be exactly out_features wide")
+        g8w, dq_g = fp8_scales.quantize_bf8(("gw", id(w)), g, colsum=db, colsum_weight=cs_weight, colsum_scale=inv_keep)
+        prob = ops.Tn8Problem(g8w, x8[0], _g2(dw), n, _g2(dw).shape[1], dq_g, x8[1], alpha=inv_keep if cs_weight is not None else 1.0)
+    else:
+        prob = (g, x_in, _g2(dw), n, _g2(dw).shape[1], db)
+        if cs_weight is not None:
+            prob = prob + (cs_weight, inv_keep, inv_keep)
     if _wgrad_batch is not None:
         _wgrad_batch.append(prob)
     else:
@@ -440,6 +447,12 @@ FP8_LINEAR = os.environ.get("AP_FP8", "0") == "1"
 # leaves the fc2 input-gradient launch a second time as e4m3 bytes (its epilogue, delayed scale of its own site), the transposed weight is
 # quantised with the forward copy's scale in the per-step weight launch.  AP_FP8_DGRAD=0: forward products only (round 4).
 FP8_DGRAD = os.environ.get("AP_FP8_DGRAD", "1") != "0"
+# The WEIGHT gradients of the four Linear layers on fp8 operands as well (configs[4]: "e4m3 fwd / e5m2 grads"): the forward keeps the e4m3
+# copy of each layer input it made for its own product (and the dq it was quantised with) instead of the bf16 input, the backward quantises
+# dL/dy to e5m2 (ops.quantize_bf8, delayed scale of a gradient site; the bias gradient from the bf16 dL/dy in the same pass) and queues an
+# fp8 problem (ops.Tn8Problem) in place of the bf16 one.  Only with FP8_LINEAR, only where both widths are multiples of 128.  The input
+# gradients are not touched.  AP_FP8_WGRAD=1 switches it on (default off).
+FP8_WGRAD = os.environ.get("AP_FP8_WGRAD", "0") == "1"
 
 
 class _Fp8Scales:
@@ -454,6 +467,7 @@ class _Fp8Scales:
         self.amax = torch.zeros(self.CAP, dtype=torch.float32, device=device)
         self.scale = torch.ones(self.CAP, dtype=torch.float32, device=device)
         self.dq = torch.ones(self.CAP, dtype=torch.float32, device=device)
+        self.qmax = None              # per-slot format maximum once an e5m2 site exists (e4m3: ops.FP8_MAX, e5m2: ops.BF8_MAX)
         self.slots = {}
 
     def roll(self):
@@ -461,12 +475,14 @@ class _Fp8Scales:
         if self.amax is None:
             return
         seen = self.amax > 0
-        self.scale.copy_(torch.where(seen, ops.FP8_MAX / self.amax.clamp_min(1e-30), self.scale))
+        top = ops.FP8_MAX if self.qmax is None else self.qmax
+        self.scale.copy_(torch.where(seen, top / self.amax.clamp_min(1e-30), self.scale))
         self.dq.copy_(1.0 / self.scale)
         self.amax.zero_()
 
-    def site(self, key, x):
-        """-> slot index of the (per-tensor) quantisation site; a new site is scaled by the tensor in front of it"""
+    def site(self, key, x, top=None):
+        """-> slot index of the (per-tensor) quantisation site; a new site is scaled by the tensor in front of it.  top: the format's
+        largest value (None: e4m3)"""
         if self.amax is None or self.amax.device != x.device:
             self._init(x.device)
         if self.generation != _WeightBank.generation:          # an optimizer step has passed
@@ -478,14 +494,25 @@ class _Fp8Scales:
             if i >= self.CAP:
                 raise AutoProgHipError("fp8: more than %d quantisation sites" % self.CAP)
             self.slots[key] = i
+            top = ops.FP8_MAX if top is None else top
+            if top != ops.FP8_MAX:
+                if self.qmax is None:
+                    self.qmax = torch.full((self.CAP,), ops.FP8_MAX, dtype=torch.float32, device=x.device)
+                self.qmax[i] = top
             amax = x.detach().abs().amax().float().clamp_min(1e-12)
-            self.scale[i:i + 1].copy_((ops.FP8_MAX / amax).reshape(1))
-            self.dq[i:i + 1].copy_((amax / ops.FP8_MAX).reshape(1))
+            self.scale[i:i + 1].copy_((top / amax).reshape(1))
+            self.dq[i:i + 1].copy_((amax / top).reshape(1))
         return i
 
     def quantize(self, key, x):
         i = self.site(key, x)
         return ops.quantize_fp8(x, self.scale[i:i + 1], self.amax[i:i + 1]), self.dq[i:i + 1]
+
+    def quantize_bf8(self, key, g, colsum=None, colsum_weight=None, colsum_scale=1.0):
+        """an output gradient as e5m2 bytes (gradient site `key`), the bias gradient of the bf16 g in the same pass -> (bytes, dq)"""
+        i = self.site(key, g, top=ops.BF8_MAX)
+        y = ops.quantize_bf8(g, self.scale[i:i + 1], self.amax[i:i + 1], colsum=colsum, colsum_weight=colsum_weight, colsum_scale=colsum_scale)
+        return y, self.dq[i:i + 1]
 
     def producer(self, key, device):
         """(scale, amax, dq) of a site whose PRODUCER quantises (ops.layernorm_fwd(fp8=...)); None on the site's first use -- the
@@ -604,6 +631,16 @@ def _linear_fwd(x, w, x8=None, emit_for=None, **kw):
     return (y, None) if emit_for is not None else y
 
 
+def _wgrad8_ok(x, w):
+    """FP8_WGRAD applies to the Linear with weight w on input x"""
+    return FP8_WGRAD and _fp8_ok(x, w) and ops.gemm_tn8_ok(w.shape[0], w.shape[1])
+
+
+def _fp8_input(x, w, x8):
+    """(FP8_WGRAD) the e4m3 operand of the Linear with weight w -- what _linear_fwd quantises itself when the producer did not"""
+    return x8 if x8 is not None else fp8_scales.quantize(("x", id(w)), x)
+
+
 def _ln_fwd_for(x, gw, gb, eps, w):
     """LayerNorm whose output feeds the Linear with weight w: under FP8_LINEAR the kernel also emits the e4m3 operand"""
     if _fp8_ok(x, w):
@@ -644,6 +681,9 @@ class TransformerBlockFn(torch.autograd.Function):
         if rs2 is not None and k2 is None:
             k2 = (rs2 != 0).float()
         xn1, m1, r1, xq = _ln_fwd_for(x2, n1w, n1b, eps, qkv_w)
+        w8 = [None, None, None, None]     # FP8_WGRAD: (e4m3 input, dq) of qkv, proj, fc1, fc2 for the weight gradients
+        if _wgrad8_ok(xn1, qkv_w):
+            xq = w8[0] = _fp8_input(xn1, qkv_w, xq)
         qkv = _linear_fwd(xn1, qkv_w, x8=xq, bias=qkv_b)
         oq = None
         site = fp8_scales.producer(("x", id(proj_w)), x.device) if (FP8_LINEAR and ops.mhsa_emits_fp8(N, C // heads)) else None
@@ -652,6 +692,8 @@ class TransformerBlockFn(torch.autograd.Function):
             oq = (o8, site[2])
         else:
             o, lse = ops.mhsa_fwd(qkv, B, N, heads, scale, out_row_scale=k1)                   # rows of dropped samples: zeros
+        if _wgrad8_ok(o, proj_w):
+            oq = w8[1] = _fp8_input(o, proj_w, oq)
         x1 = _linear_fwd(o, proj_w, x8=oq, bias=proj_b, row_scale=rs1, rows_per_scale=N, residual=x2)
         fused = None
         use_fused = FUSED_MLP and STORE_GELU_GRAD == 2 and not FP8_LINEAR and B * N >= FUSED_MLP_MIN_ROWS and ops.mlp_fused_ok(B * N, C, fc1_w.shape[0])
@@ -670,22 +712,35 @@ class TransformerBlockFn(torch.autograd.Function):
                     y, a, h = fused
         if fused is None:
             h = _gelu_side_buffer(B * N, fc1_w.shape[0], x.device)
+            if _wgrad8_ok(xn2, fc1_w):
+                xq = w8[2] = _fp8_input(xn2, fc1_w, xq)
             a, aq = _linear_fwd(xn2, fc1_w, x8=xq, emit_for=fc2_w, bias=fc1_b, gelu=True, preact_out=h, preact_grad=STORE_GELU_GRAD, row_scale=k2, rows_per_scale=N)
+            if _wgrad8_ok(a, fc2_w):
+                aq = w8[3] = _fp8_input(a, fc2_w, aq)
             y = _linear_fwd(a, fc2_w, x8=aq, bias=fc2_b, row_scale=rs2, rows_per_scale=N, residual=x1)
         if rs1 is not None and tm1 is None:
             tm1 = token_mask(k1, N)
         if rs2 is not None and tm2 is None:
             tm2 = token_mask(k2, N)
+        if fused is None:
+            # a bf16 layer input that only its weight gradient reads is not kept once that gradient runs on the e4m3 copy
+            xn1 = None if w8[0] is not None else xn1
+            xn2 = None if w8[2] is not None else xn2
+            a = None if w8[3] is not None else a
+        # the e4m3 inputs go with the saved tensors; their dq (views of the scale vector, which later quantisation sites write) as attributes
         ctx.save_for_backward(x2, m1, r1, xn1, qkv, o, lse, x1, m2, r2, xn2, h, a, rs1, rs2, tm1, tm2,
-                              n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b)
+                              n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b,
+                              *[q[0] if q is not None else None for q in w8])
         ctx.cfg = (B, N, heads, scale, float(inv_keep))
+        ctx.w8dq = [q[1] if q is not None else None for q in w8]
         return y.view(x.shape)
 
     @staticmethod
     def backward(ctx, dy):
         (x2, m1, r1, xn1, qkv, o, lse, x1, m2, r2, xn2, h, a, rs1, rs2, tm1, tm2,
-         n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b) = ctx.saved_tensors
+         n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, *b8) = ctx.saved_tensors
         B, N, heads, scale, inv_keep = ctx.cfg
+        w8 = [(b, d) if b is not None else None for b, d in zip(b8, ctx.w8dq)]
         params = (n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b)
         bufs, sunk = _param_grad_buffers(params)
         (dn1w, dn1b, dqkv_w, dqkv_b, dproj_w, dproj_b, dn2w, dn2b, dfc1_w, dfc1_b, dfc2_w, dfc2_b) = bufs
@@ -700,10 +755,11 @@ class TransformerBlockFn(torch.autograd.Function):
                 site = fp8_scales.producer(("g", id(fc1_w)), dy2.device)
                 if site is not None and ops.gemm_nt_emits_q8(dy2.shape[0], h.shape[1], dy2.shape[1], h):
                     dh, d8 = _linear_bwd(dy2, a, fc2_w, dfc2_w, dfc2_b, row_scale=rs2, rows_per_scale=N, cs_weight=tm2, inv_keep=inv_keep,
-                                         q8=(site[0], site[1]), **_gelu_bwd_kw(h))
+                                         q8=(site[0], site[1]), x8=w8[3], **_gelu_bwd_kw(h))
                     dh8 = (d8, site[2])
                 else:
-                    dh = _linear_bwd(dy2, a, fc2_w, dfc2_w, dfc2_b, row_scale=rs2, rows_per_scale=N, cs_weight=tm2, inv_keep=inv_keep, **_gelu_bwd_kw(h))
+                    dh = _linear_bwd(dy2, a, fc2_w, dfc2_w, dfc2_b, row_scale=rs2, rows_per_scale=N, cs_weight=tm2, inv_keep=inv_keep, x8=w8[3],
+                                     **_gelu_bwd_kw(h))
                     dh8 = fp8_scales.quantize(("g", id(fc1_w)), dh)
             else:
                 fused = None
@@ -716,14 +772,15 @@ class TransformerBlockFn(torch.autograd.Function):
                     _linear_bwd(dy2, a, fc2_w, dfc2_w, dfc2_b, need_dx=False, cs_weight=tm2, inv_keep=inv_keep)
                     _linear_bwd(dh, xn2, fc1_w, dfc1_w, dfc1_b, need_dx=False)
                 else:
-                    dh = _linear_bwd(dy2, a, fc2_w, dfc2_w, dfc2_b, row_scale=rs2, rows_per_scale=N, cs_weight=tm2, inv_keep=inv_keep, **_gelu_bwd_kw(h))
+                    dh = _linear_bwd(dy2, a, fc2_w, dfc2_w, dfc2_b, row_scale=rs2, rows_per_scale=N, cs_weight=tm2, inv_keep=inv_keep, x8=w8[3],
+                                     **_gelu_bwd_kw(h))
             if dxn2 is None:
-                dxn2 = _linear_bwd(dh, xn2, fc1_w, dfc1_w, dfc1_b, g8=dh8)
+                dxn2 = _linear_bwd(dh, xn2, fc1_w, dfc1_w, dfc1_b, g8=dh8, x8=w8[2])
             dx1 = ops.layernorm_bwd(dxn2, x1, n2w, m2, r2, dy2, dn2w, dn2b, defer=batch.ln)
             # attention branch
-            do = _linear_bwd(dx1, o, proj_w, dproj_w, dproj_b, row_scale=rs1, rows_per_scale=N, cs_weight=tm1, inv_keep=inv_keep)
+            do = _linear_bwd(dx1, o, proj_w, dproj_w, dproj_b, row_scale=rs1, rows_per_scale=N, cs_weight=tm1, inv_keep=inv_keep, x8=w8[1])
             dqkv = ops.mhsa_bwd(qkv, o, do, lse, B, N, heads, scale)      # dropped samples: do = 0, so the masked rows of o do not matter
-            dxn1 = _linear_bwd(dqkv, xn1, qkv_w, dqkv_w, dqkv_b)
+            dxn1 = _linear_bwd(dqkv, xn1, qkv_w, dqkv_w, dqkv_b, x8=w8[0])
             dx = ops.layernorm_bwd(dxn1, x2, n1w, m1, r1, dx1, dn1w, dn1b, defer=batch.ln)
         return (dx.view(dy.shape), None, None, *_finish_param_grads(params, bufs, sunk, batch.deferred), None, None, None, None, None, None, None, None, None)
 

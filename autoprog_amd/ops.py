@@ -342,6 +342,84 @@ def quantize_fp8_multi(table, njobs, scales, amax):
           "ap_quantize_fp8_multi")
 
 
+BF8_MAX = 57344.0        # OCP e5m2
+
+
+def quantize_bf8(g, scale, amax=None, colsum=None, colsum_weight=None, colsum_scale=1.0):
+    """bf16 output gradient g [rows, cols] -> uint8 tensor of e5m2 bytes, y = sat(g * scale[0]); amax[0] = max(amax[0], max|g|).
+    colsum (fp32 [cols], optional): += colsum_scale * sum_r w[r] * g[r, :] of the UN-quantised g (the bias gradient, in the same pass),
+    w = colsum_weight (bf16 per-row weights, e.g. the DropPath token mask; None = ones, colsum_scale then unused).  Under
+    `deterministic` the row splits' sums are added in split order."""
+    from ._lib import BF8_COLSUM_SPLITS
+    _req(g, BF16, "g"); _req(scale, torch.float32, "scale")
+    y = torch.empty(g.shape, dtype=torch.uint8, device=g.device)
+    rows, cols = (g.shape[0], g.shape[1]) if g.dim() == 2 else (1, g.numel())
+    ws = None
+    if colsum is not None:
+        _req(colsum, torch.float32, "colsum")
+        if g.dim() != 2 or colsum.numel() < cols:
+            raise AutoProgHipError("quantize_bf8: colsum needs a 2-D g and cols entries")
+        if colsum_weight is not None:
+            _req(colsum_weight, BF16, "colsum_weight")
+            if colsum_weight.numel() < rows:
+                raise AutoProgHipError("quantize_bf8: colsum_weight needs one entry per row")
+        if deterministic:
+            ws = torch.empty(BF8_COLSUM_SPLITS * cols, dtype=torch.float32, device=g.device)
+    check(lib.ap_quantize_bf8(g.data_ptr(), y.data_ptr(), g.numel(), scale.data_ptr(), amax.data_ptr() if amax is not None else None,
+                              colsum.data_ptr() if colsum is not None else None, rows, cols,
+                              colsum_weight.data_ptr() if colsum_weight is not None else None, float(colsum_scale),
+                              ws.data_ptr() if ws is not None else None, _stream()), "ap_quantize_bf8")
+    return y
+
+
+def gemm_tn8_ok(n1, n2):
+    """widths the fp8 weight-gradient kernel takes (ap_gemm_tn8_acc_grouped): multiples of 128"""
+    return n1 % 128 == 0 and n2 % 128 == 0 and n1 > 0 and n2 > 0
+
+
+class Tn8Problem(tuple):
+    """an fp8 weight-gradient problem for gemm_tn8_acc_grouped / gemm_tn_acc_grouped: (a8, b8, c, n1, n2, None, dq_a, dq_b, alpha):
+    c[:n1, :n2] += alpha * dq_a[0] * dq_b[0] * a8^T b8 with a8 [M, n1] e5m2 bytes (a_fmt = FP8_E5M2; e4m3 with FP8_E4M3) and b8
+    [M, n2] e4m3 bytes; dq_* fp32 device scalars.  Slot 5 (a column sum) is always None: quantize_bf8 forms the bias gradient."""
+    a_fmt = 1
+
+    def __new__(cls, a8, b8, c, n1, n2, dq_a, dq_b, alpha=1.0, a_fmt=1):
+        self = super().__new__(cls, (a8, b8, c, n1, n2, None, dq_a, dq_b, alpha))
+        self.a_fmt = a_fmt
+        return self
+
+
+def gemm_tn8_acc_grouped(problems, ln=None):
+    """ONE launch of the fp8 weight-gradient kernel for a list of Tn8Problem (at most TN_MAX_GROUP); ln: deferred LayerNorm reductions
+    riding in the launch (at most LN_MAX_BATCH).  Deterministic mode as for gemm_tn_acc_grouped."""
+    from ._lib import Tn8Problem as _Tn8, TN_MAX_GROUP, LnReduce, LN_MAX_BATCH
+    ln = list(ln) if ln else []
+    if len(problems) > TN_MAX_GROUP or len(ln) > LN_MAX_BATCH:
+        raise AutoProgHipError("gemm_tn8_acc_grouped: at most %d problems and %d LayerNorm reductions" % (TN_MAX_GROUP, LN_MAX_BATCH))
+    arr = (_Tn8 * len(problems))()
+    for q, prob in zip(arr, problems):
+        a8, b8, c, n1, n2, _, dq_a, dq_b, alpha = prob
+        _req(a8, torch.uint8, "a8"); _req(b8, torch.uint8, "b8"); _req(c, torch.float32, "c")
+        _req(dq_a, torch.float32, "dq_a"); _req(dq_b, torch.float32, "dq_b")
+        if a8.shape[0] != b8.shape[0]:
+            raise ValueError("gemm_tn8_acc_grouped: token counts differ")
+        q.A, q.lda, q.B, q.ldb, q.C, q.ldc = a8.data_ptr(), a8.shape[1], b8.data_ptr(), b8.shape[1], c.data_ptr(), c.shape[1]
+        q.M, q.N1, q.N2 = a8.shape[0], (c.shape[0] if n1 is None else n1), (c.shape[1] if n2 is None else n2)
+        q.a_fmt, q.alpha, q.dq_a, q.dq_b = int(getattr(prob, "a_fmt", 1)), float(alpha), dq_a.data_ptr(), dq_b.data_ptr()
+    ptr = ctypes.cast(arr, ctypes.c_void_p)
+    ws, ws_bytes = None, 0
+    if deterministic:
+        ws_bytes = lib.ap_gemm_tn8_grouped_workspace(ptr, len(problems))
+        ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=problems[0][0].device)
+    larr = None
+    if ln:
+        larr = (LnReduce * len(ln))()
+        for q, (lws, n, C, dg, db) in zip(larr, ln):
+            q.partial, q.n_partial, q.C, q.dgamma, q.dbeta = lws.data_ptr(), n, C, dg.data_ptr(), db.data_ptr()
+    check(lib.ap_gemm_tn8_acc_grouped_ln(ptr, len(problems), ctypes.cast(larr, ctypes.c_void_p) if larr is not None else None, len(ln),
+                                         ws.data_ptr() if ws is not None else None, ws_bytes, _stream()), "ap_gemm_tn8_acc_grouped_ln")
+
+
 def poison_lds(pattern=0x7FC07FC0):
     """test aid: every CU's LDS filled with `pattern` (default: bf16 NaN pairs)"""
     scratch = torch.zeros(2, dtype=torch.int32, device="cuda")
@@ -453,6 +531,17 @@ def gemm_tn_acc_grouped(problems, ln=None):
     ln: deferred LayerNorm reductions (the entries layernorm_bwd(..., defer=...) appended): LN_MAX_BATCH of them ride in the first launch."""
     from ._lib import TnProblem, TN_MAX_GROUP, TN_MAX_GROUP_DET, LnReduce, LN_MAX_BATCH
     ln = list(ln) if ln else []
+    fp8 = [p for p in problems if isinstance(p, Tn8Problem)]
+    if fp8:                           # the fp8 problems (functional.FP8_WGRAD) in launches of their own; the riders go with the first
+        problems = [p for p in problems if not isinstance(p, Tn8Problem)]
+        for i0 in range(0, len(fp8), TN_MAX_GROUP):
+            gemm_tn8_acc_grouped(fp8[i0:i0 + TN_MAX_GROUP], ln=None if problems else ln[:LN_MAX_BATCH])
+            if not problems:
+                ln = ln[LN_MAX_BATCH:]
+        if not problems:
+            if ln:
+                layernorm_bwd_reduce_batched(ln)
+            return
     if len(ln) > LN_MAX_BATCH:
         layernorm_bwd_reduce_batched(ln[LN_MAX_BATCH:])
         ln = ln[:LN_MAX_BATCH]

@@ -226,6 +226,34 @@ int ap_gemm_tn_acc_grouped(const ap_tn_problem* problems, int count, void* works
  * workgroups of its own: the weight gradients and the LayerNorm parameter gradients of one block in ONE launch */
 int ap_gemm_tn_acc_grouped_ln(const ap_tn_problem* problems, int count, const ap_ln_reduce* ln_items, int ln_count,
                               void* workspace, size_t ws_bytes, ap_stream_t stream);
+/* ---- fp8 weight gradients (configs[4]: "e4m3 fwd / e5m2 grads"): C[N1,N2] += alpha * dq_a[0] * dq_b[0] * A8[M,N1]^T . B8[M,N2]
+ * A8: output gradient as OCP e5m2 (a_fmt = AP_FP8_E5M2) or e4m3 (AP_FP8_E4M3) bytes, B8: layer input as e4m3 bytes, fp32 accumulation.
+ * dq_a / dq_b are DEVICE scalars (1/scale of the quantisation), read at run time (graph replays stay correct).
+ * y = sat(g * scale[0]) -> e5m2 (|.| <= 57344, round to nearest even), n % 16 == 0; amax (nullable): amax[0] = max(amax[0], max |g|).
+ * colsum (nullable): the bias gradient of the UN-quantised g [rows, cols] (rows * cols == n, cols % 16 == 0):
+ * colsum[c] += colsum_scale * sum_r w[r] * g[r,c], w = colsum_weight (bf16 per-row weights, NULL = ones; colsum_scale then unused) */
+#define AP_BF8_COLSUM_SPLITS 64
+/* colsum_ws (nullable): AP_BF8_COLSUM_SPLITS * cols floats -- the row splits' partial sums are stored there and added in split order
+ * (bitwise reproducible, the AP_DETERMINISTIC=1 mode); NULL: fp32 atomics */
+int ap_quantize_bf8(const ap_bf16* g, unsigned char* y, int64_t n, const float* scale, float* amax, float* colsum, int rows, int cols,
+                    const ap_bf16* colsum_weight, float colsum_scale, float* colsum_ws, ap_stream_t stream);
+#define AP_FP8_E4M3 0
+#define AP_FP8_E5M2 1
+typedef struct ap_tn8_problem {
+    const unsigned char* A; int lda;   /* [M,N1] bytes, format a_fmt; lda % 16 == 0 */
+    const unsigned char* B; int ldb;   /* [M,N2] e4m3 bytes; ldb % 16 == 0 */
+    float* C; int ldc;                 /* [N1,N2] += alpha * dq_a[0] * dq_b[0] * A^T . B */
+    int M, N1, N2;                     /* N1, N2 multiples of 128 (every Linear width of VOLO-D5); any M > 0 */
+    int a_fmt;                         /* AP_FP8_E5M2 or AP_FP8_E4M3 */
+    float alpha;                       /* 0 is read as 1 */
+    const float* dq_a; const float* dq_b;
+} ap_tn8_problem;
+/* `workspace` as for ap_gemm_tn_acc_grouped (NULL: fp32 atomics; >= ap_gemm_tn8_grouped_workspace() bytes: deterministic split order).
+ * AP_ERR_UNSUPPORTED for a width or format outside the above (the caller then runs the bf16 product). */
+size_t ap_gemm_tn8_grouped_workspace(const ap_tn8_problem* problems, int count);
+int ap_gemm_tn8_acc_grouped(const ap_tn8_problem* problems, int count, void* workspace, size_t ws_bytes, ap_stream_t stream);
+int ap_gemm_tn8_acc_grouped_ln(const ap_tn8_problem* problems, int count, const ap_ln_reduce* ln_items, int ln_count,
+                               void* workspace, size_t ws_bytes, ap_stream_t stream);
 /* bias gradient: out[n] += sum_m A[m,n] */
 int ap_colsum_acc(const ap_bf16* A, int lda, float* out, int M, int N, ap_stream_t stream);
 
