@@ -150,6 +150,8 @@ _SIGNATURES["ap_conv3x3_c128_wgrad"] = (_I, [_P, _P, _P, _I, _I, _I, _P, ctypes.
 _SIGNATURES["ap_sum_reps_acc"] = (_I, [_P, _P, _L, _I, _P])
 
 _SIGNATURES["ap_mlp_fused"] = (_I, [POINTER(MlpFusedArgs), _P])
+_SIGNATURES["ap_mlp_fused_infer"] = (_I, [POINTER(MlpFusedArgs), _P])
+_SIGNATURES["ap_classify_stats"] = (_I, [_P, _I, _I, _P, _P, _P, _L, _P])
 _SIGNATURES["ap_calib_copy"] = (_I, [_P, _P, _L, _P])
 _SIGNATURES["ap_calib_mfma"] = (_I, [_P, _P, _I, _P])
 

@@ -864,6 +864,8 @@ static void g8_pick(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t s
         case G8_BIAS | G8_GELU | G8_RS: g8_go<NT1, G8_BIAS | G8_GELU | G8_RS>(ga, ep, grid, st); break;
         case G8_BIAS | G8_GELU | G8_GTAB: g8_go<NT1, G8_BIAS | G8_GELU | G8_GTAB>(ga, ep, grid, st); break;
         case G8_BIAS | G8_GELU | G8_RS | G8_GTAB: g8_go<NT1, G8_BIAS | G8_GELU | G8_RS | G8_GTAB>(ga, ep, grid, st); break;
+        case G8_BIAS | G8_GELU | G8_GTAB | G8_NOSIDE: g8_go<NT1, G8_BIAS | G8_GELU | G8_GTAB | G8_NOSIDE>(ga, ep, grid, st); break;
+        case G8_BIAS | G8_GELU | G8_RS | G8_GTAB | G8_NOSIDE: g8_go<NT1, G8_BIAS | G8_GELU | G8_RS | G8_GTAB | G8_NOSIDE>(ga, ep, grid, st); break;
         case G8_DGELU: g8_go<NT1, G8_DGELU>(ga, ep, grid, st); break;
         case G8_DGELU | G8_RS: g8_go<NT1, G8_DGELU | G8_RS>(ga, ep, grid, st); break;
         case G8_MUL: g8_go<NT1, G8_MUL>(ga, ep, grid, st); break;
@@ -970,9 +972,9 @@ static int ws_try(const bf16_t* A, int lda, const bf16_t* B, int ldb, bf16_t* C,
     if (!on || K != WS_K || N % WS_BN || M % WS_BM || M < 16384 || (ldc & 15) || (lda & 7) || (ldb & 7)) return 1;
     if (ep.dgelu_of || ep.mul_by || ep.row_scale || ep.residual || ep.q8) return 1;
     int epi = -1;
-    if (ep.gelu == 3 && ep.preact && !ep.mul8) {
+    if (ep.gelu == 3 && (ep.preact || ep.noside) && !ep.mul8) {
         ep.gelu_tab = g8_gelu_table_ptr(st);
-        if (ep.gelu_tab) epi = 0;
+        if (ep.gelu_tab) epi = ep.noside ? 2 : 0;
     } else if (!ep.gelu && ep.mul8 && !ep.bias) epi = 1;
     if (epi < 0) return 1;
     WsArgs a;
@@ -985,9 +987,11 @@ static int ws_try(const bf16_t* A, int lda, const bf16_t* B, int ldb, bf16_t* C,
     if (!attr) {
         (void)hipFuncSetAttribute((const void*)k_gemm_nt_ws<0>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS_BYTES(0));
         (void)hipFuncSetAttribute((const void*)k_gemm_nt_ws<1>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS_BYTES(1));
+        (void)hipFuncSetAttribute((const void*)k_gemm_nt_ws<2>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS_BYTES(2));
         attr = true; (void)hipGetLastError();
     }
     if (epi == 0) hipLaunchKernelGGL(k_gemm_nt_ws<0>, dim3(grid), dim3(512), WS_LDS_BYTES(0), st, a, ep);
+    else if (epi == 2) hipLaunchKernelGGL(k_gemm_nt_ws<2>, dim3(grid), dim3(512), WS_LDS_BYTES(2), st, a, ep);
     else hipLaunchKernelGGL(k_gemm_nt_ws<1>, dim3(grid), dim3(512), WS_LDS_BYTES(1), st, a, ep);
     return ap_check_launch();
 }
@@ -1005,7 +1009,10 @@ int ap_gemm_nt(const ap_bf16* A, int lda, const ap_bf16* B, int ldb, ap_bf16* C,
         ep.residual = epi->residual; ep.ldr = epi->ldr; ep.mul8 = epi->mul_by8;
         if (ep.residual && ep.ldr < N) return AP_ERR_SHAPE;
         if ((ep.mul_by != nullptr) + (ep.dgelu_of != nullptr) + (ep.mul8 != nullptr) > 1) return AP_ERR_SHAPE;
-        if (ep.gelu < 0 || ep.gelu > 3 || (ep.gelu >= 2 && !ep.preact)) return AP_ERR_SHAPE;
+        // gelu = 4: the value of mode 3 in `out`, no side store (forward-only launches); preact_out is ignored
+        if (ep.gelu == 4) { ep.gelu = 3; ep.noside = 1; ep.preact = nullptr; }
+        else if (ep.gelu < 0 || ep.gelu > 3 || (ep.gelu >= 2 && !ep.preact)) return AP_ERR_SHAPE;
+        if (ep.noside && (ep.mul_by || ep.dgelu_of || ep.mul8 || ep.residual || epi->q8_out || !ep.bias)) return AP_ERR_UNSUPPORTED;
         // q8_out of a bf16 launch (round 5): the output a second time as e4m3 bytes, for the fp8 input-gradient product that consumes it.
         // Exists in the 8-phase kernel's mul_by8 flavours only (the input gradient of fc2): anything else is refused, not silently skipped
         if (epi->q8_out) {
@@ -1021,6 +1028,7 @@ int ap_gemm_nt(const ap_bf16* A, int lda, const ap_bf16* B, int ldb, ap_bf16* C,
         const size_t lds = (size_t)8 * 64 * SK_STRIDE * sizeof(float);
         static bool sk_attr = false;
         if (!sk_attr) { (void)hipFuncSetAttribute((const void*)k_gemm_nt_skinny, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); sk_attr = true; (void)hipGetLastError(); }
+        if (ep.noside) return AP_ERR_UNSUPPORTED;       // (the caller falls back to gelu = 3 with a side buffer)
         hipLaunchKernelGGL(k_gemm_nt_skinny, dim3((N + 31) / 32, (M + 63) / 64), dim3(512), lds, (hipStream_t)stream, A, lda, B, ldb, C, ldc, M, N, K, ep);
         return ap_check_launch();
     }
@@ -1073,6 +1081,8 @@ int ap_gemm_nt(const ap_bf16* A, int lda, const ap_bf16* B, int ldb, ap_bf16* C,
     }
     // variants 20 / 21: the persistent 8-phase kernel of gemm8p.h with 256 x 192 / 256 x 256 tiles (whole 8-column chunks only)
     if ((variant == 20 || variant == 21) && ((K & 63) || (N & 7) || (ldc & 7) || (ep.residual && (ep.ldr & 7)))) variant = 1;
+    // gelu = 4 exists in the table flavours of the 8-phase kernel (and in the weight-stationary kernel above) only: refused AFTER the choice
+    if (ep.noside && ((variant != 20 && variant != 21) || !g8_gelu_table_ptr((hipStream_t)stream))) return AP_ERR_UNSUPPORTED;
     // q8_out exists in the 8-phase kernel's G8_Q8 flavours only: a forced tile (AP_GEMM_NT_TILE), a rule (AP_GEMM_NT_RULE), AP_GEMM_NT_192 or
     // the fallback above may have picked a kernel that never writes it -- refused here, AFTER the choice, not silently skipped
     if (ep.q8 && variant != 20 && variant != 21) return AP_ERR_UNSUPPORTED;

@@ -78,11 +78,12 @@ struct G8Args {
 // epilogue flavour of an instantiation (EF >= 0: bits known at compile time; EF < 0: read from the arguments at run time).  The
 // generic epilogue is ~25 KB of code that a CU runs once or twice per launch, cold: an instantiation per flavour of the training
 // step keeps what is fetched to what is used (2.8 us -> see DESIGN.md on the 25088 x 384 x 1152 launch).
-enum { G8_BIAS = 1, G8_GELU = 2, G8_DGELU = 4, G8_RS = 8, G8_RES = 16, G8_MUL = 32, G8_MUL8 = 64, G8_GTAB = 128, G8_Q8 = 256 };
+enum { G8_BIAS = 1, G8_GELU = 2, G8_DGELU = 4, G8_RS = 8, G8_RES = 16, G8_MUL = 32, G8_MUL8 = 64, G8_GTAB = 128, G8_Q8 = 256, G8_NOSIDE = 512 };
 __host__ __device__ inline int g8_flavour(const EpiArgs& ep) {
     return (ep.bias ? G8_BIAS : 0) | (ep.gelu ? G8_GELU : 0) | (ep.dgelu_of ? G8_DGELU : 0) | (ep.row_scale ? G8_RS : 0) | (ep.residual ? G8_RES : 0) |
            (ep.mul_by ? G8_MUL : 0) | (ep.mul8 ? G8_MUL8 : 0) | ((ep.gelu == 3 && ep.gelu_tab) ? G8_GTAB : 0) |
-           ((ep.q8 && !ep.gelu) ? G8_Q8 : 0);        // (the fp8 GELU launches emit their e4m3 side output without a flavour bit of their own)
+           ((ep.q8 && !ep.gelu) ? G8_Q8 : 0) |       // (the fp8 GELU launches emit their e4m3 side output without a flavour bit of their own)
+           (ep.noside ? G8_NOSIDE : 0);              // gelu = 4: the GTAB flavours without the derivative codes
 }
 
 // NT1: B part 1 holds NT1 16-column tiles per wave (1: 256 x 192 block tile, 2: 256 x 256).
@@ -132,6 +133,7 @@ __global__ void __launch_bounds__(512, 2) k_gemm_nt_8p(G8Args ga, EpiArgs ep) {
     // GTAB (the GELU flavours): 16 KB of the staging region hold the GELU table of gemm_epi.h (gelu = 3 launches: Phi(h) and the 8-bit
     // derivative code per bf16 value); the staging passes are half as tall
     constexpr bool GTAB = EF >= 0 && (EF & G8_GELU) != 0 && (EF & G8_GTAB) != 0;        // (the gelu = 1 / 2 launches keep the tall passes: 55.9 against 61.4 us)
+    constexpr bool NOSIDE = GTAB && (EF & G8_NOSIDE) != 0;       // forward-only: the codes are neither packed nor stored
     constexpr int PASS_MT = (NT1 == 1 ? 4 : 2) / (GTAB ? 2 : 1);    // 16-row tiles per wave group and staging pass
     constexpr int NPASS = 8 / PASS_MT;
     constexpr int RS = BN * 2;                   // bytes of a staged row
@@ -632,10 +634,12 @@ __global__ void __launch_bounds__(512, 2) k_gemm_nt_8p(G8Args ga, EpiArgs ep) {
 #pragma unroll
                             for (int q = 0; q < 4; ++q)
                                 o[q] = pack_bf2(bf_lo(x[q]) * __uint_as_float(e8[2 * q]) * rs, bf_hi(x[q]) * __uint_as_float(e8[2 * q + 1]) * rs);
-                            // codes: byte 0 of each entry
-                            gqv[0] = __builtin_amdgcn_perm(e8[1], e8[0], 0x0c0c0400u) | (__builtin_amdgcn_perm(e8[3], e8[2], 0x0c0c0400u) << 16);
-                            gqv[1] = __builtin_amdgcn_perm(e8[5], e8[4], 0x0c0c0400u) | (__builtin_amdgcn_perm(e8[7], e8[6], 0x0c0c0400u) << 16);
-                            gqok = true;
+                            if constexpr (!NOSIDE) {
+                                // codes: byte 0 of each entry
+                                gqv[0] = __builtin_amdgcn_perm(e8[1], e8[0], 0x0c0c0400u) | (__builtin_amdgcn_perm(e8[3], e8[2], 0x0c0c0400u) << 16);
+                                gqv[1] = __builtin_amdgcn_perm(e8[5], e8[4], 0x0c0c0400u) | (__builtin_amdgcn_perm(e8[7], e8[6], 0x0c0c0400u) << 16);
+                                gqok = true;
+                            }
                             x = o;
                         } else
                         if (rowgelu) {
@@ -684,7 +688,7 @@ __global__ void __launch_bounds__(512, 2) k_gemm_nt_8p(G8Args ga, EpiArgs ep) {
                         if (!(G8_ABL & 32)) g8_store(ga.C + (int64_t)m * ga.ldc + n, x);
                         else asm volatile("" :: "v"(x));
                     }
-                    if (rowgelu && ep.gelu == 3) {
+                    if (!NOSIDE && rowgelu && ep.gelu == 3) {
                         // 8 code bytes per lane: the lane with the even chunk of a pair takes its neighbour's 8 bytes (the XOR swizzle keeps chunk
                         // pairs on lane pairs) and stores 16 -- whole 128-byte lines per 16 lanes where the tile's column offset allows it
                         const unsigned n0lo = (unsigned)__shfl_xor((int)gqv[0], 1, 64), n0hi = (unsigned)__shfl_xor((int)gqv[1], 1, 64);

@@ -54,6 +54,8 @@ struct EpiArgs {
     const unsigned char* mul8;  // out = v * gq_decode(mul8[m,n]) (ld = ldc bytes): the 8-bit derivative codes of a gelu = 3 forward
     const unsigned* gelu_tab;   // gelu = 3 launches of the 8-phase kernel: the 4096-entry table of gq_tab_entry() below (global memory), or nullptr
     BnIn abn;                   // PATCH = 1 only: abn.mean != nullptr -> the A rows (patches of an NHWC map with 64 channels) are relu(bn(.)) of what is read
+    int noside;                 // ap_gemm_epilogue.gelu = 4 (forward-only launches): gelu = 3's value in `out`, no derivative codes (preact is null);
+                                // only the G8_NOSIDE flavours of the 8-phase kernel and k_gemm_nt_ws<2> are ever launched with it
 };
 
 // 8-bit fixed-point code of gelu'(h) in [-0.1290, 1.1290] (gelu = 3 / mul_by8, include/autoprog_hip.h): code = clamp(rint(202 g) + 26, 0, 255),

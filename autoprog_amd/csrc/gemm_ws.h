@@ -29,6 +29,7 @@
 //               over ascending 32-deep K steps -- the order of the 8-phase kernel: results are bit-identical to it
 //   EPI = 0   : + bias, GELU and its 8-bit derivative code from the table (ap_gemm_epilogue.gelu = 3), the codes to preact_out
 //   EPI = 1   : * the stored codes (mul_by8)
+//   EPI = 2   : EPI 0 without the codes (ap_gemm_epilogue.gelu = 4, forward-only launches): the same bits in C, preact_out untouched
 #pragma once
 #include "common.h"
 #include "gemm_epi.h"
@@ -44,7 +45,7 @@
 #define WS_LDS_A (WS_BM * WS_ROWB)                // 24576: the two groups' 32-row halves
 // EPI 0: bf16 staging + the 16 KB table; EPI 1: fp32 staging (the multiply by the stored derivative happens on the fp32 accumulator value,
 // rounded once -- as in the 8-phase kernel)
-#define WS_LDS_BYTES(EPI) (WS_LDS_A + ((EPI) == 0 ? WS_LDS_A + 16384 : 2 * WS_LDS_A))
+#define WS_LDS_BYTES(EPI) (WS_LDS_A + ((EPI) != 1 ? WS_LDS_A + 16384 : 2 * WS_LDS_A))
 
 __device__ __forceinline__ int ws_key(int r) { return ((r >> 1) & 1) | (((r >> 2) & 3) << 1); }
 // byte offset of 16-byte chunk c (0 .. 23) of row r
@@ -60,8 +61,10 @@ struct WsArgs {
     int M, N, n_slices, n_items, per_xcd;     // n_items: 64-row tiles; per_xcd: tile streams per XCD (each served by n_slices workgroups)
 };
 
-template <int EPI>
+template <int EPIK>
 __global__ void __launch_bounds__(512, 2) k_gemm_nt_ws(WsArgs a, EpiArgs ep) {
+    constexpr int EPI = EPIK == 2 ? 0 : EPIK;                     // the arithmetic of the flavour
+    constexpr bool CODES = EPIK == 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char ws_smem[];
     unsigned char* const Al = ws_smem;
     unsigned char* const St = Al + WS_LDS_A;
@@ -187,14 +190,16 @@ __global__ void __launch_bounds__(512, 2) k_gemm_nt_ws(WsArgs a, EpiArgs ep) {
                 }
 #pragma unroll
                 for (int q = 0; q < 4; ++q) o[q] = pack_bf2(bf_lo(x[q]) * __uint_as_float(e8[2 * q]), bf_hi(x[q]) * __uint_as_float(e8[2 * q + 1]));
-                u32x2 gq;
-                gq[0] = __builtin_amdgcn_perm(e8[1], e8[0], 0x0c0c0400u) | (__builtin_amdgcn_perm(e8[3], e8[2], 0x0c0c0400u) << 16);
-                gq[1] = __builtin_amdgcn_perm(e8[5], e8[4], 0x0c0c0400u) | (__builtin_amdgcn_perm(e8[7], e8[6], 0x0c0c0400u) << 16);
-                // 8 code bytes per lane: the lane with the even chunk of a pair takes its neighbour's and stores 16 (24 chunks per row: pairs never straddle rows)
-                const unsigned n0lo = (unsigned)__shfl_xor((int)gq[0], 1, 64), n0hi = (unsigned)__shfl_xor((int)gq[1], 1, 64);
-                if (!(p & 1)) {
-                    u32x4 o4; o4[0] = gq[0]; o4[1] = gq[1]; o4[2] = n0lo; o4[3] = n0hi;
-                    if (!(WS_ABL & 1) || o4[0] == 0x12345678u) st16_nt(reinterpret_cast<unsigned char*>(ep.preact) + m * a.ldc + n, o4);
+                if constexpr (CODES) {
+                    u32x2 gq;
+                    gq[0] = __builtin_amdgcn_perm(e8[1], e8[0], 0x0c0c0400u) | (__builtin_amdgcn_perm(e8[3], e8[2], 0x0c0c0400u) << 16);
+                    gq[1] = __builtin_amdgcn_perm(e8[5], e8[4], 0x0c0c0400u) | (__builtin_amdgcn_perm(e8[7], e8[6], 0x0c0c0400u) << 16);
+                    // 8 code bytes per lane: the lane with the even chunk of a pair takes its neighbour's and stores 16 (24 chunks per row: pairs never straddle rows)
+                    const unsigned n0lo = (unsigned)__shfl_xor((int)gq[0], 1, 64), n0hi = (unsigned)__shfl_xor((int)gq[1], 1, 64);
+                    if (!(p & 1)) {
+                        u32x4 o4; o4[0] = gq[0]; o4[1] = gq[1]; o4[2] = n0lo; o4[3] = n0hi;
+                        if (!(WS_ABL & 1) || o4[0] == 0x12345678u) st16_nt(reinterpret_cast<unsigned char*>(ep.preact) + m * a.ldc + n, o4);
+                    }
                 }
             } else {
                 const f32x4 f0 = *reinterpret_cast<const f32x4*>(Sg + ws_off32(r, 2 * p)), f1 = *reinterpret_cast<const f32x4*>(Sg + ws_off32(r, 2 * p + 1));

@@ -484,9 +484,13 @@ __device__ __forceinline__ void mf_tab_addr2(unsigned w, unsigned& a0, unsigned&
 
 // RES: the forward launch adds a residual (a.res != nullptr).  A template parameter, not a branch: with both epilogues in one kernel hipcc spilled
 // accumulator quadruples where the two paths join and reloaded them -- each reload behind an s_waitcnt vmcnt(0) -- in the middle of the pipelined epilogue.
-template <int C, bool BWD, bool LN = false, bool RES = false>
+// INFER: the forward-only launch (ap_mlp_fused_infer): the same `out`, none of what only a backward pass reads -- no store of the hidden chunk, no
+// derivative codes, no LN(x) / mean / rstd.  A template parameter for the same reason.  Every dropped store is role A's, and role A's only counted
+// vmcnt wait belongs to the backward launch: no count of the forward changes (role B, which counts its DMA, stores nothing before its last wait).
+template <int C, bool BWD, bool LN = false, bool RES = false, bool INFER = false>
 __global__ void __launch_bounds__(512, 2) k_mlp_fused2(MlpArgs a) {
     static_assert(!(BWD && (LN || RES)), "the LayerNorm in front of fc1 and the residual belong to the forward launch");
+    static_assert(!(BWD && INFER), "the forward-only launch has no backward flavour");
     static_assert(C == 384, "version 2 is written for C = 384 (six pieces per phase, two slots per phase)");
     constexpr int PP = C / 64, NCH = 3 * C / 64, KS = C / 32, NT2 = C / 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char mf_smem[];
@@ -633,7 +637,7 @@ __global__ void __launch_bounds__(512, 2) k_mlp_fused2(MlpArgs a) {
                 q += __shfl_xor(q, 32, 64);
                 q += __shfl_xor(q, 16, 64);
                 const float rsd = rsqrtf(q * invC + a.ln_eps);
-                if (g == 0) { a.LnMean[m0 + mt * 16 + fr] = mu; a.LnRstd[m0 + mt * 16 + fr] = rsd; }
+                if constexpr (!INFER) { if (g == 0) { a.LnMean[m0 + mt * 16 + fr] = mu; a.LnRstd[m0 + mt * 16 + fr] = rsd; } }
                 const f32x2 rs2v = {rsd, rsd};
 #pragma unroll
                 for (int i = 0; i < KS / 4; ++i)
@@ -652,8 +656,13 @@ __global__ void __launch_bounds__(512, 2) k_mlp_fused2(MlpArgs a) {
                         }
                         xf[mt][4 * i + 2 * p] = (u32x4){o0[0], o0[1], o0[2], o0[3]};
                         xf[mt][4 * i + 2 * p + 1] = (u32x4){o1[0], o1[1], o1[2], o1[3]};
-                        st16_nt(a.LnOut + (int64_t)(m0 + mt * 16 + fr) * a.ldlo + (4 * i + 2 * p) * 32 + g * 8, xf[mt][4 * i + 2 * p]);
-                        st16_nt(a.LnOut + (int64_t)(m0 + mt * 16 + fr) * a.ldlo + (4 * i + 2 * p + 1) * 32 + g * 8, xf[mt][4 * i + 2 * p + 1]);
+                        if constexpr (!INFER) {
+                            st16_nt(a.LnOut + (int64_t)(m0 + mt * 16 + fr) * a.ldlo + (4 * i + 2 * p) * 32 + g * 8, xf[mt][4 * i + 2 * p]);
+                            st16_nt(a.LnOut + (int64_t)(m0 + mt * 16 + fr) * a.ldlo + (4 * i + 2 * p + 1) * 32 + g * 8, xf[mt][4 * i + 2 * p + 1]);
+                        } else {
+                            // (no store pins the order of the (i, p) pairs any more: left free, hipcc interleaved them and spilled 28 registers)
+                            asm volatile("" : "+v"(xf[mt][4 * i + 2 * p]), "+v"(xf[mt][4 * i + 2 * p + 1]));
+                        }
                     }
             }
         }
@@ -696,13 +705,15 @@ __global__ void __launch_bounds__(512, 2) k_mlp_fused2(MlpArgs a) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
                         o[b][q] = pack_bf2(bf_lo(hb[b][q]) * __uint_as_float(e[b][2 * q]) * rs, bf_hi(hb[b][q]) * __uint_as_float(e[b][2 * q + 1]) * rs);
-                    u32x2 gq;
-                    gq[0] = __builtin_amdgcn_perm(e[b][1], e[b][0], 0x0c0c0400u) | (__builtin_amdgcn_perm(e[b][3], e[b][2], 0x0c0c0400u) << 16);
-                    gq[1] = __builtin_amdgcn_perm(e[b][5], e[b][4], 0x0c0c0400u) | (__builtin_amdgcn_perm(e[b][7], e[b][6], 0x0c0c0400u) << 16);
-                    if (!(MF_ABL & 16)) {
-                        st16_nt(a.Hout + hrow[mt] + j * 64 + b * 32, o[b]);
-                        *reinterpret_cast<u32x2*>(a.G + hrow[mt] + j * 64 + b * 32) = gq;
-                    } else asm volatile("" :: "v"(gq));
+                    if constexpr (!INFER) {
+                        u32x2 gq;
+                        gq[0] = __builtin_amdgcn_perm(e[b][1], e[b][0], 0x0c0c0400u) | (__builtin_amdgcn_perm(e[b][3], e[b][2], 0x0c0c0400u) << 16);
+                        gq[1] = __builtin_amdgcn_perm(e[b][5], e[b][4], 0x0c0c0400u) | (__builtin_amdgcn_perm(e[b][7], e[b][6], 0x0c0c0400u) << 16);
+                        if (!(MF_ABL & 16)) {
+                            st16_nt(a.Hout + hrow[mt] + j * 64 + b * 32, o[b]);
+                            *reinterpret_cast<u32x2*>(a.G + hrow[mt] + j * 64 + b * 32) = gq;
+                        } else asm volatile("" :: "v"(gq));
+                    }
                 }
             } else {
 #pragma unroll
@@ -1019,19 +1030,19 @@ const unsigned* g8_gelu_table_ptr(hipStream_t st) {
 }
 #endif
 
-template <int C, bool BWD, bool LN = false, bool RES = false>
+template <int C, bool BWD, bool LN = false, bool RES = false, bool INFER = false>
 static int mf_launch(const MlpArgs& a, hipStream_t st) {
     static int version = 0;                  // AP_MLP_FUSED_V = 1: the one-wave-per-SIMD kernel; default 2: producer / consumer waves
     if (!version) { const char* e = getenv("AP_MLP_FUSED_V"); version = (e && e[0] == '1') ? 1 : 2; }
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute((const void*)k_mlp_fused<C, BWD>, hipFuncAttributeMaxDynamicSharedMemorySize, MF_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)k_mlp_fused2<C, BWD, LN, RES>, hipFuncAttributeMaxDynamicSharedMemorySize, M2_LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)k_mlp_fused2<C, BWD, LN, RES, INFER>, hipFuncAttributeMaxDynamicSharedMemorySize, M2_LDS_BYTES);
         attr = true; (void)hipGetLastError();
     }
-    if (version == 1 && LN) return AP_ERR_UNSUPPORTED;
+    if (version == 1 && (LN || INFER)) return AP_ERR_UNSUPPORTED;
     if (version == 1) hipLaunchKernelGGL((k_mlp_fused<C, BWD>), dim3(a.M / MF_BM), dim3(256), MF_LDS_BYTES, st, a);
-    else hipLaunchKernelGGL((k_mlp_fused2<C, BWD, LN, RES>), dim3(a.M / MF_BM), dim3(512), M2_LDS_BYTES, st, a);
+    else hipLaunchKernelGGL((k_mlp_fused2<C, BWD, LN, RES, INFER>), dim3(a.M / MF_BM), dim3(512), M2_LDS_BYTES, st, a);
     return ap_check_launch();
 }
 
@@ -1071,6 +1082,36 @@ int ap_mlp_fused(const ap_mlp_fused_args* p, ap_stream_t stream) {
         return ln ? mf_launch<384, false, true, false>(a, st) : mf_launch<384, false, false, false>(a, st);
     }
     return mf_launch<384, true>(a, st);
+}
+
+// the forward of ap_mlp_fused without its side outputs (hidden_out, codes, ln_out, ln_mean, ln_rstd are neither required nor written): `out` is
+// bit-identical to ap_mlp_fused's for the same inputs
+int ap_mlp_fused_infer(const ap_mlp_fused_args* p, ap_stream_t stream) {
+    if (!p || !p->wa || !p->wb || !p->out) return AP_ERR_NULL;
+    if (p->backward) return AP_ERR_SHAPE;
+    const bool ln = p->ln_in != nullptr;
+    if (!ln && !p->x) return AP_ERR_NULL;
+    if (ln && (!p->ln_gamma || !p->ln_beta)) return AP_ERR_NULL;
+    if (ln && ((p->ld_ln & 7) || p->ld_ln < p->c)) return AP_ERR_SHAPE;
+    const int C = p->c, Hd = p->hidden, M = p->m;
+    if (M <= 0 || C <= 0 || Hd <= 0) return AP_ERR_SHAPE;
+    if (!ln && ((p->ldx & 7) || p->ldx < C)) return AP_ERR_SHAPE;
+    if ((p->ldwa & 7) || (p->ldwb & 7) || (p->ldo & 7) || p->ldwa < C || p->ldwb < Hd || p->ldo < C) return AP_ERR_SHAPE;
+    if (p->residual && ((p->ldr & 7) || p->ldr < C)) return AP_ERR_SHAPE;
+    if (C != 384 || Hd != 3 * C || (M % MF_BM)) return AP_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    MlpArgs a;
+    a.X = ln ? p->ln_in : p->x; a.ldx = ln ? p->ld_ln : p->ldx; a.Wa = p->wa; a.ldwa = p->ldwa; a.Wb = p->wb; a.ldwb = p->ldwb; a.Out = p->out; a.ldo = p->ldo;
+    a.Hout = nullptr; a.ldh = Hd; a.G = nullptr; a.bias1 = p->bias1; a.bias2 = p->bias2;
+    a.rs1 = p->row_scale_hidden; a.rs2 = p->row_scale_out; a.rows_per_scale = p->rows_per_scale > 0 ? p->rows_per_scale : 1;
+    a.res = p->residual; a.ldr = p->ldr; a.M = M; a.Hd = Hd;
+    a.LnOut = nullptr; a.ldlo = 0; a.LnG = ln ? p->ln_gamma : nullptr; a.LnB = ln ? p->ln_beta : nullptr; a.ln_eps = ln ? p->ln_eps : 0.f;
+    a.LnMean = a.LnRstd = nullptr;
+    (void)hipGetLastError();
+    a.gelu_tab = g8_gelu_table_ptr(st);
+    if (!a.gelu_tab) return AP_ERR_UNSUPPORTED;                // (as ap_mlp_fused: AP_GELU_TABLE=0, or a capture in front of the table's first build)
+    if (a.res) return ln ? mf_launch<384, false, true, true, true>(a, st) : mf_launch<384, false, false, true, true>(a, st);
+    return ln ? mf_launch<384, false, true, false, true>(a, st) : mf_launch<384, false, false, false, true>(a, st);
 }
 
 }  // extern "C"

@@ -272,3 +272,51 @@ extern "C" int ap_soft_ce_sparse_fwd_bwd_dev(const ap_bf16* logits, int ldx, con
                        idx, val, K, p_sb, p_sn, rows_per_batch, smoothing, row_loss, reinterpret_cast<bf16_t*>(dlogits), grad_scale, M, C, mix_lam, mix_batches, mix_lam_dev);
     return ap_check_launch();
 }
+
+// ---------------------------------------------------------------------------------------------------------------- validation statistics
+// ap_classify_stats: cross entropy against a hard label and the rank of the label's logit, one wave per row (lanes stride over the classes: coalesced
+// 2-byte loads, any ld), xor-butterfly reductions, every lane ends with the full sums (bit-equal across lanes) and lane 0 stores.  The row is read
+// twice (maximum + rank, then the exponentials): 2 KB that stay in the cache -- a validation pass launches this once per batch.
+__global__ void __launch_bounds__(256)
+k_classify_stats(const bf16_t* __restrict__ logits, int ld, int C, const int64_t* __restrict__ labels, float* __restrict__ loss,
+                 int* __restrict__ rank, int64_t rows) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                              // (whole waves; no barrier in this kernel)
+    const int64_t lab = labels[row];
+    if (lab < 0 || lab >= C) {                            // padding: nothing is read through the label
+        if (lane == 0) { loss[row] = 0.f; rank[row] = -1; }
+        return;
+    }
+    const bf16_t* z = logits + row * ld;
+    const float zl = bf2f(z[lab]);
+    float mx = -3.0e38f;
+    int above = 0;
+    for (int c = lane; c < C; c += 64) {
+        const float v = bf2f(z[c]);
+        mx = fmaxf(mx, v);
+        above += v > zl ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+        above += __shfl_xor(above, o, 64);
+    }
+    float se = 0.f;
+    for (int c = lane; c < C; c += 64) se += expf(bf2f(z[c]) - mx);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
+    if (lane == 0) { loss[row] = (mx - zl) + logf(se); rank[row] = above; }
+}
+
+extern "C" int ap_classify_stats(const ap_bf16* logits, int ld, int n_classes, const int64_t* labels, float* loss, int* rank, int64_t rows,
+                                 ap_stream_t stream) {
+    if (rows < 0 || n_classes <= 0 || ld < n_classes) return AP_ERR_SHAPE;
+    if (rows == 0) return AP_OK;
+    if (!logits || !labels || !loss || !rank) return AP_ERR_NULL;
+    if ((rows + 3) / 4 > 0x7fffffffLL) return AP_ERR_SHAPE;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_classify_stats, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const bf16_t*>(logits), ld, n_classes, labels, loss, rank, rows);
+    return ap_check_launch();
+}

@@ -387,6 +387,12 @@ FUSED_MLP_LN = os.environ.get("AP_FUSED_MLP_LN", "1") == "1"
 FUSED_MLP_MIN_ROWS = int(os.environ.get("AP_FUSED_MLP_MIN_ROWS", "18432"))
 
 
+# Forward-only passes (validation, the search's probes -- anything under torch.no_grad()): the blocks run as plain functions that write only
+# what a forward needs (transformer_block / outlooker_block / class_block below), bit-identical to the training forward.  AP_INFER=0: every
+# forward goes through the training Functions, as before.
+INFER = os.environ.get("AP_INFER", "1") != "0"
+
+
 def _gelu_bwd_kw(h):
     return {"mul_by": h} if STORE_GELU_GRAD else {"dgelu_of": h}
 
@@ -785,6 +791,64 @@ class TransformerBlockFn(torch.autograd.Function):
         return (dx.view(dy.shape), None, None, *_finish_param_grads(params, bufs, sunk, batch.deferred), None, None, None, None, None, None, None, None, None)
 
 
+def infer_mode():
+    """does a block take its forward-only body?  Decided where the block Functions are applied (inside Function.forward grad mode is always off).
+    An fp8 forward keeps the training Function even under no_grad."""
+    return INFER and not FP8_LINEAR and not torch.is_grad_enabled()
+
+
+def _fc1_infer(x, fc1_w, fc1_b, **kw):
+    """gelu(x fc1^T + b) with the bits of the training forward's launch and no side tensor (8-bit codes configuration; under AP_GELU_STORE_GRAD = 0 / 1
+    the training launch's value is another kernel path's, so that launch itself runs, with its side buffer)"""
+    if STORE_GELU_GRAD == 2:
+        return ops.gemm_nt(x, bank.get(fc1_w), bias=fc1_b, gelu="table", **kw)
+    h = _gelu_side_buffer(x.shape[0], fc1_w.shape[0], x.device)
+    return ops.gemm_nt(x, bank.get(fc1_w), bias=fc1_b, gelu=True, preact_out=h, preact_grad=STORE_GELU_GRAD, **kw)
+
+
+def _transformer_block_infer(x, rs1, rs2, n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b,
+                             B, N, heads, eps, k1=None, k2=None, tm1=None, tm2=None, inv_keep=None):
+    """TransformerBlockFn.forward without what only its backward reads (hidden activation, gelu' codes, LN copies and statistics of the fused MLP,
+    token masks); every intermediate is dropped once the launch that reads it is enqueued.  rs / k are the DropPath factors and masks of a
+    train-mode no_grad forward (the search's probes): the same launches take them, so the numbers are the training forward's."""
+    C = x.shape[-1]
+    x2 = x.reshape(B * N, C).contiguous()
+    scale = (C // heads) ** -0.5
+    if rs1 is not None and k1 is None:
+        k1 = (rs1 != 0).float()
+    if rs2 is not None and k2 is None:
+        k2 = (rs2 != 0).float()
+    xn1 = ops.layernorm_fwd(x2, n1w, n1b, eps)[0]
+    qkv = ops.gemm_nt(xn1, bank.get(qkv_w), bias=qkv_b)
+    del xn1
+    o = ops.mhsa_fwd(qkv, B, N, heads, scale, out_row_scale=k1)[0]
+    del qkv
+    x1 = ops.gemm_nt(o, bank.get(proj_w), bias=proj_b, row_scale=rs1, rows_per_scale=N, residual=x2)
+    del o, x2
+    use_fused = FUSED_MLP and STORE_GELU_GRAD == 2 and B * N >= FUSED_MLP_MIN_ROWS and ops.mlp_fused_ok(B * N, C, fc1_w.shape[0])
+    y = None
+    if use_fused and FUSED_MLP_LN:
+        y = ops.mlp_fused_infer(None, bank.get(fc1_w), bank.get(fc2_w), bias1=fc1_b, bias2=fc2_b, row_scale_hidden=k2, row_scale_out=rs2,
+                                rows_per_scale=N, residual=x1, ln=(x1, n2w, n2b, eps))
+    if y is None:
+        xn2 = ops.layernorm_fwd(x1, n2w, n2b, eps)[0]
+        if use_fused:
+            y = ops.mlp_fused_infer(xn2, bank.get(fc1_w), bank.get(fc2_w), bias1=fc1_b, bias2=fc2_b, row_scale_hidden=k2, row_scale_out=rs2,
+                                    rows_per_scale=N, residual=x1)
+        if y is None:
+            a = _fc1_infer(xn2, fc1_w, fc1_b, row_scale=k2, rows_per_scale=N)
+            del xn2
+            y = ops.gemm_nt(a, bank.get(fc2_w), bias=fc2_b, row_scale=rs2, rows_per_scale=N, residual=x1)
+    return y.view(x.shape)
+
+
+def transformer_block(x, *args):
+    """TransformerBlockFn.apply, or the forward-only body when no backward can follow (see infer_mode)"""
+    if infer_mode():
+        return _transformer_block_infer(x, *args)
+    return TransformerBlockFn.apply(x, *args)
+
+
 # ----------------------------------------------------------------------------- class block
 class ClassBlockFn(torch.autograd.Function):
     """ClassBlock.forward (models/volo.py:304-308) on SEPARATE class token [B,C] and tokens [B*N,C]:
@@ -847,6 +911,38 @@ class ClassBlockFn(torch.autograd.Function):
         return (dcls.view(ctx.shapes[0]), dtok.view(ctx.shapes[1]), *_finish_param_grads(params, bufs, sunk, batch.deferred), None, None, None, None)
 
 
+def _class_block_infer(cls, tok, n1w, n1b, kv_w, kv_b, q_w, q_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, B, N, heads, eps):
+    """ClassBlockFn.forward without what only its backward reads; the same launches in the same order otherwise (fc1 has B <= 256 rows, a launch
+    the library serves with its skinny kernel: ops.gemm_nt runs it with a side buffer of its own)"""
+    C = cls.shape[-1]
+    c0 = cls.reshape(B, C).contiguous()
+    t0 = tok.reshape(B * N, C).contiguous()
+    scale = (q_w.shape[0] // heads) ** -0.5
+    nc = ops.layernorm_fwd(c0, n1w, n1b, eps)[0]
+    nt = ops.layernorm_fwd(t0, n1w, n1b, eps)[0]
+    kv_t = ops.gemm_nt(nt, bank.get(kv_w), bias=kv_b)
+    del nt
+    kv_c = ops.gemm_nt(nc, bank.get(kv_w), bias=kv_b)
+    q = ops.gemm_nt(nc, bank.get(q_w), bias=q_b)
+    del nc
+    o = ops.class_attn_fwd(q, kv_t, B, N + 1, heads, scale, kv_cls=kv_c)[0]
+    del q, kv_t, kv_c
+    c1 = ops.gemm_nt(o, bank.get(proj_w), bias=proj_b, residual=c0)
+    del o
+    n2 = ops.layernorm_fwd(c1, n2w, n2b, eps)[0]
+    a = _fc1_infer(n2, fc1_w, fc1_b)
+    del n2
+    c2 = ops.gemm_nt(a, bank.get(fc2_w), bias=fc2_b, residual=c1)
+    return c2, tok
+
+
+def class_block(cls, tok, *args):
+    """ClassBlockFn.apply, or the forward-only body when no backward can follow (see infer_mode)"""
+    if infer_mode():
+        return _class_block_infer(cls, tok, *args)
+    return ClassBlockFn.apply(cls, tok, *args)
+
+
 FUSE_POOL_BWD = os.environ.get("AP_FUSE_POOL_BWD", "1") != "0"      # 0: the average pool's backward as a pass of its own (rounds 1 - 4)
 
 
@@ -902,6 +998,36 @@ class OutlookerBlockFn(torch.autograd.Function):
                 ops.avgpool2_bwd_acc(dpooled.view(B, (H + 1) // 2, (W + 1) // 2, C), dxn1.view(B, H, W, C))
                 dx = ops.layernorm_bwd(dxn1, x2, n1w, m1, r1, dx1, dn1w, dn1b, defer=batch.ln)
         return (dx.view(dy.shape), *_finish_param_grads(params, bufs, sunk, batch.deferred), None, None)
+
+
+def _outlooker_block_infer(x, n1w, n1b, v_w, v_b, attn_w, attn_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, heads, eps):
+    """OutlookerBlockFn.forward without the gelu' codes (T x 3 C bytes per block) and with every intermediate dropped once its reader is enqueued"""
+    B, H, W, C = x.shape
+    T = B * H * W
+    x2 = x.reshape(T, C).contiguous()
+    scale = (C // heads) ** -0.5
+    xn1 = ops.layernorm_fwd(x2, n1w, n1b, eps)[0]
+    v = ops.gemm_nt(xn1, bank.get(v_w), bias=v_b)
+    pooled = ops.avgpool2_fwd(xn1.view(B, H, W, C))
+    del xn1
+    logits = ops.gemm_nt(pooled.view(-1, C), bank.get(attn_w), bias=attn_b)
+    del pooled
+    yo = ops.outlook_fwd(v.view(B, H, W, C), logits, heads, scale)
+    del v, logits
+    x1 = ops.gemm_nt(yo.view(T, C), bank.get(proj_w), bias=proj_b, residual=x2)
+    del yo, x2
+    xn2 = ops.layernorm_fwd(x1, n2w, n2b, eps)[0]
+    a = _fc1_infer(xn2, fc1_w, fc1_b)
+    del xn2
+    y = ops.gemm_nt(a, bank.get(fc2_w), bias=fc2_b, residual=x1)
+    return y.view(x.shape)
+
+
+def outlooker_block(x, *args):
+    """OutlookerBlockFn.apply, or the forward-only body when no backward can follow (see infer_mode)"""
+    if infer_mode():
+        return _outlooker_block_infer(x, *args)
+    return OutlookerBlockFn.apply(x, *args)
 
 
 # --------------------------------------------------------------------- fine-grained pieces
@@ -1509,6 +1635,43 @@ class Stem64Fn(torch.autograd.Function):
         if not last:
             gr += [None, None]
         return (None, gr[0], gr[1], gr[2], None, None, gr[3], gr[4], gr[5], None, None, gr[6], gr[7], gr[8], None, None, None, None, None, None)
+
+
+def _stem64_infer(xs, w7, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2, w3, g3, b3, rm3, rv3, training, momentum, eps, apply_last=True):
+    """Stem64Fn.forward for a pass no backward follows: the same launches (the stem keeps the kernels it has; a train-mode probe still takes
+    batch statistics and updates the running ones), but a convolution's pre-BatchNorm output (205 MB at B = 128, 224 px) is dropped as soon as
+    the next convolution is enqueued instead of living to the end of the node -- the three of them are the peak of a whole no_grad forward"""
+    wp7 = ops.conv7_pack(w7.detach().float().contiguous())
+    wf2 = ops.conv3x3_pack(w2.detach().float().contiguous())[0]
+    wf3 = ops.conv3x3_pack(w3.detach().float().contiguous())[0]
+    mom1, mom2, mom3 = momentum
+    eps1, eps2, eps3 = eps
+    if training:
+        z1, p1 = ops.conv7_s2d(xs, wp7, True)
+        _, mean1, rstd1 = ops.bn_relu_fwd(z1, g1, b1, rm1, rv1, True, mom1, eps1, partials=p1, apply=False)
+        z2, p2 = ops.conv3x3_c64(z1, wf2, True, bn_in=(mean1, rstd1, g1, b1))
+        del z1
+        _, mean2, rstd2 = ops.bn_relu_fwd(z2, g2, b2, rm2, rv2, True, mom2, eps2, partials=p2, apply=False)
+        z3, p3 = ops.conv3x3_c64(z2, wf3, True, bn_in=(mean2, rstd2, g2, b2))
+        del z2
+        y, mean3, rstd3 = ops.bn_relu_fwd(z3, g3, b3, rm3, rv3, True, mom3, eps3, partials=p3, apply=apply_last)
+    else:
+        z1 = ops.conv7_s2d(xs, wp7)
+        _, mean1, rstd1 = ops.bn_relu_fwd(z1, g1, b1, rm1, rv1, False, mom1, eps1, apply=False)
+        z2 = ops.conv3x3_c64(z1, wf2, bn_in=(mean1, rstd1, g1, b1))
+        del z1
+        _, mean2, rstd2 = ops.bn_relu_fwd(z2, g2, b2, rm2, rv2, False, mom2, eps2, apply=False)
+        z3 = ops.conv3x3_c64(z2, wf3, bn_in=(mean2, rstd2, g2, b2))
+        del z2
+        y, mean3, rstd3 = ops.bn_relu_fwd(z3, g3, b3, rm3, rv3, False, mom3, eps3, apply=apply_last)
+    return y if apply_last else (z3, mean3, rstd3)
+
+
+def stem64(xs, *args):
+    """Stem64Fn.apply, or the forward-only body when no backward can follow (see infer_mode)"""
+    if infer_mode():
+        return _stem64_infer(xs, *args)
+    return Stem64Fn.apply(xs, *args)
 
 
 STEM_FUSE_BN = os.environ.get("AP_STEM_FUSE_BN", "1") != "0"

@@ -158,9 +158,9 @@ class Outlooker(nn.Module):
         if self.is_identity_layer:
             return x
         a, m = self.attn, self.mlp
-        return AF.OutlookerBlockFn.apply(_bf16(x), self.norm1.weight, self.norm1.bias, a.v.weight, a.v.bias, a.attn.weight,
-                                         a.attn.bias, a.proj.weight, a.proj.bias, self.norm2.weight, self.norm2.bias,
-                                         m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, a.num_heads, self.norm1.eps)
+        return AF.outlooker_block(_bf16(x), self.norm1.weight, self.norm1.bias, a.v.weight, a.v.bias, a.attn.weight,
+                                  a.attn.bias, a.proj.weight, a.proj.bias, self.norm2.weight, self.norm2.bias,
+                                  m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, a.num_heads, self.norm1.eps)
 
 
 class Attention(nn.Module):
@@ -216,10 +216,10 @@ class Transformer(nn.Module):
             rs1, k1, tm1 = rng.draw(B, keep, x.device, N)
             rs2, k2, tm2 = rng.draw(B, keep, x.device, N)
         a, m = self.attn, self.mlp
-        return AF.TransformerBlockFn.apply(x, rs1, rs2, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias,
-                                           a.proj.weight, a.proj.bias, self.norm2.weight, self.norm2.bias, m.fc1.weight,
-                                           m.fc1.bias, m.fc2.weight, m.fc2.bias, B, N, a.num_heads, self.norm1.eps,
-                                           k1, k2, tm1, tm2, 1.0 / keep)
+        return AF.transformer_block(x, rs1, rs2, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias,
+                                    a.proj.weight, a.proj.bias, self.norm2.weight, self.norm2.bias, m.fc1.weight,
+                                    m.fc1.bias, m.fc2.weight, m.fc2.bias, B, N, a.num_heads, self.norm1.eps,
+                                    k1, k2, tm1, tm2, 1.0 / keep)
 
 
 _default_rng = DropPathRng()
@@ -270,9 +270,9 @@ class ClassBlock(nn.Module):
         cls, tokens = _bf16(cls), _bf16(tokens)
         B, N, C = tokens.shape
         a, m = self.attn, self.mlp
-        out = AF.ClassBlockFn.apply(cls, tokens, self.norm1.weight, self.norm1.bias, a.kv.weight, a.kv.bias, a.q.weight, a.q.bias,
-                                    a.proj.weight, a.proj.bias, self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias,
-                                    m.fc2.weight, m.fc2.bias, B, N, a.num_heads, self.norm1.eps)
+        out = AF.class_block(cls, tokens, self.norm1.weight, self.norm1.bias, a.kv.weight, a.kv.bias, a.q.weight, a.q.bias,
+                             a.proj.weight, a.proj.bias, self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias,
+                             m.fc2.weight, m.fc2.bias, B, N, a.num_heads, self.norm1.eps)
         return out if pass_tokens else out[0]
 
     def forward_cls(self, x):
@@ -353,10 +353,10 @@ class PatchEmbed(nn.Module):
                 # the last BatchNorm + ReLU inside the projection's staging (functional.PatchConvFn bn_*): its activation is never written
                 fuse_last = (AF.STEM_FUSE_BN_PROJ and self.proj.stride[0] == k and self.proj.in_channels == 64 and (xs.shape[1] % k == 0) and (xs.shape[2] % k == 0)
                              and (k * 64) % 64 == 0)
-                whole = AF.Stem64Fn.apply(xs, c[0].weight, c[1].weight, c[1].bias, c[1].running_mean, c[1].running_var,
-                                          c[3].weight, c[4].weight, c[4].bias, c[4].running_mean, c[4].running_var,
-                                          c[6].weight, c[7].weight, c[7].bias, c[7].running_mean, c[7].running_var,
-                                          self.training, (c[1].momentum, c[4].momentum, c[7].momentum), (c[1].eps, c[4].eps, c[7].eps), not fuse_last)
+                whole = AF.stem64(xs, c[0].weight, c[1].weight, c[1].bias, c[1].running_mean, c[1].running_var,
+                                  c[3].weight, c[4].weight, c[4].bias, c[4].running_mean, c[4].running_var,
+                                  c[6].weight, c[7].weight, c[7].bias, c[7].running_mean, c[7].running_var,
+                                  self.training, (c[1].momentum, c[4].momentum, c[7].momentum), (c[1].eps, c[4].eps, c[7].eps), not fuse_last)
                 if self.training:
                     torch._foreach_add_([c[i].num_batches_tracked for i in (1, 4, 7) if c[i].num_batches_tracked is not None], 1)
                 if fuse_last:

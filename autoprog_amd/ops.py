@@ -196,10 +196,18 @@ def layernorm_bwd_reduce_batched(items):
 GELU_CODE_SCALE, GELU_CODE_ZERO = 202.0, 26.0       # the 8-bit derivative codes of gelu = 3 (include/autoprog_hip.h): gelu' = (code - 26) / 202
 
 
+GELU_TABLE_FALLBACKS = 0       # gemm_nt(gelu="table") launches the library refused and that ran as mode 3 with a side buffer of their own
+
+
 def _gelu_mode(gelu, preact_grad, preact_out):
-    """ap_gemm_epilogue.gelu: 1 stores h, 2 gelu'(h) as bf16, 3 gelu'(h) as 8-bit codes (preact_out then is a uint8 tensor)"""
+    """ap_gemm_epilogue.gelu: 1 stores h, 2 gelu'(h) as bf16, 3 gelu'(h) as 8-bit codes (preact_out then is a uint8 tensor);
+    gelu = "table": 4, the value of mode 3 and no side store (forward-only passes)"""
     if not gelu:
         return 0
+    if isinstance(gelu, str):
+        if gelu != "table" or preact_out is not None or preact_grad:
+            raise AutoProgHipError('gemm_nt: gelu="table" is the forward-only mode: no preact_out, no preact_grad')
+        return 4
     mode = 1 + int(preact_grad)
     if mode == 3 and (preact_out is None or preact_out.dtype != torch.uint8):
         raise AutoProgHipError("gemm_nt: preact_grad = 2 stores 8-bit codes: preact_out must be a uint8 tensor")
@@ -211,6 +219,46 @@ def _gelu_mode(gelu, preact_grad, preact_out):
 def mlp_fused_ok(M, C, hidden):
     """does ap_mlp_fused take this MLP?  (csrc/mlp_fused.hip: C = 384, hidden = 3 C, whole 128-row blocks)"""
     return C == 384 and hidden == 3 * C and M % 128 == 0 and M > 0
+
+
+def mlp_fused_infer(x, wa, wb, bias1=None, bias2=None, row_scale_hidden=None, row_scale_out=None, rows_per_scale=1, residual=None, ln=None):
+    """the forward of mlp_fused for a pass no backward follows (ap_mlp_fused_infer): -> out [M, C], bit-identical to mlp_fused(...)[0]; the hidden
+    activation, the gelu' codes and LN(rows) / mean / rstd are neither allocated nor written.  ln = (rows, gamma, beta, eps) with x = None as in mlp_fused.
+    -> None when the library does not take the launch"""
+    from ._lib import MlpFusedArgs
+    if ln is not None:
+        x = _req(ln[0], BF16, "ln rows")
+    _req(x, BF16, "x"); _req(wa, BF16, "wa"); _req(wb, BF16, "wb")
+    M, C = x.shape
+    H = wa.shape[0]
+    if not mlp_fused_ok(M, C, H):
+        return None
+    out = torch.empty((M, C), dtype=BF16, device=x.device)
+    a = MlpFusedArgs()
+    a.x, a.ldx = x.data_ptr(), x.shape[1]
+    a.wa, a.ldwa = wa.data_ptr(), wa.shape[1]
+    a.wb, a.ldwb = wb.data_ptr(), wb.shape[1]
+    a.out, a.ldo = out.data_ptr(), C
+    a.hidden_out, a.ldh, a.codes = None, H, None
+    a.bias1 = _req(bias1, torch.float32, "bias1").data_ptr() if bias1 is not None else None
+    a.bias2 = _req(bias2, torch.float32, "bias2").data_ptr() if bias2 is not None else None
+    a.row_scale_hidden = _req(row_scale_hidden, torch.float32, "row_scale_hidden").data_ptr() if row_scale_hidden is not None else None
+    a.row_scale_out = _req(row_scale_out, torch.float32, "row_scale_out").data_ptr() if row_scale_out is not None else None
+    a.rows_per_scale = int(rows_per_scale)
+    if residual is not None:
+        _req(residual, BF16, "residual")
+        a.residual, a.ldr = residual.data_ptr(), residual.shape[1]
+    a.m, a.c, a.hidden, a.backward = M, C, H, 0
+    if ln is not None:
+        a.x = None
+        a.ln_in, a.ld_ln = x.data_ptr(), C
+        a.ln_gamma, a.ln_beta = _req(ln[1], torch.float32, "ln gamma").data_ptr(), _req(ln[2], torch.float32, "ln beta").data_ptr()
+        a.ln_eps = float(ln[3])
+    code = lib.ap_mlp_fused_infer(ctypes.byref(a), _stream())
+    if code == -2:                    # AP_ERR_UNSUPPORTED
+        return None
+    check(code, "ap_mlp_fused_infer")
+    return out
 
 
 def mlp_fused(x, wa, wb, backward=False, bias1=None, bias2=None, row_scale_hidden=None, row_scale_out=None, rows_per_scale=1,
@@ -280,6 +328,8 @@ def gemm_nt(a, b, n=None, k=None, bias=None, gelu=False, preact_out=None, dgelu_
     """out[M, :n] = epilogue(a[M, :k] @ b[:n, :k]^T); a/b bf16 2-D (row stride = shape[1]).
     preact_grad: with gelu, preact_out receives gelu'(h) instead of h (True / 1: bf16; 2: 8-bit codes, preact_out uint8); its backward
     passes that tensor as mul_by (a uint8 tensor is taken as the codes).
+    gelu = "table" (forward-only passes): out holds exactly what the preact_grad = 2 launch stores there and no side tensor exists; where the
+    library has no such kernel for the launch (AP_ERR_UNSUPPORTED) it runs as that launch with a side buffer allocated and dropped here.
     q8 = (scale, amax) (gemm_nt_emits_q8 launches): -> (out, out8), out8 = the e4m3 bytes of out * scale[0], amax[0] raised to max |out|"""
     _req(a, BF16, "a"); _req(b, BF16, "b")
     M = a.shape[0]
@@ -317,8 +367,14 @@ def gemm_nt(a, b, n=None, k=None, bias=None, gelu=False, preact_out=None, dgelu_
             raise AutoProgHipError("gemm_nt: q8 exists for the mul_by (8-bit codes) launches only")
         out8 = torch.empty((M, ldc), dtype=torch.uint8, device=a.device)
         epi.q8_out, epi.q8_scale, epi.q8_amax = out8.data_ptr(), q8[0].data_ptr(), (q8[1].data_ptr() if q8[1] is not None else None)
-    check(lib.ap_gemm_nt(a.data_ptr(), a.shape[1], b.data_ptr(), b.shape[1], out.data_ptr(), ldc, M, n, k,
-                         epi_ref, _stream()), "ap_gemm_nt")
+    code = lib.ap_gemm_nt(a.data_ptr(), a.shape[1], b.data_ptr(), b.shape[1], out.data_ptr(), ldc, M, n, k, epi_ref, _stream())
+    if code == -2 and epi_ref is not None and epi.gelu == 4:
+        global GELU_TABLE_FALLBACKS
+        GELU_TABLE_FALLBACKS += 1
+        side = torch.empty((M, ldc), dtype=torch.uint8, device=a.device)
+        epi.gelu, epi.preact_out = 3, side.data_ptr()
+        code = lib.ap_gemm_nt(a.data_ptr(), a.shape[1], b.data_ptr(), b.shape[1], out.data_ptr(), ldc, M, n, k, epi_ref, _stream())
+    check(code, "ap_gemm_nt")
     return out if q8 is None else (out, out8)
 
 
@@ -722,6 +778,21 @@ def loss_combine(a, wa, b=None, wb=0.0):
     check(lib.ap_loss_combine(a.data_ptr(), a.numel(), float(wa), b.data_ptr() if b is not None else None, b.numel() if b is not None else 0,
                               float(wb), out.data_ptr(), _stream()), "ap_loss_combine")
     return out
+
+
+def classify_stats(logits, labels, n_classes=None):
+    """logits bf16 [rows, ld] (n_classes valid columns, default ld), labels int64 [rows] -> (loss fp32 [rows], rank int32 [rows]):
+    loss = logsumexp(z) - z[label]; rank = number of classes whose logit is STRICTLY greater than the label's (top-k correct iff 0 <= rank < k);
+    a label outside [0, n_classes) gives loss 0, rank -1 (include/autoprog_hip.h ap_classify_stats)"""
+    _req(logits, BF16, "logits"); _req(labels, torch.int64, "labels")
+    if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0]:
+        raise AutoProgHipError("classify_stats: logits [rows, ld] and labels [rows]")
+    rows, ld = logits.shape
+    n_classes = ld if n_classes is None else int(n_classes)
+    loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    rank = torch.empty(rows, dtype=torch.int32, device=logits.device)
+    check(lib.ap_classify_stats(logits.data_ptr(), ld, n_classes, labels.data_ptr(), loss.data_ptr(), rank.data_ptr(), rows, _stream()), "ap_classify_stats")
+    return loss, rank
 
 
 def soft_ce_fwd_bwd(logits, C, target, t_sb, t_sc, t_sn, rows_per_batch, grad_scale, mix_lam=1.0, mix_batches=0, mix_lam_ptr=None):

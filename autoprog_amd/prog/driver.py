@@ -11,7 +11,8 @@ between stages with `FlatAdamWEma.grow` (prog/elastic.py) and `set_sample_config
 resolution, nothing is copied to evaluate it.  The per-step input resize runs on the device (ap_resize_bilinear_nhwc).
 
 Out of scope: data loading, augmentation strength schedules (only DropPath lives in the model), LR scheduler,
-checkpoint files, validation -- the caller supplies `get_batch(r) -> (images, target)` and reads `history`.
+checkpoint files -- the caller supplies `get_batch(r) -> (images, target)` and reads `history`.  Validation (prog/validate.py) runs after
+every training epoch when the caller also supplies `get_val_batches`.
 """
 import random
 import time
@@ -30,7 +31,7 @@ def _sync():
 class AutoProgDriver:
     def __init__(self, model, loss_fn, optimizer, reducer, get_batch, r_list, l_list, dp_list, grow_epochs, steps_per_epoch,
                  search_epochs=2, auto_grow=True, probe_batches=4, time_steps=4, seed=0, log=None, original_batch_splits=1,
-                 r_max=None, dist_bn="", use_graphs=False, graph_after=2, clip_grad=None, clip_mode="norm"):
+                 r_max=None, dist_bn="", use_graphs=False, graph_after=2, clip_grad=None, clip_mode="norm", get_val_batches=None):
         """model: supernet sized for l_list[-1] (e.g. volo_h12_l18); optimizer: FlatAdamWEma over it; reducer: its
         GradientBucketReducer; r_list / l_list / dp_list / grow_epochs: the stage schedule (prog/progressive.py:4-31);
         get_batch(r): a training batch (images at ANY size -- the stem resizes to r -- and a token-label target for r // 16).
@@ -49,7 +50,11 @@ class AutoProgDriver:
         replay one graph per candidate drawn (<= 9 per search), captured on the search supernet's slabs the same way.
         With DropPath off a graphed run is bit-identical to the eager one; with it the masks come from the same generator at replay time.
         clip_grad / clip_mode: the reference's --clip-grad / --clip-mode (main_prog.py:129-132, prog/scaler.py:60-68), applied inside the fused
-        optimizer step (FlatAdamWEma.step) of every update, eager or replayed."""
+        optimizer step (FlatAdamWEma.step) of every update, eager or replayed.
+        get_val_batches(): an iterable of (images, labels) validation batches, called once per pass.  When given, the model and then every
+        EMA copy are validated after each training epoch (main_prog.py:889-906, prog/validate.py) and the metrics (loss / top1 / top5, the
+        EMA copies' with the suffix _EMA_{decay}) join that epoch's `history` entry; None (default): no validation, `history` as before."""
+        self.get_val_batches = get_val_batches
         self.use_graphs, self.graph_after = bool(use_graphs), int(graph_after)
         self.clip_grad, self.clip_mode = clip_grad, clip_mode
         self._graphs, self._eager_seen = {}, {}
@@ -278,7 +283,20 @@ class AutoProgDriver:
                                      loss=tot / self.steps_per_epoch))
             self.log("epoch %d: r=%d l=%d loss %.4f" % (epoch, self.current_r, self.current_l, tot / self.steps_per_epoch))
             self._distribute_bn()
+            if self.get_val_batches is not None:
+                self.history[-1].update(self._validate())
         return self.history
+
+    def _validate(self):
+        """main_prog.py:889-906: the model, then each EMA copy (after the BatchNorm statistics were distributed), on the validation batches"""
+        from .validate import validate, validate_ema
+        self._eager()
+        metrics = validate(self.model, self.get_val_batches(), reducer=self.reducer)
+        if getattr(self.opt, "ema_decays", None):
+            metrics.update(validate_ema(self.model, self.opt, self.get_val_batches, reducer=self.reducer))
+        self._activate(self.current_l, self.current_r, self.current_dp)
+        self.log("epoch validation: %s" % {k: round(v, 4) for k, v in metrics.items()})
+        return dict(metrics)
 
     def _distribute_bn(self):
         """main_prog.py:883-887: `if args.distributed and args.dist_bn in ('broadcast', 'reduce')` after every training epoch, :1634-1637

@@ -120,7 +120,12 @@ typedef struct ap_gemm_epilogue {
     int gelu;                   /* 1: out = gelu_erf(v) (models/volo.py:157); 2: the same, and preact_out receives gelu'(v) instead of v;
                                  * 3 (ABI version 6): as 2, but preact_out is an UNSIGNED CHAR [M, ldc] tensor of 8-bit fixed-point codes
                                  * code = clamp(rint(202 * gelu'(v)) + 26, 0, 255), i.e. gelu' = (code - 26) / 202 on [-0.1287, 1.1337] (gelu' lives in
-                                 * [-0.1290, 1.1290]; 0, 1/2 and 1 are exact codes): half the bytes of the bf16 derivative, |error| <= 1/404 */
+                                 * [-0.1290, 1.1290]; 0, 1/2 and 1 are exact codes): half the bytes of the bf16 derivative, |error| <= 1/404;
+                                 * 4 (forward-only launches, additive in ABI version 7): `out` holds exactly the bits mode 3 stores there and nothing
+                                 * else is written -- preact_out is ignored and may be NULL.  Needs a bias; no residual / mul_by / dgelu_of / q8_out.
+                                 * Taken by the launches the 8-phase kernel or the weight-stationary kernel serves with the GELU table;
+                                 * AP_ERR_UNSUPPORTED for any other launch (M <= 256, K % 64 != 0, M < 4096, AP_GELU_TABLE=0, ...): the caller then
+                                 * issues mode 3 with a side buffer */
     ap_bf16* preact_out;        /* with gelu: also store v (the pre-activation; gelu = 2: its activation derivative) here, ld = ldc */
     const ap_bf16* dgelu_of;    /* out = v * gelu'(dgelu_of[m,n]) (backward of the above), ld = ldc */
     const float* row_scale;     /* [ceil(M/rows_per_scale)] or NULL */
@@ -176,6 +181,11 @@ typedef struct ap_mlp_fused_args {
     float* ln_mean; float* ln_rstd;
 } ap_mlp_fused_args;
 int ap_mlp_fused(const ap_mlp_fused_args* args, ap_stream_t stream);
+/* The forward of ap_mlp_fused for a pass that no backward follows (additive in ABI version 7): `out` is bit-identical to ap_mlp_fused's for
+ * the same arguments; hidden_out, codes, ln_out, ln_mean and ln_rstd may be NULL and are never written.  backward must be 0 (AP_ERR_SHAPE).
+ * Same shape contract (c = 384, hidden = 3 c, m % 128 == 0, the GELU table at hand; AP_MLP_FUSED_V=1 has no such kernel): AP_ERR_UNSUPPORTED
+ * otherwise. */
+int ap_mlp_fused_infer(const ap_mlp_fused_args* args, ap_stream_t stream);
 
 /* ---- fp8 forward GEMM (BASELINE configs[4] "mixed MFMA fp8 GEMM"): OCP e4m3 operands, fp32 accumulation, bf16 output.
  * y = sat(x * scale[0]) -> e4m3, n % 16 == 0; amax (nullable): amax[0] = max(amax[0], max |x|) for the next step's scale */
@@ -317,6 +327,14 @@ int ap_mix_token_swap_dev(const ap_bf16* x, ap_bf16* y, int B, int H, int W, int
  * (columns C..ldx-1 of dlogits are zeroed).
  * mix_batches = B > 0: the target of batch b is mix_lam * t[b] + (1 - mix_lam) * t[B-1-b] (the mix-token image label,
  * loss/cross_entropy.py:151-152) -- no mixed copy of the target is materialised; 0: plain.       */
+/* Validation statistics, per row (additive in ABI version 7): logits bf16 [rows, ld], n_classes <= ld valid columns, labels int64 [rows] ->
+ *   loss[row] = logsumexp(z) - z[label]                                    (fp32 accumulation)
+ *   rank[row] = #{c : z[c] > z[label]}   -- STRICTLY greater: a row is top-k correct iff 0 <= rank < k.  On ties this is the most favourable
+ *               of the orders torch.topk may return (its choice among equal values is unspecified); without ties the two agree.
+ * A row whose label is outside [0, n_classes) gets loss = 0, rank = -1 (the padding of a last batch; nothing is read through such a label).
+ * rows = 0 succeeds without a launch.  No atomics, no host synchronisation. */
+int ap_classify_stats(const ap_bf16* logits, int ld, int n_classes, const int64_t* labels, float* loss, int* rank, int64_t rows,
+                      ap_stream_t stream);
 int ap_soft_ce_fwd_bwd(const ap_bf16* logits, int ldx, const float* target, int64_t t_sb,
                        int64_t t_sc, int64_t t_sn, int rows_per_batch, float* row_loss,
                        ap_bf16* dlogits, float grad_scale, int64_t M, int C,
