@@ -51,6 +51,14 @@ class LnReduce(Structure):
     _fields_ = [("partial", c_void_p), ("n_partial", c_int), ("C", c_int), ("dgamma", c_void_p), ("dbeta", c_void_p)]
 
 
+class InputPrepArgs(Structure):
+    """ap_input_prep_args (include/autoprog_hip.h)"""
+    _fields_ = [("u8", c_void_p), ("in_layout", c_int), ("B", c_int), ("Hi", c_int), ("Wi", c_int),
+                ("out", c_void_p), ("out_layout", c_int), ("Ho", c_int), ("Wo", c_int),
+                ("table", c_void_p), ("params", c_void_p), ("mix_enabled", c_int), ("boxes", c_void_p), ("boxes_host", c_void_p),
+                ("n_boxes", c_int), ("erase_mode", c_int)]
+
+
 class PatchMap(Structure):
     """ap_patch_map (include/autoprog_hip.h)"""
     _fields_ = [("group", c_int), ("group_stride", c_int), ("row_stride", c_int), ("kseg", c_int), ("kseg_stride", c_int)]
@@ -61,6 +69,7 @@ TN_MAX_GROUP_DET = 8       # the deterministic mode (workspace) takes 8
 BF8_COLSUM_SPLITS = 64     # AP_BF8_COLSUM_SPLITS: rows of the deterministic column-sum workspace of ap_quantize_bf8
 FP8_E4M3, FP8_E5M2 = 0, 1  # AP_FP8_E4M3 / AP_FP8_E5M2
 LN_MAX_BATCH = 12          # AP_LN_MAX_BATCH
+PREP_MAX_BOXES = 8         # AP_PREP_MAX_BOXES
 _P, _I, _L, _F = c_void_p, c_int, c_int64, c_float
 _SIGNATURES = {
     "ap_abi_version": (c_int, []),
@@ -152,6 +161,7 @@ _SIGNATURES["ap_sum_reps_acc"] = (_I, [_P, _P, _L, _I, _P])
 _SIGNATURES["ap_mlp_fused"] = (_I, [POINTER(MlpFusedArgs), _P])
 _SIGNATURES["ap_mlp_fused_infer"] = (_I, [POINTER(MlpFusedArgs), _P])
 _SIGNATURES["ap_classify_stats"] = (_I, [_P, _I, _I, _P, _P, _P, _L, _P])
+_SIGNATURES["ap_input_prep"] = (_I, [POINTER(InputPrepArgs), _P])
 _SIGNATURES["ap_calib_copy"] = (_I, [_P, _P, _L, _P])
 _SIGNATURES["ap_calib_mfma"] = (_I, [_P, _P, _I, _P])
 

@@ -1353,6 +1353,37 @@ class SparseTokenLabelCEFn(torch.autograd.Function):
         return dc, da.reshape(B, N, C), None, None, None, None, None, None
 
 
+class MixedLabelCEFn(torch.autograd.Function):
+    """SoftTargetCrossEntropy on a Mixup / CutMix batch whose target is still (labels, lam) -- data.MixedLabelTarget -- instead of the
+    dense [B, C] tensor timm's mixup_target builds every step (main_prog.py:978-979 -> loss/cross_entropy.py:21-36): the sparse
+    soft-target kernel with ONE (label, 1.0) pair per image, the label smoothing, and the batch mix lam * t[b] + (1 - lam) * t[B-1-b]
+    formed by the kernel.  lam: a host float, or an object with `lam_ptr` (lam in device memory: a graph replay)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ones, smoothing, lam):
+        B, C = logits.shape
+        ld = ops.round_up(C, 8)
+        if ld != C or not logits.is_contiguous():
+            xp = torch.zeros((B, ld), dtype=BF16, device=logits.device)
+            xp[:, :C] = logits
+        else:
+            xp = logits
+        labels, ones = labels.view(B, 1), ones.view(B, 1)             # K = 1 pair per row
+        if hasattr(lam, "lam_ptr"):
+            row_loss, dl = ops.soft_ce_sparse_fwd_bwd(xp, C, labels, ones, 1, 0, 1, smoothing, 1.0 / B, mix_lam=1.0, mix_batches=B, mix_lam_ptr=lam.lam_ptr)
+        else:
+            row_loss, dl = ops.soft_ce_sparse_fwd_bwd(xp, C, labels, ones, 1, 0, 1, smoothing, 1.0 / B, mix_lam=lam, mix_batches=B if lam < 1 else 0)
+        ctx.save_for_backward(dl)
+        ctx.C = C
+        return row_loss.mean()
+
+    @staticmethod
+    def backward(ctx, g):
+        (dl,) = ctx.saved_tensors
+        out = ops.row_scale(dl, g.reshape(1).float().contiguous(), dl.shape[0])
+        return (out if out.shape[1] == ctx.C else out[:, :ctx.C]), None, None, None, None
+
+
 class OutlookCoreFn(torch.autograd.Function):
     """unfold -> softmax -> attn@v -> fold (models/volo.py:83-98) on v [B,H,W,C], logits [B*h*w, ld]."""
 

@@ -17,6 +17,9 @@ same numpy calls in the same order as the eager forward, so a graphed run and an
     gs.capture()                                                        # warm-up steps on a side stream, then one captured step
     loss = gs.step(new_images, new_target)                              # copies the batch in, refreshes the scalars, replays
 
+`images` may be a data.PreparedBatch (a loader's uint8 batch with the step's Mixup / CutMix / RandomErasing decisions) and `target` its
+MixedLabelTarget: the static buffers are then the uint8 batch, the labels and the batch's parameter block.
+
 One graph per elastic configuration: `set_sample_config` changes which kernels run, so the driver keeps a GraphedStep per (l, r).
 Single-rank only (RCCL collectives are not captured here): with world > 1 the eager step runs."""
 import numpy as np
@@ -111,8 +114,10 @@ class GraphedStep:
             raise ValueError("GraphedStep: single-rank only (the gradient exchange is not captured)")
         self.model, self.loss_fn, self.reducer, self.opt = model, loss_fn, reducer, opt
         self.clip_grad, self.clip_mode = clip_grad, clip_mode
-        self.images = images.clone()
-        self.target = _clone_target(target)
+        # a data.PreparedBatch in place of the images: a static uint8 buffer and a static copy of the step's parameter block (mix mode, lam,
+        # CutMix box, noise key, erase records), refreshed by ONE device copy in front of every replay; the loss reads lam from that block
+        self.images = _clone_images(images)
+        self.target = _clone_target(target, self.images)
         self.scalars = StepScalars(self.images.device)
         self.graph = None
         self.loss = None
@@ -177,7 +182,7 @@ class GraphedStep:
         if self.graph is None:
             raise RuntimeError("GraphedStep.step() before capture()")
         if images is not None:
-            self.images.copy_(images, non_blocking=True)
+            _copy_images(self.images, images)
         if target is not None:
             _copy_target(self.target, target)
         self.model.step_scalars = self.scalars
@@ -191,17 +196,49 @@ class GraphedStep:
             self.model.step_scalars = None
 
 
-def _clone_target(t):
+def _clone_images(images):
+    from .data import PreparedBatch
+    if isinstance(images, PreparedBatch):
+        # (no host copy of the block: the records were checked when the batch was prepared, and a replay goes through no entry point)
+        return PreparedBatch(images.u8.clone(), images.layout, images.table, images.block.clone(), None, images.mix, images.n_boxes,
+                             images.erase_mode, images.lam, images.owner)
+    return images.clone()
+
+
+def _copy_images(dst, src):
+    from .data import PreparedBatch
+    if isinstance(dst, PreparedBatch):
+        if not isinstance(src, PreparedBatch):
+            raise TypeError("this graph was captured on a PreparedBatch")
+        dst.u8.copy_(src.u8, non_blocking=True)
+        dst.block.copy_(src.block, non_blocking=True)
+        dst.lam = src.lam
+    else:
+        dst.copy_(src, non_blocking=True)
+
+
+def _clone_target(t, images=None):
+    from .data import MixedLabelTarget, PreparedBatch
     from .loss.cross_entropy import SparseTokenLabelTarget
     if isinstance(t, SparseTokenLabelTarget):
         return SparseTokenLabelTarget(t.idx.clone(), t.val.clone(), t.smoothing)
+    if isinstance(t, MixedLabelTarget):
+        if not isinstance(images, PreparedBatch):
+            raise TypeError("a MixedLabelTarget goes with the PreparedBatch whose parameter block holds its lam")
+        m = MixedLabelTarget(t.labels.clone(), t.lam, t.smoothing, t.num_classes, block=images.block)
+        m.from_device = True                 # lam of the loss: word 1 of the static block (mix_lam_dev), whatever the replay's draw was
+        return m
     return t.clone()
 
 
 def _copy_target(dst, src):
+    from .data import MixedLabelTarget
     from .loss.cross_entropy import SparseTokenLabelTarget
     if isinstance(dst, SparseTokenLabelTarget):
         dst.idx.copy_(src.idx, non_blocking=True)
         dst.val.copy_(src.val, non_blocking=True)
+    elif isinstance(dst, MixedLabelTarget):
+        dst.labels.copy_(src.labels, non_blocking=True)
+        dst.lam = src.lam
     else:
         dst.copy_(src, non_blocking=True)

@@ -31,6 +31,17 @@ class SoftTargetCrossEntropy(nn.Module):
     """reference SoftTargetCrossEntropy (loss/cross_entropy.py:21-36)"""
 
     def forward(self, x, target):
+        from ..data import MixedLabelTarget
+        if isinstance(target, MixedLabelTarget):
+            # a Mixup / CutMix batch of data.DeviceBatchPrep: (labels, lam) go to the sparse kernel as they are; rows wider than it takes
+            # are densified (timm's mixup_target) and take the dense kernel
+            C = x.shape[-1]
+            if x.dim() == 2 and target.labels.is_cuda and x.shape[0] == target.labels.shape[0] and -(-C // 8) * 8 <= SPARSE_CE_MAX_CLASSES:
+                lam = target if target.from_device else target.lam
+                return AF.MixedLabelCEFn.apply(x.to(torch.bfloat16), target.labels, target.ones, target.smoothing, lam)
+            if target.from_device:
+                raise NotImplementedError("a graph-mode step (lam in device memory) needs the sparse soft-target kernel")
+            target = target.dense(C)
         return _dense_ce(x.to(torch.bfloat16), target)
 
 

@@ -12,6 +12,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import functional as AF
+from ..data import PreparedBatch
 from ..prog.helpers import get_new_layer_idx
 from .registry import register_model
 from .volo import Transformer, DropPathRng, trunc_normal_, IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD
@@ -42,6 +43,12 @@ class PatchEmbed16(nn.Module):
     def forward(self, x):
         if not x.is_cuda:
             raise RuntimeError("autoprog_amd models run on the GPU only (no CPU fallback)")
+        if isinstance(x, PreparedBatch):
+            # a loader's uint8 batch (data.DeviceBatchPrep.prep): normalise / mix / erase in one launch that writes the bf16 image at the
+            # batch's own size (this embedding never resizes), NHWC; the patches below are then gathered from its NCHW view
+            if x.shape[-1] != x.shape[-2]:
+                raise RuntimeError("a PreparedBatch needs square images")
+            x = x.run(x.shape[-1], "nhwc").permute(0, 3, 1, 2)
         B, Cin, H, W = x.shape
         p = self.patch_size[0]
         h, w = H // p, W // p

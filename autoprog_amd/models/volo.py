@@ -22,6 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import functional as AF
+from ..data import PreparedBatch
 from ..prog.helpers import ActiveLayerMask
 from .registry import register_model
 
@@ -334,17 +335,21 @@ class PatchEmbed(nn.Module):
         torch.nn.functional.conv2d (MIOpen, bf16 channels_last) with the same HIP BatchNorm + ReLU kernels."""
         if not x.is_cuda:
             raise RuntimeError("autoprog_amd models run on the GPU only (no CPU fallback)")
+        # a loader's uint8 batch with the step's mix / erase decisions (data.DeviceBatchPrep.prep): normalise, mix, erase and the resize
+        # below are ONE launch (ops.input_prep) that writes what the resize kernels would have written from the prepared fp32 tensor
+        prepared = isinstance(x, PreparedBatch)
+        plain = prepared or (x.dtype == torch.float32 and not x.requires_grad)
         fused = self.compute_dtype == BF16
         # the stage's resolution applies to training-mode forwards (training steps and the train-mode EMA probes of a search);
         # an eval() forward keeps the resolution it is given unless resize_in_eval is set
         size = self.resize_to if (self.resize_to and (self.training or self.resize_in_eval)) else x.shape[-1]
         first = None
-        if (fused and self.stem_conv and self.hip_conv and x.dtype == torch.float32 and x.shape[-1] == x.shape[-2] and not x.requires_grad
+        if (fused and self.stem_conv and self.hip_conv and plain and x.shape[-1] == x.shape[-2]
                 and size % 2 == 0 and tuple(self.conv[0].weight.shape) in ((64, 3, 7, 7), (128, 3, 7, 7)) and self.conv[0].stride[0] == 2):
             # resize + space-to-depth in one kernel, then the 7x7 / stride 2 convolution of csrc/conv7.hip with its BatchNorm + ReLU
             from .. import ops
             bn = self.conv[1]
-            xs = ops.resize_bilinear_s2d16(x.contiguous(), size)
+            xs = x.run(size, "s2d16") if prepared else ops.resize_bilinear_s2d16(x.contiguous(), size)
             if (AF.STEM_FUSE_BN and all(tuple(self.conv[i].weight.shape) == (64, 64, 3, 3) for i in (3, 6))
                     and all(self.conv[i].running_mean is not None for i in (1, 4, 7))):
                 # the three convolutions as one node: the activations between them are applied inside the next convolution's staging
@@ -366,11 +371,13 @@ class PatchEmbed(nn.Module):
             first = AF.Conv7BNReLUFn.apply(xs, self.conv[0].weight, bn.weight, bn.bias,
                                            bn.running_mean, bn.running_var, self.training, bn.momentum, bn.eps)
             x = first.permute(0, 3, 1, 2)
-        elif fused and x.dtype == torch.float32 and x.shape[-1] == x.shape[-2] and not x.requires_grad:
+        elif fused and plain and x.shape[-1] == x.shape[-2]:
             # one kernel: bilinear resize to the step's resolution (identity when the sizes agree) + NCHW fp32 -> NHWC bf16
             from .. import ops
-            x = ops.resize_bilinear_nhwc(x.contiguous(), size).permute(0, 3, 1, 2)      # NCHW view of channels_last memory
+            x = (x.run(size, "nhwc") if prepared else ops.resize_bilinear_nhwc(x.contiguous(), size)).permute(0, 3, 1, 2)      # NCHW view of channels_last memory
         else:
+            if prepared:
+                raise RuntimeError("a PreparedBatch needs the bf16 stem and square images (there is no torch fallback for ops.input_prep)")
             if size != x.shape[-1]:
                 x = F.interpolate(x.float(), size=(size, size), mode="bilinear", align_corners=False)
             # one pass: NCHW fp32 -> NHWC(channels_last) in the compute dtype (autocast would otherwise cast a second time)

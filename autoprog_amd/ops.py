@@ -10,7 +10,7 @@ import os
 
 import torch
 
-from ._lib import GemmEpilogue, AutoProgHipError, check, lib
+from ._lib import GemmEpilogue, InputPrepArgs, PREP_MAX_BOXES, AutoProgHipError, check, lib
 
 BF16 = torch.bfloat16
 
@@ -1032,6 +1032,48 @@ def conv3x3_c64_wgrad(x, dy, dw, bn_in=None):
         return dw
     check(lib.ap_conv3x3_c64_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), B, H, W, ws.data_ptr(), ws_bytes, _stream()), "ap_conv3x3_c64_wgrad")
     return dw
+
+
+# ------------------------------------------------------------------------------------- a loader's uint8 batch -> the stem's input
+PREP_PARAM_WORDS, PREP_BOX_WORDS = 16, 8          # the device block of ap_input_prep: 16 words of per-step parameters, then 8 per box record
+_PREP_ERASE = {"const": 0, "rand": 1, "pixel": 2}
+
+
+def input_prep(u8, size, out="s2d16", table=None, params=None, layout="nchw", mix=False, n_boxes=0, erase_mode="const", host_block=None):
+    """uint8 [B,3,Hi,Wi] (layout "nchw", what timm's fast_collate yields) or [B,Hi,Wi,3] ("nhwc") -> bf16 [B,size/2,size/2,16] (out
+    "s2d16", the layout of resize_bilinear_s2d16) or [B,size,size,3] ("nhwc", that of resize_bilinear_nhwc): normalise by `table`
+    (fp32 [3,256] on the device), Mixup / CutMix with image B-1-b, RandomErasing and the bilinear resize in one launch
+    (include/autoprog_hip.h, ap_input_prep).  `params`: int32 device tensor, PREP_PARAM_WORDS words of per-step parameters followed by
+    B * n_boxes box records of PREP_BOX_WORDS words (data.DeviceBatchPrep fills it); None: no mix, no erase.  `mix` False ignores the
+    block's mix mode.  `host_block`: a CPU copy of `params` whose records are checked against the image before the launch."""
+    _req(u8, torch.uint8, "u8"); _req(table, torch.float32, "table")
+    if u8.dim() != 4 or u8.shape[1 if layout == "nchw" else 3] != 3 or layout not in ("nchw", "nhwc"):
+        raise AutoProgHipError("input_prep: a uint8 [B,3,H,W] (nchw) or [B,H,W,3] (nhwc) batch, got %s as %s" % (tuple(u8.shape), layout))
+    if out not in ("s2d16", "nhwc") or erase_mode not in _PREP_ERASE or tuple(table.shape) != (3, 256):
+        raise AutoProgHipError("input_prep: out %r, erase_mode %r, table %s" % (out, erase_mode, tuple(table.shape)))
+    B = u8.shape[0]
+    Hi, Wi = (u8.shape[2], u8.shape[3]) if layout == "nchw" else (u8.shape[1], u8.shape[2])
+    a = InputPrepArgs()
+    a.u8, a.in_layout, a.B, a.Hi, a.Wi = u8.data_ptr(), int(layout == "nhwc"), B, Hi, Wi
+    a.out_layout, a.Ho, a.Wo = int(out == "nhwc"), size, size
+    a.table = table.data_ptr()
+    a.mix_enabled, a.n_boxes, a.erase_mode = int(bool(mix)), int(n_boxes), _PREP_ERASE[erase_mode]
+    if params is not None:
+        _req(params, torch.int32, "params")
+        words = PREP_PARAM_WORDS + B * max(0, min(int(n_boxes), PREP_MAX_BOXES)) * PREP_BOX_WORDS
+        if params.numel() < words or (host_block is not None and (host_block.is_cuda or host_block.dtype != torch.int32 or host_block.numel() < words)):
+            raise AutoProgHipError("input_prep: the parameter block holds %d words, %d needed" % (params.numel(), words))
+        a.params = params.data_ptr()
+        if n_boxes:
+            a.boxes = params.data_ptr() + 4 * PREP_PARAM_WORDS
+            if host_block is not None:
+                a.boxes_host = host_block.data_ptr() + 4 * PREP_PARAM_WORDS
+    elif mix or n_boxes:
+        raise AutoProgHipError("input_prep: mix / erase need the parameter block")
+    y = torch.empty((B, size // 2, size // 2, 16) if out == "s2d16" else (B, size, size, 3), dtype=BF16, device=u8.device)
+    a.out = y.data_ptr()
+    check(lib.ap_input_prep(ctypes.byref(a), _stream()), "ap_input_prep")
+    return y
 
 
 # ------------------------------------------------------------------------------------- stem 7x7 / stride 2 convolution (3 -> 64)

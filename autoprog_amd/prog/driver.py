@@ -31,7 +31,8 @@ def _sync():
 class AutoProgDriver:
     def __init__(self, model, loss_fn, optimizer, reducer, get_batch, r_list, l_list, dp_list, grow_epochs, steps_per_epoch,
                  search_epochs=2, auto_grow=True, probe_batches=4, time_steps=4, seed=0, log=None, original_batch_splits=1,
-                 r_max=None, dist_bn="", use_graphs=False, graph_after=2, clip_grad=None, clip_mode="norm", get_val_batches=None):
+                 r_max=None, dist_bn="", use_graphs=False, graph_after=2, clip_grad=None, clip_mode="norm", get_val_batches=None,
+                 batch_prep=None, re_list=None):
         """model: supernet sized for l_list[-1] (e.g. volo_h12_l18); optimizer: FlatAdamWEma over it; reducer: its
         GradientBucketReducer; r_list / l_list / dp_list / grow_epochs: the stage schedule (prog/progressive.py:4-31);
         get_batch(r): a training batch (images at ANY size -- the stem resizes to r -- and a token-label target for r // 16).
@@ -53,7 +54,18 @@ class AutoProgDriver:
         optimizer step (FlatAdamWEma.step) of every update, eager or replayed.
         get_val_batches(): an iterable of (images, labels) validation batches, called once per pass.  When given, the model and then every
         EMA copy are validated after each training epoch (main_prog.py:889-906, prog/validate.py) and the metrics (loss / top1 / top5, the
-        EMA copies' with the suffix _EMA_{decay}) join that epoch's `history` entry; None (default): no validation, `history` as before."""
+        EMA copies' with the suffix _EMA_{decay}) join that epoch's `history` entry; None (default): no validation, `history` as before.
+        batch_prep: a data.DeviceBatchPrep.  A uint8 image tensor from get_batch then goes through batch_prep.prep (normalise, Mixup /
+        CutMix, RandomErasing and the stage's resize become one launch inside the patch embedding) and integer labels [B] that come
+        with it become its MixedLabelTarget; anything else passes as it is.  re_list: the per-stage RandomErasing probability (the
+        seventh value of prog.progressive.progressive_schedule, beside r_list / l_list / dp_list): batch_prep.re_prob is set to
+        re_list[stage] at every stage change.  Both None (default): batches pass untouched."""
+        if re_list is not None and (batch_prep is None or len(re_list) != len(r_list)):
+            raise ValueError("re_list needs a batch_prep and one entry per stage")
+        self.batch_prep, self.re_list = batch_prep, (list(re_list) if re_list is not None else None)
+        self._raw_get_batch = get_batch
+        if batch_prep is not None:
+            get_batch = self._prepared_batch
         self.get_val_batches = get_val_batches
         self.use_graphs, self.graph_after = bool(use_graphs), int(graph_after)
         self.clip_grad, self.clip_mode = clip_grad, clip_mode
@@ -72,6 +84,14 @@ class AutoProgDriver:
         self.history = []                     # one dict per epoch: stage, (r, l), mean loss, search decisions
         self.current_r, self.current_l, self.current_dp = None, None, 0.0
         self.mask = None
+
+    def _prepared_batch(self, *a):
+        images, target = self._raw_get_batch(*a)
+        if torch.is_tensor(images) and images.dtype == torch.uint8:
+            images = self.batch_prep.prep(images)
+            if torch.is_tensor(target) and target.dim() == 1 and not target.dtype.is_floating_point:
+                target = images.target(target)
+        return images, target
 
     # ------------------------------------------------------------------ elastic plumbing
     def _config(self, l, r):
@@ -266,6 +286,8 @@ class AutoProgDriver:
         for epoch in range(num_epochs):
             if epoch in self.grow_epochs:
                 stage = self.grow_epochs.index(epoch)
+                if self.re_list is not None:                               # the stage's loader is built with its own re_prob
+                    self.batch_prep.re_prob = float(self.re_list[stage])
                 if self.auto_grow and stage < len(self.grow_epochs) - 1:
                     r, l = self.search(stage, epoch)
                     skip.update(range(epoch, epoch + self.search_epochs))      # the search consumed these epochs (main_prog.py:856-857)

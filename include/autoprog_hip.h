@@ -506,6 +506,40 @@ int ap_adamw_ema_step(float* p, const float* g, float* m, float* v, const unsign
 int ap_batched_transpose_bf16(const ap_bf16* src, ap_bf16* dst, const void* desc_dev, int count, int total_tiles,
                               ap_stream_t stream);
 
+/* ---- a loader's batch, prepared on the device in one launch (additive in ABI version 7; csrc/input_prep.hip).  What the reference does
+ * between its loader and its model every step: timm's PrefetchLoader (.float().sub_(mean).div_(std), RandomErasing on the GPU), the
+ * collate-time Mixup / CutMix of main_prog.py:195-207,978-979 and the resize of main_prog.py:973-974.  uint8 in, the stem's bf16 layout
+ * out.  The value of source pixel (b, c, y, x), in this order:
+ *   1. normalise   n = table[c][u8]: `table` is 3 x 256 fp32, (v - 255 mean[c]) / (255 std[c]) computed by the caller
+ *   2. mix         (mix_enabled != 0; mode read from `params` in DEVICE memory) with the partner image B-1-b (timm's x.flip(0)):
+ *                  mixup m = lam * n[b] + (1 - lam) * n[B-1-b]; cutmix m = n[B-1-b] inside rows [yl, yh) x columns [xl, xh), n[b] outside
+ *   3. erase       up to n_boxes records per image in DEVICE memory (`boxes`: [B][n_boxes] records of 8 x 4 bytes: int32 top, left, h, w,
+ *                  fp32 v0, v1, v2, one unused word; h == 0: no box; a later record wins where two overlap).  Inside a box the value of
+ *                  channel c becomes 0 (AP_ERASE_CONST), the record's v[c] (AP_ERASE_RAND) or a standard normal that is a pure function
+ *                  of (seed, b, c, y, x) (AP_ERASE_PIXEL: Philox-4x32-10 on the counter (x, y, b, 0) keyed by the seed, Box-Muller)
+ *   4. resize      bilinear, align_corners = False, to Ho x Wo, with the arithmetic of ap_resize_bilinear_s2d16 / ap_resize_bilinear_nhwc
+ *                  operation for operation: with no mix and no erase the output is bit-identical to those kernels fed the normalised tensor
+ * params (DEVICE, 16 x 4 bytes): int32 [0] mix mode (0 none, 1 mixup, 2 cutmix), fp32 [1] lam, int32 [2..5] yl, yh, xl, xh,
+ * uint32 [6..7] seed, fp32 [8] 1 - lam; the rest unused.  A graph replay sees whatever the block holds when it runs.
+ * boxes_host (nullable): a host copy of the records; when given every record is checked against the image (AP_ERR_SHAPE).  The kernel
+ * only ever COMPARES coordinates with a box, so a record it was not shown cannot make it read or write out of bounds.
+ * u8 must be 16-byte aligned.  out_layout AP_PREP_S2D16 needs even Ho, Wo; n_boxes <= 8; B == 0 succeeds without a launch. */
+enum { AP_PREP_NCHW = 0, AP_PREP_NHWC = 1 };                    /* in_layout: u8 [B,3,Hi,Wi] / [B,Hi,Wi,3] */
+enum { AP_PREP_S2D16 = 0, AP_PREP_OUT_NHWC = 1 };               /* out_layout: bf16 [B,Ho/2,Wo/2,16] / [B,Ho,Wo,3] */
+enum { AP_ERASE_CONST = 0, AP_ERASE_RAND = 1, AP_ERASE_PIXEL = 2 };
+#define AP_PREP_MAX_BOXES 8
+typedef struct ap_input_prep_args {
+    const unsigned char* u8; int in_layout; int B, Hi, Wi;
+    ap_bf16* out; int out_layout; int Ho, Wo;
+    const float* table;              /* DEVICE fp32 [3][256] */
+    const int* params;               /* DEVICE block above; NULL: no mix, seed 0 */
+    int mix_enabled;                 /* 0: the mix mode of `params` is ignored (no partner image is staged) */
+    const int* boxes;                /* DEVICE records, NULL with n_boxes == 0 */
+    const int* boxes_host;           /* nullable host copy, validated */
+    int n_boxes, erase_mode;
+} ap_input_prep_args;
+int ap_input_prep(const ap_input_prep_args* args, ap_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
