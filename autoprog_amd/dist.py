@@ -74,7 +74,7 @@ class GradientBucketReducer:
         self._owned = {id(p) for p in self.params}
         self._no_sink = set()
 
-    # ------------------------------------------------------------------ gradient sink (functional.set_grad_sink)
+    # ------------------------------------------------------------------ gradient sink (wgrad.set_grad_sink)
     def owns(self, p):
         return id(p) in self._owned and id(p) not in self._no_sink and p.grad is not None
 
@@ -108,7 +108,7 @@ class GradientBucketReducer:
         return self._micro < self.accumulate_steps - 1
 
     def completes_a_bucket(self, held_params):
-        """would releasing these held parameters complete a bucket that has not left yet?  (functional's weight-gradient window asks
+        """would releasing these held parameters complete a bucket that has not left yet?  (the weight-gradient window of wgrad.py asks
         before it decides to launch early)"""
         if self.world <= 1 or self._accumulating():
             return False
@@ -121,7 +121,7 @@ class GradientBucketReducer:
         return any(not self._launched[b] and self._pending[b] == n for b, n in waiting.items())
 
     def hold(self, params):
-        """the gradients of these parameters are still to be written (functional's weight-gradient window holds their problems): autograd
+        """the gradients of these parameters are still to be written (the weight-gradient window of wgrad.py holds their problems): autograd
         runs their AccumulateGrad nodes -- and the post-accumulate hook -- when the block's backward returns, with nothing to accumulate;
         that must not count as ready.  param_ready() releases them."""
         self._held.update(id(p) for p in params if p is not None)
@@ -130,14 +130,14 @@ class GradientBucketReducer:
         """let the fused block backward passes accumulate straight into the slab (no per-parameter
         temporaries, no autograd add kernels).  `model.multi_use_parameters()` (when present) names the
         parameters that stay on the autograd path (see exclude_from_sink)."""
-        from . import functional
+        from . import wgrad
         if model is not None and hasattr(model, "multi_use_parameters"):
             self.exclude_from_sink(model.multi_use_parameters())
-        functional.set_grad_sink(self)
+        wgrad.set_grad_sink(self)
 
     def uninstall_sink(self):
-        from . import functional
-        functional.set_grad_sink(None)
+        from . import wgrad
+        wgrad.set_grad_sink(None)
 
     # ------------------------------------------------------------------ hooks
     def _on_grad(self, p):
@@ -164,8 +164,8 @@ class GradientBucketReducer:
     # ------------------------------------------------------------------ step API
     def zero_grad(self):
         """gradients stay attached to the slab (never set to None)"""
-        from . import functional
-        functional.reset_wgrad_window()         # (a backward pass that raised may have left problems behind)
+        from . import wgrad
+        wgrad.reset_wgrad_window()              # (a backward pass that raised may have left problems behind)
         self.flat.zero_()
         self._pending_scale = 1.0               # a deferred 1/world that nobody consumed dies with the gradients it belonged to
         self._pending = [len(m) for (_, _, m) in self.buckets]
@@ -180,9 +180,9 @@ class GradientBucketReducer:
     def finish(self):
         """call after backward(): reduce buckets whose hooks did not all fire (skipped layers), wait
         for every collective and turn sums into means."""
-        from . import functional
-        functional.flush_wgrad_window()         # (empty after a backward pass: the autograd engine's final callback has flushed it)
-        functional.join_wgrad_stream()          # side-stream weight gradients land before anyone reads the slab
+        from . import wgrad
+        wgrad.flush_wgrad_window()              # (empty after a backward pass: the autograd engine's final callback has flushed it)
+        wgrad.join_wgrad_stream()               # side-stream weight gradients land before anyone reads the slab
         if self._accumulating():                # a micro-batch that only accumulates: nothing is exchanged, nothing was marked ready
             self._micro += 1
             self._held = set()

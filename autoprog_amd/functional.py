@@ -13,7 +13,7 @@ import os
 
 import torch
 
-from . import ops
+from . import ops, wgrad
 from ._lib import AutoProgHipError
 
 BF16 = torch.bfloat16
@@ -76,294 +76,9 @@ class _WeightBank:
 bank = _WeightBank()
 
 
-def _zeros_like_params(params):
-    """one zeroed fp32 slab + per-parameter views (gradient accumulators for one block)"""
-    sizes = [p.numel() if p is not None else 0 for p in params]
-    total = sum(sizes)
-    ref = next(p for p in params if p is not None)
-    slab = torch.zeros(total, dtype=torch.float32, device=ref.device)
-    out, off = [], 0
-    for p, n in zip(params, sizes):
-        out.append(slab[off:off + n].view(p.shape) if p is not None else None)
-        off += n
-    return out
-
-
-# Optional gradient sink (installed by autoprog_amd.dist.GradientBucketReducer): the block-level
-# backward passes then accumulate parameter gradients IN PLACE into param.grad (views of one flat fp32
-# slab) and signal readiness themselves, instead of returning fresh tensors for autograd to add.
-_grad_sink = None
-
-
-def set_grad_sink(sink):
-    global _grad_sink
-    _grad_sink = sink
-
-
-def _param_grad_buffers(params):
-    """-> (buffers, sink_used).  With a sink: param.grad itself; otherwise one zeroed slab."""
-    sink = _grad_sink
-    if sink is not None and all(p is None or sink.owns(p) for p in params):
-        return [p.grad if p is not None else None for p in params], True
-    return _zeros_like_params(params), False
-
-
-def _finish_param_grads(params, bufs, sink_used, deferred=False):
-    if not sink_used:
-        join_wgrad_stream()              # autograd consumes these buffers on the current stream
-        return bufs
-    if deferred:                         # the weight-gradient window delivers them (flush_wgrad_window)
-        return [None] * len(params)
-    if _grad_sink.needs_stream_join():
-        join_wgrad_stream()              # a bucket all-reduce may be launched from param_ready
-    for p in params:
-        if p is not None:
-            _grad_sink.param_ready(p)
-    return [None] * len(params)
-
-
 def _g2(w):
     """2-D view of a (possibly conv-shaped) weight gradient buffer"""
     return w.view(w.shape[0], -1)
-
-
-# Weight gradients do not feed the backward chain, so they CAN be issued on a side stream and overlap the
-# input-gradient GEMMs / LayerNorm / attention kernels of the main stream.  That paid (23.1 -> 22.0 ms/step) while
-# every layer's weight gradient was its own under-filled launch; with one grouped launch per block (wgrad_batch,
-# 450-512 workgroups = every CU twice) the side stream only adds contention: 19.55 ms/step vs 19.22 on one stream
-# (same box, back to back).  Default: one stream; AP_ASYNC_WGRAD=1 switches the side stream on.
-async_wgrad = os.environ.get("AP_ASYNC_WGRAD", "0") == "1"
-_side_streams = {}
-
-
-def wgrad_stream(device=None):
-    dev = torch.cuda.current_device() if device is None else device
-    st = _side_streams.get(dev)
-    if st is None:
-        st = torch.cuda.Stream(device=dev)
-        _side_streams[dev] = st
-    return st
-
-
-def join_wgrad_stream():
-    """make the current stream wait for every weight-gradient kernel issued so far"""
-    if _side_streams:
-        st = _side_streams.get(torch.cuda.current_device())
-        if st is not None:
-            torch.cuda.current_stream().wait_stream(st)
-
-
-# Weight gradients of one block are collected and issued as ONE grouped launch (ops.gemm_tn_acc_grouped): the
-# launch's workgroups are shared by the block's 4-5 Linear layers, so every layer is split over fewer token
-# ranges -> longer reduction loops and several times fewer fp32 atomics than one launch per layer.
-_wgrad_batch = None
-
-
-class wgrad_batch:
-    """with wgrad_batch(): ... _linear_bwd calls ... ; the collected weight gradients launch on exit -- or, with `sunk` (the gradients
-    accumulate in place into param.grad, nothing is returned to autograd), join the weight-gradient window of the backward pass"""
-
-    def __init__(self, sunk=False, params=()):
-        self.sunk, self.params, self.deferred = sunk, params, False
-
-    def __enter__(self):
-        global _wgrad_batch
-        self.prev = _wgrad_batch
-        _wgrad_batch = []
-        self.ln = []                  # deferred LayerNorm dgamma/dbeta reductions of the block: ops.layernorm_bwd(..., defer=batch.ln)
-        return self
-
-    def __exit__(self, *exc):
-        global _wgrad_batch
-        pending, _wgrad_batch = _wgrad_batch, self.prev
-        if exc[0] is None:
-            if self.sunk and pending and _window_add(pending, self.ln, self.params):
-                self.deferred = True
-            elif pending and not async_wgrad and fuse_ln_reduce:
-                _launch_wgrads(pending, self.ln)                 # the block's LayerNorm dgamma / dbeta reductions ride in the weight-gradient launch
-            else:
-                if self.ln:
-                    ops.layernorm_bwd_reduce_batched(self.ln)    # one launch for the block's LayerNorms (was one per LayerNorm)
-                if pending:
-                    _launch_wgrads(pending)
-        return False
-
-
-# The weight-gradient window.  A block's own launch has 40 output tiles (192 x 192) for 256 CUs, so every problem is cut into ~6 token
-# ranges whose partial tiles meet in fp32 atomics: 21-27 us of a ~100 us launch, bound by the chip's atomic rate, not by anything the
-# kernel does.  Nothing in the backward chain reads a weight gradient, so the blocks' problems are collected -- operands kept alive by
-# the references held here -- and launched once about one tile per CU has come together (six transformer blocks of VOLO-D1): no token
-# axis is cut, the tiles leave as plain read-add-stores (ops.gemm_tn_acc_grouped / k_gemm_tn_8p), results become reproducible.
-# The end of the backward pass flushes what is left (an autograd engine callback).  Only with a gradient sink: the gradients land in
-# param.grad in place, and the sink hears param_ready() at the flush instead of at the end of the block.
-# AP_WGRAD_WINDOW: tiles per launch (0 = one launch per block, the behaviour before).
-WGRAD_WINDOW = int(os.environ.get("AP_WGRAD_WINDOW", "256"))
-# The window holds UNITS -- one weight-gradient problem or one LayerNorm rider each, with the parameters whose gradient that unit
-# completes -- and launches the longest prefix that fits the tile kernel's table (WGRAD_WINDOW tiles = one per CU): a launch ends in
-# the middle of a block when that fills it.  VOLO-D5's blocks are 64 + 64 + 16 + 48 = 192 tiles: a block per launch left a quarter of
-# the chip idle, block-and-a-third launches fill it (three launches of 256 for four blocks); D1's 40-tile blocks pack 252 instead of 240.
-_window = {"units": [], "tiles": 0, "armed": None, "outs": set()}
-
-# Two private hooks of the autograd engine make the window self-flushing: queue_callback (run at the end of the backward pass the
-# caller is inside) and _current_graph_task_id (which backward pass that is).  Both are probed once; without them the window still
-# works and is flushed by GradientBucketReducer.finish() -- the sink's contract is "call finish() after backward()" either way.
-_ENGINE = getattr(getattr(torch.autograd, "Variable", None), "_execution_engine", None)
-_graph_task_id = getattr(torch._C, "_current_graph_task_id", None)
-_HAS_ENGINE_CALLBACK = hasattr(_ENGINE, "queue_callback") and _graph_task_id is not None     # (a callback is queued once per pass: both or neither)
-
-
-def _tiles_192(prob):
-    a, c, n1, n2 = prob[0], prob[2], prob[3], prob[4]
-    n1 = c.shape[0] if n1 is None else n1
-    n2 = c.shape[1] if n2 is None else n2
-    if n1 % 192 or n2 % 192 or a.shape[0] % 64 or a.shape[0] < 4096 or (len(prob) > 9 and prob[9] is not None):
-        return 0                      # not a problem of the 192 x 192-tile kernel: rides along, costs no slot
-    return (n1 // 192) * (n2 // 192)
-
-
-def _window_units(problems, ln, params):
-    """the block's problems and LayerNorm riders as units [kind, item, tiles, parameters completed, addresses written]"""
-    owner = {}
-    for p in params:
-        if p is not None and p.grad is not None:
-            owner.setdefault(p.grad.data_ptr(), []).append(p)
-    units, claimed = [], set()
-
-    def take(ptrs):
-        ps = []
-        for a in ptrs:
-            for p in owner.get(a, ()):
-                if id(p) not in claimed:
-                    claimed.add(id(p))
-                    ps.append(p)
-        return ps
-    for q in problems:
-        ptrs = [q[2].data_ptr()] + ([q[5].data_ptr()] if q[5] is not None else [])
-        units.append(["p", q, _tiles_192(q), take(ptrs), set(ptrs)])
-    for item in ln:
-        ptrs = [item[3].data_ptr(), item[4].data_ptr()]
-        units.append(["l", item, 0, take(ptrs), set(ptrs)])
-    if units:                         # a parameter no unit writes (there is none in the shipped blocks) leaves with the block's last unit
-        units[-1][3] += [p for p in params if p is not None and id(p) not in claimed]
-    return units
-
-
-def _window_add(problems, ln, params):
-    """-> True when the window took the block's weight gradients"""
-    from ._lib import TN_MAX_GROUP, LN_MAX_BATCH
-    if WGRAD_WINDOW <= 0 or async_wgrad or not fuse_ln_reduce or ops.deterministic:
-        return False
-    if len(problems) > TN_MAX_GROUP or len(ln) > LN_MAX_BATCH:
-        return False
-    w = _window
-    gid = _graph_task_id() if _graph_task_id is not None else 0
-    if w["armed"] != gid:
-        # first block of THIS backward pass.  Whatever the window still holds belongs to a pass that raised (the engine runs no
-        # callbacks then): those gradients are void, and the operands they pin are released here.
-        if w["armed"] is not None:
-            reset_wgrad_window()
-        if _HAS_ENGINE_CALLBACK:
-            if gid == -1:
-                return False          # a block backward called outside an engine pass: nothing would flush the window -- the block launches its own
-            try:                      # inside a backward pass: the engine calls back when it is over
-                _ENGINE.queue_callback(flush_wgrad_window)
-            except RuntimeError:
-                return False
-        w["armed"] = gid
-    units = _window_units(problems, ln, params)
-    outs = set()
-    for u in units:
-        outs |= u[4]
-    # a parameter that is ALREADY in the window (a block applied twice before one backward, shared weights): its LayerNorm riders
-    # add with plain read-modify-writes and tn8_plan only sees duplicates inside one call -- launch what is held first, so the
-    # two uses are ordered by the stream like the one-launch-per-block path orders them.
-    if w["units"] and (outs & w["outs"]):
-        _window_launch()
-    if hasattr(_grad_sink, "hold"):
-        _grad_sink.hold(params)       # (autograd fires their post-accumulate hooks when the block's backward returns)
-    w["units"] += units
-    w["tiles"] += sum(u[2] for u in units)
-    w["outs"] |= outs
-    while w["tiles"] >= WGRAD_WINDOW or _window_counts_full(TN_MAX_GROUP, LN_MAX_BATCH):
-        _window_launch_prefix()       # a full table's worth is there: it leaves, the rest of the block waits for the next one
-    # data parallel: when everything a gradient bucket still waits for sits in this window, launching now lets the bucket's
-    # all-reduce start under the rest of the backward pass (only once the launch is at least 60 % of a full window: a short
-    # launch cuts its problems along the token axis again)
-    if (w["tiles"] * 10 >= WGRAD_WINDOW * 6 and hasattr(_grad_sink, "completes_a_bucket") and _grad_sink.needs_stream_join()
-            and _grad_sink.completes_a_bucket([p for u in w["units"] for p in u[3]])):
-        _window_launch()
-    return True
-
-
-def _window_counts_full(max_problems, max_ln):
-    """more problems / riders held than ONE launch takes: a prefix has to go whatever its tile count"""
-    u = _window["units"]
-    return sum(1 for x in u if x[0] == "p") > max_problems or sum(1 for x in u if x[0] == "l") > max_ln
-
-
-def _window_launch_prefix():
-    """launch the longest prefix of the held units that one launch of the tile kernel takes: at most WGRAD_WINDOW tiles (at least one
-    unit), TN_MAX_GROUP problems, LN_MAX_BATCH riders; the parameters those units complete are handed to the gradient sink"""
-    from ._lib import TN_MAX_GROUP, LN_MAX_BATCH
-    w = _window
-    units = w["units"]
-    n = tiles = nprob = nln = 0
-    while n < len(units):
-        kind, _item, t = units[n][0], units[n][1], units[n][2]
-        if n and (tiles + t > WGRAD_WINDOW or (kind == "p" and nprob == TN_MAX_GROUP) or (kind == "l" and nln == LN_MAX_BATCH)):
-            break
-        tiles += t
-        nprob += kind == "p"
-        nln += kind == "l"
-        n += 1
-    taken, w["units"] = units[:n], units[n:]
-    w["tiles"] -= tiles
-    w["outs"] = set()
-    for u in w["units"]:
-        w["outs"] |= u[4]
-    problems = [u[1] for u in taken if u[0] == "p"]
-    ln = [u[1] for u in taken if u[0] == "l"]
-    if problems:
-        ops.gemm_tn_acc_grouped(problems, ln=ln)
-    elif ln:
-        ops.layernorm_bwd_reduce_batched(ln)
-    if _grad_sink is not None:
-        for u in taken:
-            for p in u[3]:
-                _grad_sink.param_ready(p)
-
-
-def _window_launch():
-    """everything the window holds, in as many launches as it takes"""
-    while _window["units"]:
-        _window_launch_prefix()
-
-
-def flush_wgrad_window():
-    """launch what the window holds (the end of every backward pass does; harmless when it is empty)"""
-    _window["armed"] = None
-    _window_launch()
-
-
-def reset_wgrad_window():
-    """drop what a backward pass that raised left behind"""
-    _window.update(units=[], tiles=0, armed=None, outs=set())
-
-
-fuse_ln_reduce = os.environ.get("AP_FUSE_LN_REDUCE", "1") != "0"
-
-
-def _launch_wgrads(problems, ln=None):
-    if async_wgrad:
-        side = wgrad_stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            ops.gemm_tn_acc_grouped(problems)
-        for prob in problems:
-            prob[0].record_stream(side)
-            prob[1].record_stream(side)
-    else:
-        ops.gemm_tn_acc_grouped(problems, ln=ln)
 
 
 # The MLPs store gelu'(h) instead of h in the forward (the backward needs nothing else of h) and multiply by it in the backward:
@@ -415,14 +130,11 @@ def _linear_bwd(g, x_in, w, dw, db, n=None, dgelu_of=None, need_dx=True, row_sca
             raise AutoProgHipError("fp8 weight gradient: dL/dy must be exactly out_features wide")
         g8w, dq_g = fp8_scales.quantize_bf8(("gw", id(w)), g, colsum=db, colsum_weight=cs_weight, colsum_scale=inv_keep)
         prob = ops.Tn8Problem(g8w, x8[0], _g2(dw), n, _g2(dw).shape[1], dq_g, x8[1], alpha=inv_keep if cs_weight is not None else 1.0)
+    elif cs_weight is not None:
+        prob = ops.WgradProblem(g, x_in, _g2(dw), n, _g2(dw).shape[1], db, colsum_weight=cs_weight, colsum_scale=inv_keep, alpha=inv_keep)
     else:
-        prob = (g, x_in, _g2(dw), n, _g2(dw).shape[1], db)
-        if cs_weight is not None:
-            prob = prob + (cs_weight, inv_keep, inv_keep)
-    if _wgrad_batch is not None:
-        _wgrad_batch.append(prob)
-    else:
-        _launch_wgrads([prob])
+        prob = ops.WgradProblem(g, x_in, _g2(dw), n, _g2(dw).shape[1], db)
+    wgrad.enqueue(prob)
     if not need_dx:
         return None
     wt = bank.get_t(w)                       # [K, ld(N)]
@@ -748,10 +460,10 @@ class TransformerBlockFn(torch.autograd.Function):
         B, N, heads, scale, inv_keep = ctx.cfg
         w8 = [(b, d) if b is not None else None for b, d in zip(b8, ctx.w8dq)]
         params = (n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b)
-        bufs, sunk = _param_grad_buffers(params)
+        bufs, sunk = wgrad._param_grad_buffers(params)
         (dn1w, dn1b, dqkv_w, dqkv_b, dproj_w, dproj_b, dn2w, dn2b, dfc1_w, dfc1_b, dfc2_w, dfc2_b) = bufs
         dy2 = dy.reshape(x2.shape).contiguous()
-        with wgrad_batch(sunk, params) as batch:         # the four weight gradients (and the two LayerNorm parameter gradients) launch together: on exit, or with the window's
+        with wgrad.wgrad_batch(sunk, params) as batch:         # the four weight gradients (and the two LayerNorm parameter gradients) launch together: on exit, or with the window's
             # MLP branch
             dh8 = None
             dxn2 = None
@@ -788,7 +500,7 @@ class TransformerBlockFn(torch.autograd.Function):
             dqkv = ops.mhsa_bwd(qkv, o, do, lse, B, N, heads, scale)      # dropped samples: do = 0, so the masked rows of o do not matter
             dxn1 = _linear_bwd(dqkv, xn1, qkv_w, dqkv_w, dqkv_b, x8=w8[0])
             dx = ops.layernorm_bwd(dxn1, x2, n1w, m1, r1, dx1, dn1w, dn1b, defer=batch.ln)
-        return (dx.view(dy.shape), None, None, *_finish_param_grads(params, bufs, sunk, batch.deferred), None, None, None, None, None, None, None, None, None)
+        return (dx.view(dy.shape), None, None, *wgrad._finish_param_grads(params, bufs, sunk, batch.deferred), None, None, None, None, None, None, None, None, None)
 
 
 def infer_mode():
@@ -891,11 +603,11 @@ class ClassBlockFn(torch.autograd.Function):
          n1w, n1b, kv_w, kv_b, q_w, q_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b) = ctx.saved_tensors
         B, N, heads, scale = ctx.cfg
         params = (n1w, n1b, kv_w, kv_b, q_w, q_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b)
-        bufs, sunk = _param_grad_buffers(params)
+        bufs, sunk = wgrad._param_grad_buffers(params)
         (dn1w, dn1b, dkv_w, dkv_b, dq_w, dq_b, dproj_w, dproj_b, dn2w, dn2b, dfc1_w, dfc1_b, dfc2_w, dfc2_b) = bufs
         g = dc2.contiguous() if dc2 is not None else torch.zeros(c0.shape, dtype=BF16, device=c0.device)
         dpass = dtok_pass.reshape(t0.shape).contiguous() if dtok_pass is not None else None
-        with wgrad_batch() as batch:          # (not in the weight-gradient window: 12 small problems for one 8-tile one)
+        with wgrad.wgrad_batch() as batch:          # (not in the weight-gradient window: 12 small problems for one 8-tile one)
             dh = _linear_bwd(g, a, fc2_w, dfc2_w, dfc2_b, **_gelu_bwd_kw(h))
             dn2 = _linear_bwd(dh, n2, fc1_w, dfc1_w, dfc1_b)
             dc1 = ops.layernorm_bwd(dn2, c1, n2w, m2, r2, g, dn2w, dn2b, defer=batch.ln)
@@ -908,7 +620,7 @@ class ClassBlockFn(torch.autograd.Function):
             dnc = ops.gemm_nt(dq, wq_t, n=wq_t.shape[0], k=wq_t.shape[1], residual=dnc_kv)      # dq Wq + dkv_c Wkv in one epilogue
             dcls = ops.layernorm_bwd(dnc, c0, n1w, mc, rc, dc1, dn1w, dn1b)       # reduced at once: it shares dn1w / dn1b with the deferred
             dtok = ops.layernorm_bwd(dnt, t0, n1w, mt, rt, dpass, dn1w, dn1b, defer=batch.ln)     # token piece (two deferred sums into one vector would race)
-        return (dcls.view(ctx.shapes[0]), dtok.view(ctx.shapes[1]), *_finish_param_grads(params, bufs, sunk, batch.deferred), None, None, None, None)
+        return (dcls.view(ctx.shapes[0]), dtok.view(ctx.shapes[1]), *wgrad._finish_param_grads(params, bufs, sunk, batch.deferred), None, None, None, None)
 
 
 def _class_block_infer(cls, tok, n1w, n1b, kv_w, kv_b, q_w, q_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, B, N, heads, eps):
@@ -981,10 +693,10 @@ class OutlookerBlockFn(torch.autograd.Function):
         B, H, W, C, heads, scale = ctx.cfg
         T = B * H * W
         params = (n1w, n1b, v_w, v_b, attn_w, attn_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b)
-        bufs, sunk = _param_grad_buffers(params)
+        bufs, sunk = wgrad._param_grad_buffers(params)
         (dn1w, dn1b, dv_w, dv_b, dattn_w, dattn_b, dproj_w, dproj_b, dn2w, dn2b, dfc1_w, dfc1_b, dfc2_w, dfc2_b) = bufs
         dy2 = dy.reshape(T, C).contiguous()
-        with wgrad_batch(sunk, params) as batch:         # the five weight gradients launch together: on exit, or with the window's
+        with wgrad.wgrad_batch(sunk, params) as batch:         # the five weight gradients launch together: on exit, or with the window's
             dh = _linear_bwd(dy2, a, fc2_w, dfc2_w, dfc2_b, **_gelu_bwd_kw(h))
             dxn2 = _linear_bwd(dh, xn2, fc1_w, dfc1_w, dfc1_b)
             dx1 = ops.layernorm_bwd(dxn2, x1, n2w, m2, r2, dy2, dn2w, dn2b, defer=batch.ln)
@@ -997,7 +709,7 @@ class OutlookerBlockFn(torch.autograd.Function):
             if dx is None:
                 ops.avgpool2_bwd_acc(dpooled.view(B, (H + 1) // 2, (W + 1) // 2, C), dxn1.view(B, H, W, C))
                 dx = ops.layernorm_bwd(dxn1, x2, n1w, m1, r1, dx1, dn1w, dn1b, defer=batch.ln)
-        return (dx.view(dy.shape), *_finish_param_grads(params, bufs, sunk, batch.deferred), None, None)
+        return (dx.view(dy.shape), *wgrad._finish_param_grads(params, bufs, sunk, batch.deferred), None, None)
 
 
 def _outlooker_block_infer(x, n1w, n1b, v_w, v_b, attn_w, attn_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, heads, eps):
@@ -1042,9 +754,9 @@ class LayerNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         xc, w, b, m, r = ctx.saved_tensors
-        bufs, sunk = _param_grad_buffers((w, b))      # with a gradient sink: accumulate straight into param.grad
+        bufs, sunk = wgrad._param_grad_buffers((w, b))      # with a gradient sink: accumulate straight into param.grad
         dx = ops.layernorm_bwd(dy.contiguous(), xc, w, m, r, None, bufs[0], bufs[1])
-        dw, db = _finish_param_grads((w, b), bufs, sunk)
+        dw, db = wgrad._finish_param_grads((w, b), bufs, sunk)
         return dx, dw, db, None
 
 
@@ -1081,9 +793,9 @@ class LinearFn(torch.autograd.Function):
             else:
                 hf = h.float()
                 g = (g.float() * (0.5 * (1.0 + torch.erf(hf * 0.7071067811865476)) + hf * torch.exp(-0.5 * hf * hf) * 0.3989422804014327)).to(BF16)
-        bufs, sunk = _param_grad_buffers((w, b))      # with a gradient sink (and w, b real parameters): param.grad itself
+        bufs, sunk = wgrad._param_grad_buffers((w, b))      # with a gradient sink (and w, b real parameters): param.grad itself
         dx = _linear_bwd(g, x2, w, bufs[0], bufs[1], n=N, need_dx=ctx.needs_input_grad[0])
-        dw, db = _finish_param_grads((w, b), bufs, sunk)
+        dw, db = wgrad._finish_param_grads((w, b), bufs, sunk)
         if dx is not None:
             dx = dx[:, :x2.shape[1]] if dx.shape[1] != x2.shape[1] else dx
             dx = dx.reshape(*ctx.lead, x2.shape[1])
@@ -1124,9 +836,9 @@ class ClsExpandFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (cls_token,) = ctx.saved_tensors
-        bufs, sunk = _param_grad_buffers((cls_token,))
+        bufs, sunk = wgrad._param_grad_buffers((cls_token,))
         ops.colsum_acc(g.contiguous(), bufs[0].view(-1))
-        (dc,) = _finish_param_grads((cls_token,), bufs, sunk)
+        (dc,) = wgrad._finish_param_grads((cls_token,), bufs, sunk)
         return dc, None
 
 
@@ -1215,9 +927,9 @@ class PosEmbedInterpFn(torch.autograd.Function):
     def backward(ctx, g):
         pos, wyt, wxt = ctx.saved_tensors
         _, h0, w0, C = g.shape
-        bufs, sunk = _param_grad_buffers((pos,))
+        bufs, sunk = wgrad._param_grad_buffers((pos,))
         ops.resample_grid(g.reshape(h0, w0, C).contiguous().float(), wyt, wxt, out=bufs[0].view(pos.shape[1], pos.shape[2], C), accumulate=True)
-        (dp,) = _finish_param_grads((pos,), bufs, sunk)
+        (dp,) = wgrad._finish_param_grads((pos,), bufs, sunk)
         return dp, None, None
 
 
@@ -1453,9 +1165,9 @@ class BNReLUFn(torch.autograd.Function):
         xc, weight, bias, mean, rstd = ctx.saved_tensors
         if not ctx.training:
             raise AutoProgHipError("BNReLUFn backward is implemented for training mode (batch statistics) only")
-        bufs, sunk = _param_grad_buffers((weight, bias))      # with a gradient sink: accumulate straight into param.grad
+        bufs, sunk = wgrad._param_grad_buffers((weight, bias))      # with a gradient sink: accumulate straight into param.grad
         dx = ops.bn_relu_bwd(dy.contiguous(), xc, weight, bias, mean, rstd, bufs[0], bufs[1])
-        dg, db = _finish_param_grads((weight, bias), bufs, sunk)
+        dg, db = wgrad._finish_param_grads((weight, bias), bufs, sunk)
         return dx, dg, db, None, None, None, None, None
 
 
@@ -1499,7 +1211,7 @@ class PatchConvFn(torch.autograd.Function):
             g = gp
         g = g.contiguous()
         params = (weight, bias) if bn is None else (weight, bias, bn_gamma, bn_beta)
-        bufs, sunk = _param_grad_buffers(params)
+        bufs, sunk = wgrad._param_grad_buffers(params)
         dx = None
         b_rows, b_bn = xc, bn             # the weight gradient's B rows: the map the forward read (+ its transform)
         if ctx.needs_input_grad[0]:
@@ -1517,10 +1229,10 @@ class PatchConvFn(torch.autograd.Function):
         elif bn is not None:
             raise AutoProgHipError("PatchConvFn with a BatchNorm input: the BatchNorm's parameter gradients need the input gradient")
         dwmat = torch.zeros((N, K), dtype=torch.float32, device=g.device)
-        _launch_wgrads([(g, b_rows, dwmat, N, K, bufs[1], None, 1.0, 1.0, ops.patch_map(H, W, C, k), b_bn)])
-        join_wgrad_stream()
+        wgrad.enqueue(ops.WgradProblem(g, b_rows, dwmat, N, K, bufs[1], b_patch=ops.patch_map(H, W, C, k), b_bn=b_bn))
+        wgrad.join_wgrad_stream()
         bufs[0].add_(dwmat.view(N, k, k, C).permute(0, 3, 1, 2))                              # back to OIHW
-        gr = _finish_param_grads(params, bufs, sunk)
+        gr = wgrad._finish_param_grads(params, bufs, sunk)
         return (dx, gr[0], gr[1], None, None, None) + ((gr[2], gr[3]) if bn is not None else (None, None))
 
 
@@ -1553,10 +1265,10 @@ class Conv7BNReLUFn(torch.autograd.Function):
         if not ctx.training:
             raise AutoProgHipError("Conv7BNReLUFn backward is implemented for training mode (batch statistics) only")
         params = (conv_w, weight, bias)
-        bufs, sunk = _param_grad_buffers(params)
+        bufs, sunk = wgrad._param_grad_buffers(params)
         dz = ops.bn_relu_bwd(dy.contiguous(), z, weight, bias, mean, rstd, bufs[1], bufs[2])
         ops.conv7_s2d_wgrad(xs, dz, bufs[0])
-        dw, dg, db = _finish_param_grads(params, bufs, sunk)
+        dw, dg, db = wgrad._finish_param_grads(params, bufs, sunk)
         return None, dw, dg, db, None, None, None, None, None
 
 
@@ -1585,11 +1297,11 @@ class Conv3x3BNReLUFn(torch.autograd.Function):
         if not ctx.training:
             raise AutoProgHipError("Conv3x3BNReLUFn backward is implemented for training mode (batch statistics) only")
         params = (conv_w, weight, bias)
-        bufs, sunk = _param_grad_buffers(params)
+        bufs, sunk = wgrad._param_grad_buffers(params)
         dz = ops.bn_relu_bwd(dy.contiguous(), z, weight, bias, mean, rstd, bufs[1], bufs[2])
         dx = ops.conv3x3_c64(dz, wb) if ctx.needs_input_grad[0] else None
         ops.conv3x3_c64_wgrad(xc, dz, bufs[0])
-        dw, dg, db = _finish_param_grads(params, bufs, sunk)
+        dw, dg, db = wgrad._finish_param_grads(params, bufs, sunk)
         return dx, dw, dg, db, None, None, None, None, None
 
 
@@ -1640,7 +1352,7 @@ class Stem64Fn(torch.autograd.Function):
             raise AutoProgHipError("Stem64Fn backward is implemented for training mode (batch statistics) only")
         last = ctx.apply_last
         params = (w7, g1, b1, w2, g2, b2, w3, g3, b3) if last else (w7, g1, b1, w2, g2, b2, w3)
-        bufs, sunk = _param_grad_buffers(params)
+        bufs, sunk = wgrad._param_grad_buffers(params)
         if last:
             dw7, dg1, db1, dw2, dg2, db2, dw3, dg3, db3 = bufs
             dz3 = ops.bn_relu_bwd(dy.contiguous(), z3, g3, b3, mean3, rstd3, dg3, db3)
@@ -1662,7 +1374,7 @@ class Stem64Fn(torch.autograd.Function):
             ops.conv3x3_c64_wgrad(z1, dz2, dw2, bn_in=(mean1, rstd1, g1, b1))
             dz1 = ops.bn_relu_bwd(da1, z1, g1, b1, mean1, rstd1, dg1, db1)
         ops.conv7_s2d_wgrad(xs, dz1, dw7)
-        gr = list(_finish_param_grads(params, bufs, sunk))
+        gr = list(wgrad._finish_param_grads(params, bufs, sunk))
         if not last:
             gr += [None, None]
         return (None, gr[0], gr[1], gr[2], None, None, gr[3], gr[4], gr[5], None, None, gr[6], gr[7], gr[8], None, None, None, None, None, None)

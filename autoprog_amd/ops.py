@@ -7,10 +7,12 @@ There is no fallback path: a CPU tensor or a missing library raises.
 import ctypes
 import math
 import os
+from collections import namedtuple
 
 import torch
 
-from ._lib import GemmEpilogue, InputPrepArgs, PREP_MAX_BOXES, AutoProgHipError, check, lib
+from . import _lib
+from ._lib import GemmEpilogue, InputPrepArgs, LnReduce, TnProblem, LN_MAX_BATCH, PREP_MAX_BOXES, TN_MAX_GROUP, TN_MAX_GROUP_DET, AutoProgHipError, check, lib
 
 BF16 = torch.bfloat16
 
@@ -142,6 +144,11 @@ def layernorm_fwd(x, gamma, beta, eps, fp8=None):
 _ln_ws = {}          # (rows, C) -> ap_layernorm_bwd_workspace bytes (a pure function of the shape: one foreign call per shape, not per launch)
 
 
+# a deferred LayerNorm dgamma / dbeta reduction (what layernorm_bwd(..., defer=...) appends): `n_partial` partial rows of width C in the fp32
+# workspace `partial`, summed into dgamma / dbeta by layernorm_bwd_reduce_batched or by the weight-gradient launch it rides in
+LnRider = namedtuple("LnRider", "partial n_partial C dgamma dbeta")
+
+
 def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, defer=None, pool=None):
     """dx = dres + dLN/dx ; dgamma/dbeta (fp32) are accumulated in place.  defer: a list -- the dgamma/dbeta reduction is not
     launched but appended to it (layernorm_bwd_reduce_batched reduces the LayerNorms of a block in one launch).
@@ -166,14 +173,14 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, defer=None, poo
         if rc == -2:                   # AP_ERR_UNSUPPORTED
             return None
         check(rc, "ap_layernorm_bwd_partial_pool")
-        defer.append((ws, n.value, C, dgamma, dbeta))
+        defer.append(LnRider(ws, n.value, C, dgamma, dbeta))
         return dx
     if defer is not None and rows > 0:
         n = ctypes.c_int(0)
         check(lib.ap_layernorm_bwd_partial(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                                            dres.data_ptr() if dres is not None else None, dx.data_ptr(), rows, C, ws.data_ptr(), ws_bytes,
                                            ctypes.byref(n), _stream()), "ap_layernorm_bwd_partial")
-        defer.append((ws, n.value, C, dgamma, dbeta))
+        defer.append(LnRider(ws, n.value, C, dgamma, dbeta))
         return dx
     check(lib.ap_layernorm_bwd(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                                dres.data_ptr() if dres is not None else None, dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
@@ -181,15 +188,19 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, defer=None, poo
     return dx
 
 
+def _ln_reduce_array(items):
+    """the ap_ln_reduce table of a launch that carries these deferred reductions"""
+    arr = (LnReduce * len(items))()
+    for q, (ws, n, C, dg, db) in zip(arr, items):
+        q.partial, q.n_partial, q.C, q.dgamma, q.dbeta = ws.data_ptr(), n, C, dg.data_ptr(), db.data_ptr()
+    return arr
+
+
 def layernorm_bwd_reduce_batched(items):
     """items: the entries layernorm_bwd(..., defer=items) appended; one launch per LN_MAX_BATCH LayerNorms"""
-    from ._lib import LnReduce, LN_MAX_BATCH
     for i0 in range(0, len(items), LN_MAX_BATCH):
         chunk = items[i0:i0 + LN_MAX_BATCH]
-        arr = (LnReduce * len(chunk))()
-        for q, (ws, n, C, dg, db) in zip(arr, chunk):
-            q.partial, q.n_partial, q.C, q.dgamma, q.dbeta = ws.data_ptr(), n, C, dg.data_ptr(), db.data_ptr()
-        check(lib.ap_layernorm_bwd_reduce_batched(ctypes.cast(arr, ctypes.c_void_p), len(chunk), _stream()), "ap_layernorm_bwd_reduce_batched")
+        check(lib.ap_layernorm_bwd_reduce_batched(ctypes.cast(_ln_reduce_array(chunk), ctypes.c_void_p), len(chunk), _stream()), "ap_layernorm_bwd_reduce_batched")
 
 
 # ------------------------------------------------------------------------------------- gemm
@@ -433,46 +444,52 @@ def gemm_tn8_ok(n1, n2):
     return n1 % 128 == 0 and n2 % 128 == 0 and n1 > 0 and n2 > 0
 
 
-class Tn8Problem(tuple):
-    """an fp8 weight-gradient problem for gemm_tn8_acc_grouped / gemm_tn_acc_grouped: (a8, b8, c, n1, n2, None, dq_a, dq_b, alpha):
-    c[:n1, :n2] += alpha * dq_a[0] * dq_b[0] * a8^T b8 with a8 [M, n1] e5m2 bytes (a_fmt = FP8_E5M2; e4m3 with FP8_E4M3) and b8
-    [M, n2] e4m3 bytes; dq_* fp32 device scalars.  Slot 5 (a column sum) is always None: quantize_bf8 forms the bias gradient."""
-    a_fmt = 1
+def _tiles_192(prob):
+    """tiles a weight-gradient problem takes in the table of the 192 x 192-tile kernel (restates tn8_fits() in csrc/gemm.hip)"""
+    n1 = prob.c.shape[0] if prob.n1 is None else prob.n1
+    n2 = prob.c.shape[1] if prob.n2 is None else prob.n2
+    if n1 % 192 or n2 % 192 or prob.a.shape[0] % 64 or prob.a.shape[0] < 4096 or prob.b_patch is not None:
+        return 0                      # not a problem of the 192 x 192-tile kernel: rides along, costs no slot
+    return (n1 // 192) * (n2 // 192)
 
-    def __new__(cls, a8, b8, c, n1, n2, dq_a, dq_b, alpha=1.0, a_fmt=1):
-        self = super().__new__(cls, (a8, b8, c, n1, n2, None, dq_a, dq_b, alpha))
-        self.a_fmt = a_fmt
-        return self
+
+class WgradProblem(namedtuple("WgradProblem", "a b c n1 n2 colsum colsum_weight colsum_scale alpha b_patch b_bn", defaults=(None, 1.0, 1.0, None, None))):
+    """a bf16 weight-gradient problem: the fields as gemm_tn_acc_grouped describes them"""
+    __slots__ = ()
+    tiles_192 = _tiles_192
+
+
+class Tn8Problem(namedtuple("Tn8Problem", "a b c n1 n2 dq_a dq_b alpha a_fmt", defaults=(1.0, 1))):
+    """an fp8 weight-gradient problem for gemm_tn8_acc_grouped / gemm_tn_acc_grouped:
+    c[:n1, :n2] += alpha * dq_a[0] * dq_b[0] * a^T b with a [M, n1] e5m2 bytes (a_fmt = FP8_E5M2; e4m3 with FP8_E4M3) and b
+    [M, n2] e4m3 bytes; dq_* fp32 device scalars.  No column sum (quantize_bf8 forms the bias gradient), no patch addressing."""
+    __slots__ = ()
+    colsum = b_patch = None
+    tiles_192 = _tiles_192
 
 
 def gemm_tn8_acc_grouped(problems, ln=None):
     """ONE launch of the fp8 weight-gradient kernel for a list of Tn8Problem (at most TN_MAX_GROUP); ln: deferred LayerNorm reductions
     riding in the launch (at most LN_MAX_BATCH).  Deterministic mode as for gemm_tn_acc_grouped."""
-    from ._lib import Tn8Problem as _Tn8, TN_MAX_GROUP, LnReduce, LN_MAX_BATCH
     ln = list(ln) if ln else []
     if len(problems) > TN_MAX_GROUP or len(ln) > LN_MAX_BATCH:
         raise AutoProgHipError("gemm_tn8_acc_grouped: at most %d problems and %d LayerNorm reductions" % (TN_MAX_GROUP, LN_MAX_BATCH))
-    arr = (_Tn8 * len(problems))()
+    arr = (_lib.Tn8Problem * len(problems))()
     for q, prob in zip(arr, problems):
-        a8, b8, c, n1, n2, _, dq_a, dq_b, alpha = prob
+        a8, b8, c, n1, n2, dq_a, dq_b = prob.a, prob.b, prob.c, prob.n1, prob.n2, prob.dq_a, prob.dq_b
         _req(a8, torch.uint8, "a8"); _req(b8, torch.uint8, "b8"); _req(c, torch.float32, "c")
         _req(dq_a, torch.float32, "dq_a"); _req(dq_b, torch.float32, "dq_b")
         if a8.shape[0] != b8.shape[0]:
             raise ValueError("gemm_tn8_acc_grouped: token counts differ")
         q.A, q.lda, q.B, q.ldb, q.C, q.ldc = a8.data_ptr(), a8.shape[1], b8.data_ptr(), b8.shape[1], c.data_ptr(), c.shape[1]
         q.M, q.N1, q.N2 = a8.shape[0], (c.shape[0] if n1 is None else n1), (c.shape[1] if n2 is None else n2)
-        q.a_fmt, q.alpha, q.dq_a, q.dq_b = int(getattr(prob, "a_fmt", 1)), float(alpha), dq_a.data_ptr(), dq_b.data_ptr()
+        q.a_fmt, q.alpha, q.dq_a, q.dq_b = int(prob.a_fmt), float(prob.alpha), dq_a.data_ptr(), dq_b.data_ptr()
     ptr = ctypes.cast(arr, ctypes.c_void_p)
     ws, ws_bytes = None, 0
     if deterministic:
         ws_bytes = lib.ap_gemm_tn8_grouped_workspace(ptr, len(problems))
-        ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=problems[0][0].device)
-    larr = None
-    if ln:
-        larr = (LnReduce * len(ln))()
-        for q, (lws, n, C, dg, db) in zip(larr, ln):
-            q.partial, q.n_partial, q.C, q.dgamma, q.dbeta = lws.data_ptr(), n, C, dg.data_ptr(), db.data_ptr()
-    check(lib.ap_gemm_tn8_acc_grouped_ln(ptr, len(problems), ctypes.cast(larr, ctypes.c_void_p) if larr is not None else None, len(ln),
+        ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=problems[0].a.device)
+    check(lib.ap_gemm_tn8_acc_grouped_ln(ptr, len(problems), ctypes.cast(_ln_reduce_array(ln), ctypes.c_void_p) if ln else None, len(ln),
                                          ws.data_ptr() if ws is not None else None, ws_bytes, _stream()), "ap_gemm_tn8_acc_grouped_ln")
 
 
@@ -580,12 +597,11 @@ def gemm_nt_patch_dgrad(dy, wmat_t, shape, k):
 
 
 def gemm_tn_acc_grouped(problems, ln=None):
-    """problems: list of (a, b, c, n1, n2, colsum[, colsum_weight, colsum_scale[, alpha[, b_patch[, b_bn]]]]) as for gemm_tn_acc (b_bn: the
+    """problems: list of WgradProblem -- or bare (a, b, c, n1, n2, colsum[, colsum_weight, colsum_scale[, alpha[, b_patch[, b_bn]]]]) -- as for gemm_tn_acc (b_bn: the
     (mean, rstd, gamma, beta) of a BatchNorm whose relu(bn(.)) is applied to the patch-addressed b while it is staged); ONE launch for
     the whole list (chunks of 8).  colsum_weight: bf16 per-token weights of the column sum (DropPath keep mask), colsum_scale its factor;
     alpha: factor of the product (c += alpha * a^T b); b_patch: PatchMap -- b is then an NHWC feature map whose patches are the rows.
     ln: deferred LayerNorm reductions (the entries layernorm_bwd(..., defer=...) appended): LN_MAX_BATCH of them ride in the first launch."""
-    from ._lib import TnProblem, TN_MAX_GROUP, TN_MAX_GROUP_DET, LnReduce, LN_MAX_BATCH
     ln = list(ln) if ln else []
     fp8 = [p for p in problems if isinstance(p, Tn8Problem)]
     if fp8:                           # the fp8 problems (functional.FP8_WGRAD) in launches of their own; the riders go with the first
@@ -603,30 +619,25 @@ def gemm_tn_acc_grouped(problems, ln=None):
         ln = ln[:LN_MAX_BATCH]
     per = TN_MAX_GROUP_DET if deterministic else TN_MAX_GROUP
     for i0 in range(0, len(problems), per):
-        chunk = problems[i0:i0 + per]
+        chunk = [p if type(p) is WgradProblem else WgradProblem(*p) for p in problems[i0:i0 + per]]
         arr = (TnProblem * len(chunk))()
         keep = []
         for q, prob in zip(arr, chunk):
-            a, b, c, n1, n2, colsum = prob[:6]
-            csw, css = (prob[6], prob[7]) if len(prob) > 6 else (None, 1.0)
-            q.alpha = float(prob[8]) if len(prob) > 8 else 1.0
-            bp = prob[9] if len(prob) > 9 else None
+            a, b, c, n1, n2, colsum = prob.a, prob.b, prob.c, prob.n1, prob.n2, prob.colsum
+            csw, css, bp = prob.colsum_weight, prob.colsum_scale, prob.b_patch
+            q.alpha = float(prob.alpha)
             _req(a, BF16, "a"); _req(b, BF16, "b"); _req(c, torch.float32, "c")
-            if bp is not None:
+            if bp is not None:            # b is a feature map read in place: no row stride, no token count to compare, a plain column sum
                 keep.append(bp)
                 q.b_patch = ctypes.addressof(bp)
-                if len(prob) > 10 and prob[10] is not None:
-                    bb = _bn_input(prob[10])
+                if prob.b_bn is not None:
+                    bb = _bn_input(prob.b_bn)
                     keep.append(bb)
                     q.b_bn = ctypes.addressof(bb)
-                q.A, q.lda, q.B, q.ldb, q.C, q.ldc = a.data_ptr(), a.shape[1], b.data_ptr(), 0, c.data_ptr(), c.shape[1]
-                q.M, q.N1, q.N2 = a.shape[0], (c.shape[0] if n1 is None else n1), (c.shape[1] if n2 is None else n2)
-                q.colsum_A = colsum.data_ptr() if colsum is not None else None
-                q.colsum_weight, q.colsum_scale = None, 1.0
-                continue
-            if a.shape[0] != b.shape[0]:
+                csw, css = None, 1.0
+            elif a.shape[0] != b.shape[0]:
                 raise ValueError("gemm_tn_acc_grouped: token counts differ")
-            q.A, q.lda, q.B, q.ldb, q.C, q.ldc = a.data_ptr(), a.shape[1], b.data_ptr(), b.shape[1], c.data_ptr(), c.shape[1]
+            q.A, q.lda, q.B, q.ldb, q.C, q.ldc = a.data_ptr(), a.shape[1], b.data_ptr(), (0 if bp is not None else b.shape[1]), c.data_ptr(), c.shape[1]
             q.M, q.N1, q.N2 = a.shape[0], (c.shape[0] if n1 is None else n1), (c.shape[1] if n2 is None else n2)
             q.colsum_A = colsum.data_ptr() if colsum is not None else None
             if csw is not None:
@@ -639,12 +650,9 @@ def gemm_tn_acc_grouped(problems, ln=None):
         ws, ws_bytes = None, 0
         if deterministic:
             ws_bytes = lib.ap_gemm_tn_grouped_workspace(ptr, len(chunk))
-            ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=chunk[0][0].device)
+            ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=chunk[0].a.device)
         if ln:
-            larr = (LnReduce * len(ln))()
-            for q, (lws, n, C, dg, db) in zip(larr, ln):
-                q.partial, q.n_partial, q.C, q.dgamma, q.dbeta = lws.data_ptr(), n, C, dg.data_ptr(), db.data_ptr()
-            check(lib.ap_gemm_tn_acc_grouped_ln(ptr, len(chunk), ctypes.cast(larr, ctypes.c_void_p), len(ln), ws.data_ptr() if ws is not None else None,
+            check(lib.ap_gemm_tn_acc_grouped_ln(ptr, len(chunk), ctypes.cast(_ln_reduce_array(ln), ctypes.c_void_p), len(ln), ws.data_ptr() if ws is not None else None,
                                                 ws_bytes, _stream()), "ap_gemm_tn_acc_grouped_ln")
             ln = []
         else:

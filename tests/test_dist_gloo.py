@@ -49,7 +49,7 @@ def _worker(rank, world, port, q):
                     acc += g / world
             for got, want in zip(results[-1], ref):
                 assert torch.allclose(got, want, atol=1e-6), (rank, step)
-        # gradient-sink protocol (functional.set_grad_sink): a fused backward writes param.grad in place, calls
+        # gradient-sink protocol (wgrad.set_grad_sink): a fused backward writes param.grad in place, calls
         # param_ready() and returns None to autograd -- whose AccumulateGrad hook may still fire for that
         # parameter; a bucket must not be counted ready twice (it would launch before its other members exist)
         red.remove()
@@ -89,7 +89,7 @@ def _worker(rank, world, port, q):
                 acc += g / world
         for got, want in zip([p.grad for p in net.parameters()], ref):
             assert torch.allclose(got, want, atol=1e-6), (rank, "sink")
-        # deferred delivery (functional's weight-gradient window): the fused backward only NOTES its weight gradient, tells the sink to
+        # deferred delivery (the weight-gradient window of wgrad.py): the fused backward only NOTES its weight gradient, tells the sink to
         # hold() the parameter -- autograd's post-accumulate hook fires when the backward returns, with nothing written yet -- and the
         # end of the backward pass writes all of them and calls param_ready().  No bucket may leave before that.
         pending = []
@@ -290,14 +290,14 @@ def test_gradient_accumulation_equals_one_large_batch_world_size_2():
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
-# the weight-gradient window of functional.py under data parallelism: the REAL window code (collect the blocks' problems, launch when
+# the weight-gradient window of wgrad.py under data parallelism: the REAL window code (collect the blocks' problems, launch when
 # a window is full or when it completes a gradient bucket, deliver through param_ready) over the REAL reducer; only the HIP launch
 # itself (ops.gemm_tn_acc_grouped) is replaced by the same arithmetic in torch, so that this runs without a GPU.
 def _window_worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        from autoprog_amd import functional as AF, ops
+        from autoprog_amd import ops, wgrad
         from autoprog_amd.dist import GradientBucketReducer
 
         launches = []                                   # (blocks whose backward had run, problems in the launch)
@@ -311,7 +311,7 @@ def _window_worker(rank, world, port, q):
                 if colsum is not None:
                     colsum += a[:, :n1].float().sum(0)
         ops.gemm_tn_acc_grouped = cpu_grouped
-        AF.WGRAD_WINDOW = 4                             # tiles per launch: every problem below is ONE 192 x 192 tile
+        wgrad.WGRAD_WINDOW = 4                          # tiles per launch: every problem below is ONE 192 x 192 tile
 
         T, C, NB = 4096, 192, 12
 
@@ -325,12 +325,12 @@ def _window_worker(rank, world, port, q):
             @staticmethod
             def backward(ctx, dy):
                 x, w = ctx.saved_tensors
-                bufs, sunk = AF._param_grad_buffers(ctx.params)
+                bufs, sunk = wgrad._param_grad_buffers(ctx.params)
                 assert sunk
-                with AF.wgrad_batch(sunk=True, params=ctx.params) as batch:
-                    AF._wgrad_batch.append((dy.contiguous(), x, bufs[0], C, C, bufs[1]))
+                with wgrad.wgrad_batch(sunk=True, params=ctx.params) as batch:
+                    batch.add(ops.WgradProblem(dy.contiguous(), x, bufs[0], C, C, bufs[1]))
                 assert batch.deferred
-                AF._finish_param_grads(ctx.params, bufs, sunk, deferred=True)
+                wgrad._finish_param_grads(ctx.params, bufs, sunk, deferred=True)
                 done_blocks[0] += 1
                 return (dy.float() @ w).to(torch.bfloat16), None, None
 
@@ -410,7 +410,7 @@ def _window_worker(rank, world, port, q):
             raise AssertionError("backward did not raise")
         except RuntimeError as e:
             assert "boom" in str(e)
-        assert AF._window["units"], "the failed pass should have left its problems in the window"
+        assert wgrad.window.units, "the failed pass should have left its problems in the window"
         log = run()
         for a, b in zip([p.grad for p in params], reference()):
             assert torch.allclose(a, b, rtol=2e-2, atol=2e-4), (rank, "after a failed pass")
@@ -436,7 +436,7 @@ def _ws8_worker(rank, world, port, q):
     torch.set_num_threads(1)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        from autoprog_amd import functional as AF, ops
+        from autoprog_amd import ops, wgrad
         from autoprog_amd.dist import GradientBucketReducer
 
         def cpu_grouped(problems, ln=None):
@@ -446,7 +446,7 @@ def _ws8_worker(rank, world, port, q):
                 if colsum is not None:
                     colsum += a[:, :n1].float().sum(0)
         ops.gemm_tn_acc_grouped = cpu_grouped
-        AF.WGRAD_WINDOW = 4
+        wgrad.WGRAD_WINDOW = 4
         T, C, NB, K = 512, 192, 9, 3                    # 9 blocks, the elastic configuration skips blocks 3 and 6; 3 micro-batches per update
 
         class Block(torch.autograd.Function):
@@ -459,10 +459,10 @@ def _ws8_worker(rank, world, port, q):
             @staticmethod
             def backward(ctx, dy):
                 x, w = ctx.saved_tensors
-                bufs, sunk = AF._param_grad_buffers(ctx.params)
-                with AF.wgrad_batch(sunk=True, params=ctx.params) as batch:
-                    AF._wgrad_batch.append((dy.contiguous(), x, bufs[0], C, C, bufs[1]))
-                AF._finish_param_grads(ctx.params, bufs, sunk, deferred=True)
+                bufs, sunk = wgrad._param_grad_buffers(ctx.params)
+                with wgrad.wgrad_batch(sunk=True, params=ctx.params) as batch:
+                    batch.add(ops.WgradProblem(dy.contiguous(), x, bufs[0], C, C, bufs[1]))
+                wgrad._finish_param_grads(ctx.params, bufs, sunk, deferred=True)
                 return (dy.float() @ w).to(torch.bfloat16), None, None
 
         torch.manual_seed(0)

@@ -163,7 +163,7 @@ def test_gemm_tn8_unsupported_width():
 
 
 def _block_run(monkeypatch, wgrad8, real8, real16, B=8, N=784, C=768, heads=16):
-    from autoprog_amd import functional as AF, ops
+    from autoprog_amd import functional as AF, ops, wgrad
     from autoprog_amd.models.volo import Transformer
     AF.reset_fp8_state()
     monkeypatch.setattr(AF, "FP8_LINEAR", True)
@@ -190,7 +190,7 @@ def _block_run(monkeypatch, wgrad8, real8, real16, B=8, N=784, C=768, heads=16):
                                     a.proj.bias, blk.norm2.weight, blk.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
                                     B, N, heads, blk.norm1.eps, k1, k2, tm1, tm2, 1.0 / keep)
     y.backward(dy)
-    AF.flush_wgrad_window()
+    wgrad.flush_wgrad_window()
     torch.cuda.synchronize()
     AF.reset_fp8_state()
     return y.detach().clone(), x.grad.detach().clone(), {n: p.grad.detach().clone() for n, p in blk.named_parameters()}, kinds

@@ -465,7 +465,7 @@ def test_gemm_tn_8p_tile_kernel(ops):
 
 
 def test_gemm_tn_8p_launch_of_many_blocks_is_unsplit_and_exact(ops):
-    """the weight gradients of several blocks in ONE launch (functional's weight-gradient window): about one 192 x 192 tile per CU, so no
+    """the weight gradients of several blocks in ONE launch (the weight-gradient window of wgrad.py): about one 192 x 192 tile per CU, so no
     token axis is cut and the tiles are plain read-add-stores -- every result is bitwise reproducible and matches fp64; two problems
     that add into the SAME gradient (a weight used twice) keep their atomics; a problem the tile kernel does not take (486 wide)
     and twelve LayerNorm reductions ride along"""

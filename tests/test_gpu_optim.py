@@ -364,10 +364,10 @@ def test_driver_gradient_accumulation_equals_one_large_batch():
 
 
 def test_weight_gradient_window_matches_one_launch_per_block(monkeypatch):
-    """functional's weight-gradient window: the blocks' weight gradients (and LayerNorm parameter gradients) leave in a few launches
+    """the weight-gradient window (wgrad.py): the blocks' weight gradients (and LayerNorm parameter gradients) leave in a few launches
     for the whole backward pass instead of one per block, and param.grad holds the same numbers (only the order of fp32 additions
     differs); the window is empty after the pass; AP_WGRAD_WINDOW=0 is the per-block behaviour"""
-    from autoprog_amd import functional as AF, ops
+    from autoprog_amd import ops, wgrad
     model, red, opt, loss_fn, x, target = _setup()
     try:
         calls = []
@@ -375,7 +375,7 @@ def test_weight_gradient_window_matches_one_launch_per_block(monkeypatch):
         monkeypatch.setattr(ops, "gemm_tn_acc_grouped", lambda problems, ln=None: (calls.append((len(problems), len(ln or []))), real(problems, ln=ln))[1])
         grads = {}
         for window in (0, 256):
-            monkeypatch.setattr(AF, "WGRAD_WINDOW", window)
+            monkeypatch.setattr(wgrad, "WGRAD_WINDOW", window)
             calls.clear()
             np.random.seed(0); torch.manual_seed(0)
             red.zero_grad()
@@ -386,7 +386,7 @@ def test_weight_gradient_window_matches_one_launch_per_block(monkeypatch):
             launches = [c for c in calls if c[0] > 1]
             if window:
                 assert len(launches) < n_block_launches and sum(c[0] for c in calls) == n_problems and sum(c[1] for c in calls) == n_ln
-                assert not AF._window["units"] and not AF._window["armed"]
+                assert not wgrad.window.units and not wgrad.window.armed
             else:
                 n_block_launches, n_problems, n_ln = len(launches), sum(c[0] for c in calls), sum(c[1] for c in calls)
                 assert n_block_launches >= 3

@@ -97,7 +97,7 @@ def main():
             tot_t += us; tot_f += fl
             print("%-16s %7d %5d %5d %9.1f %9.1f %9.1f" % (name, M, N1, N2, us, fl / us / 1e6, 2.0 * M * (N1 + N2) / us / 1e3))
         print("TN total %.1f us, %.1f TFLOP/s" % (tot_t, tot_f / tot_t / 1e6))
-        # grouped launches: the weight gradients of one block in ONE launch (functional.wgrad_batch)
+        # grouped launches: the weight gradients of one block in ONE launch (wgrad.wgrad_batch)
         groups = {"transformer block (qkv, proj, fc1, fc2)": [(T2, 1152, 384), (T2, 384, 384), (T2, 1152, 384), (T2, 384, 1152)],
                   "outlooker block (v, attn, proj, fc1, fc2)": [(T1, 192, 192), (P, 486, 192), (T1, 192, 192), (T1, 576, 192), (T1, 192, 576)]}
         for gname, shapes in groups.items():

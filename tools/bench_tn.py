@@ -1,6 +1,6 @@
 """Weight-gradient (TN) group timing on the VOLO-D1 block shapes, operands rotated over > 256 MiB: tools/bench_tn.py [reps]
 Compares AP_GEMM_TN_8P=1 (csrc/gemm_tn8p.h) with =0 (128 x 128-tile kernel) -- run once per setting (the switch is read once).
-Second table: the same problems of SIX transformer blocks in ONE launch (what functional's weight-gradient window issues), per block."""
+Second table: the same problems of SIX transformer blocks in ONE launch (what the weight-gradient window of wgrad.py issues), per block."""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from autoprog_amd import ops
