@@ -102,9 +102,9 @@ FUSED_MLP_LN = os.environ.get("AP_FUSED_MLP_LN", "1") == "1"
 FUSED_MLP_MIN_ROWS = int(os.environ.get("AP_FUSED_MLP_MIN_ROWS", "18432"))
 
 
-# Forward-only passes (validation, the search's probes -- anything under torch.no_grad()): the blocks run as plain functions that write only
-# what a forward needs (transformer_block / outlooker_block / class_block below), bit-identical to the training forward.  AP_INFER=0: every
-# forward goes through the training Functions, as before.
+# Forward-only passes (validation, the search's probes -- anything under torch.no_grad()): a block's forward body (_transformer_forward,
+# _outlooker_forward, _class_forward, _stem64_forward: the one its Function runs) is called directly with keep = False and writes only what a
+# forward needs, bit-identical to the training forward.  AP_INFER=0: every forward goes through the training Functions, as before.
 INFER = os.environ.get("AP_INFER", "1") != "0"
 
 
@@ -370,7 +370,107 @@ def _ln_fwd_for(x, gw, gb, eps, w):
     return y, m, r, None
 
 
+def infer_mode():
+    """does a block run its forward body without keeping anything for a backward?  Decided where the block Functions are applied (inside
+    Function.forward grad mode is always off).  An fp8 forward keeps the training Function even under no_grad."""
+    return INFER and not FP8_LINEAR and not torch.is_grad_enabled()
+
+
+def _fc1_fwd(x, fc1_w, fc1_b, keep, emit_for=None, x8=None, **kw):
+    """gelu(x fc1^T + b) of a block's MLP -> (a, h), h = what the launch stores next to a for the backward (_gelu_side_buffer).  Nothing kept in the
+    8-bit codes configuration: gelu = "table", the bits of the training launch and no side tensor, h = None (under AP_GELU_STORE_GRAD = 0 / 1 the
+    training launch's value is another kernel path's, so that launch itself runs, with its side buffer).  emit_for = fc2's weight (transformer
+    block): the launch goes through _linear_fwd and a is its pair (a, the e4m3 operand of fc2 or None)"""
+    if keep or STORE_GELU_GRAD != 2:
+        h = _gelu_side_buffer(x.shape[0], fc1_w.shape[0], x.device)
+        kw.update(gelu=True, preact_out=h, preact_grad=STORE_GELU_GRAD)
+    else:
+        h = None
+        kw.update(gelu="table")
+    if emit_for is not None:
+        return _linear_fwd(x, fc1_w, x8=x8, emit_for=emit_for, bias=fc1_b, **kw), h
+    return ops.gemm_nt(x, bank.get(fc1_w), bias=fc1_b, **kw), h
+
+
 # ----------------------------------------------------------------------- transformer block
+def _transformer_forward(x, rs1, rs2, n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b,
+                         B, N, heads, eps, k1=None, k2=None, tm1=None, tm2=None, inv_keep=None, *, keep):
+    """The forward of TransformerBlockFn.  keep: a backward follows -> (y, the tensors it reads in save_for_backward order, w8).  Otherwise -> y, and
+    what only the backward reads is not written (hidden activation, gelu' codes, LN copies and statistics of the fused MLP, token masks) and every
+    intermediate is dropped once the launch that reads it is enqueued.  rs / k may be the DropPath factors and masks of a train-mode no_grad
+    forward (the search's probes): the same launches take them, so the numbers are the training forward's.  fp8 forwards always keep (infer_mode)."""
+    C = x.shape[-1]
+    if keep and inv_keep is None and (rs1 is not None or rs2 is not None):
+        # dW / db of proj and fc2 are formed as inv_keep * dy^T (masked input): the factor cannot be defaulted, and the
+        # masks must be binary (rs = mask / keep) -- a caller on the old signature would get gradients scaled by `keep`
+        raise ValueError("TransformerBlockFn: DropPath factors rs1 / rs2 need inv_keep = 1 / keep_prob")
+    x2 = x.reshape(B * N, C).contiguous()
+    scale = (C // heads) ** -0.5
+    if rs1 is not None and k1 is None:
+        k1 = (rs1 != 0).float()
+    if rs2 is not None and k2 is None:
+        k2 = (rs2 != 0).float()
+    xn1, m1, r1, xq = _ln_fwd_for(x2, n1w, n1b, eps, qkv_w)
+    w8 = [None, None, None, None]     # FP8_WGRAD: (e4m3 input, dq) of qkv, proj, fc1, fc2 for the weight gradients
+    if _wgrad8_ok(xn1, qkv_w):
+        xq = w8[0] = _fp8_input(xn1, qkv_w, xq)
+    qkv = _linear_fwd(xn1, qkv_w, x8=xq, bias=qkv_b)
+    if not keep:
+        del xn1, m1, r1
+    oq = None
+    site = fp8_scales.producer(("x", id(proj_w)), x.device) if (FP8_LINEAR and ops.mhsa_emits_fp8(N, C // heads)) else None
+    if site is not None:          # the attention kernel emits the e4m3 operand of the output projection
+        o, lse, o8 = ops.mhsa_fwd(qkv, B, N, heads, scale, out_row_scale=k1, fp8=(site[0], site[1]))
+        oq = (o8, site[2])
+    else:
+        o, lse = ops.mhsa_fwd(qkv, B, N, heads, scale, out_row_scale=k1)                   # rows of dropped samples: zeros
+    if not keep:
+        del qkv, lse
+    if _wgrad8_ok(o, proj_w):
+        oq = w8[1] = _fp8_input(o, proj_w, oq)
+    x1 = _linear_fwd(o, proj_w, x8=oq, bias=proj_b, row_scale=rs1, rows_per_scale=N, residual=x2)
+    if not keep:
+        del o, x2
+    use_fused = FUSED_MLP and STORE_GELU_GRAD == 2 and not FP8_LINEAR and B * N >= FUSED_MLP_MIN_ROWS and ops.mlp_fused_ok(B * N, C, fc1_w.shape[0])
+    mlp_fused = ops.mlp_fused if keep else ops.mlp_fused_infer          # -> y with a, h (and LN2's outputs), or y alone; None: not taken
+    y = None
+    if use_fused and FUSED_MLP_LN:
+        # LN2 -> fc1 -> GELU -> fc2 (+ DropPath scale + residual) in ONE launch (csrc/mlp_fused.hip): bit-identical to the three launches
+        y = mlp_fused(None, bank.get(fc1_w), bank.get(fc2_w), bias1=fc1_b, bias2=fc2_b, row_scale_hidden=k2, row_scale_out=rs2,
+                      rows_per_scale=N, residual=x1, ln=(x1, n2w, n2b, eps))
+        if keep and y is not None:
+            y, a, h, xn2, m2, r2 = y
+    if y is None:
+        xn2, m2, r2, xq = _ln_fwd_for(x1, n2w, n2b, eps, fc1_w)
+        if use_fused:
+            y = mlp_fused(xn2, bank.get(fc1_w), bank.get(fc2_w), bias1=fc1_b, bias2=fc2_b, row_scale_hidden=k2, row_scale_out=rs2,
+                          rows_per_scale=N, residual=x1)
+            if keep and y is not None:
+                y, a, h = y
+    if y is None:
+        if _wgrad8_ok(xn2, fc1_w):
+            xq = w8[2] = _fp8_input(xn2, fc1_w, xq)
+        (a, aq), h = _fc1_fwd(xn2, fc1_w, fc1_b, keep, emit_for=fc2_w, x8=xq, row_scale=k2, rows_per_scale=N)
+        if keep:
+            # a bf16 layer input that only its weight gradient reads is not kept once that gradient runs on the e4m3 copy
+            xn1 = None if w8[0] is not None else xn1
+            xn2 = None if w8[2] is not None else xn2
+        else:
+            del xn2, m2, r2
+        if _wgrad8_ok(a, fc2_w):
+            aq = w8[3] = _fp8_input(a, fc2_w, aq)
+        y = _linear_fwd(a, fc2_w, x8=aq, bias=fc2_b, row_scale=rs2, rows_per_scale=N, residual=x1)
+        if w8[3] is not None:
+            a = None
+    if not keep:
+        return y.view(x.shape)
+    if rs1 is not None and tm1 is None:
+        tm1 = token_mask(k1, N)
+    if rs2 is not None and tm2 is None:
+        tm2 = token_mask(k2, N)
+    return y.view(x.shape), (x2, m1, r1, xn1, qkv, o, lse, x1, m2, r2, xn2, h, a, rs1, rs2, tm1, tm2), w8
+
+
 class TransformerBlockFn(torch.autograd.Function):
     """x -> x + rs1*(proj(mhsa(qkv(LN1 x)))) -> + rs2*(fc2(gelu(fc1(LN2 .))))
     (Transformer.forward, models/volo.py:230-234; timm Block for DeiT).  rs1/rs2 are the per-sample DropPath factors
@@ -384,74 +484,13 @@ class TransformerBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, rs1, rs2, n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b,
                 B, N, heads, eps, k1=None, k2=None, tm1=None, tm2=None, inv_keep=None):
-        C = x.shape[-1]
-        if rs1 is not None or rs2 is not None:
-            # dW / db of proj and fc2 are formed as inv_keep * dy^T (masked input): the factor cannot be defaulted, and the
-            # masks must be binary (rs = mask / keep) -- a caller on the old signature would get gradients scaled by `keep`
-            if inv_keep is None:
-                raise ValueError("TransformerBlockFn: DropPath factors rs1 / rs2 need inv_keep = 1 / keep_prob")
-        elif inv_keep is None:
-            inv_keep = 1.0
-        x2 = x.reshape(B * N, C).contiguous()
-        scale = (C // heads) ** -0.5
-        if rs1 is not None and k1 is None:
-            k1 = (rs1 != 0).float()
-        if rs2 is not None and k2 is None:
-            k2 = (rs2 != 0).float()
-        xn1, m1, r1, xq = _ln_fwd_for(x2, n1w, n1b, eps, qkv_w)
-        w8 = [None, None, None, None]     # FP8_WGRAD: (e4m3 input, dq) of qkv, proj, fc1, fc2 for the weight gradients
-        if _wgrad8_ok(xn1, qkv_w):
-            xq = w8[0] = _fp8_input(xn1, qkv_w, xq)
-        qkv = _linear_fwd(xn1, qkv_w, x8=xq, bias=qkv_b)
-        oq = None
-        site = fp8_scales.producer(("x", id(proj_w)), x.device) if (FP8_LINEAR and ops.mhsa_emits_fp8(N, C // heads)) else None
-        if site is not None:          # the attention kernel emits the e4m3 operand of the output projection
-            o, lse, o8 = ops.mhsa_fwd(qkv, B, N, heads, scale, out_row_scale=k1, fp8=(site[0], site[1]))
-            oq = (o8, site[2])
-        else:
-            o, lse = ops.mhsa_fwd(qkv, B, N, heads, scale, out_row_scale=k1)                   # rows of dropped samples: zeros
-        if _wgrad8_ok(o, proj_w):
-            oq = w8[1] = _fp8_input(o, proj_w, oq)
-        x1 = _linear_fwd(o, proj_w, x8=oq, bias=proj_b, row_scale=rs1, rows_per_scale=N, residual=x2)
-        fused = None
-        use_fused = FUSED_MLP and STORE_GELU_GRAD == 2 and not FP8_LINEAR and B * N >= FUSED_MLP_MIN_ROWS and ops.mlp_fused_ok(B * N, C, fc1_w.shape[0])
-        if use_fused and FUSED_MLP_LN:
-            # LN2 -> fc1 -> GELU -> fc2 (+ DropPath scale + residual) in ONE launch (csrc/mlp_fused.hip): bit-identical to the three launches
-            fused = ops.mlp_fused(None, bank.get(fc1_w), bank.get(fc2_w), bias1=fc1_b, bias2=fc2_b, row_scale_hidden=k2, row_scale_out=rs2,
-                                  rows_per_scale=N, residual=x1, ln=(x1, n2w, n2b, eps))
-            if fused is not None:
-                y, a, h, xn2, m2, r2 = fused
-        if fused is None:
-            xn2, m2, r2, xq = _ln_fwd_for(x1, n2w, n2b, eps, fc1_w)
-            if use_fused:
-                fused = ops.mlp_fused(xn2, bank.get(fc1_w), bank.get(fc2_w), bias1=fc1_b, bias2=fc2_b, row_scale_hidden=k2, row_scale_out=rs2,
-                                      rows_per_scale=N, residual=x1)
-                if fused is not None:
-                    y, a, h = fused
-        if fused is None:
-            h = _gelu_side_buffer(B * N, fc1_w.shape[0], x.device)
-            if _wgrad8_ok(xn2, fc1_w):
-                xq = w8[2] = _fp8_input(xn2, fc1_w, xq)
-            a, aq = _linear_fwd(xn2, fc1_w, x8=xq, emit_for=fc2_w, bias=fc1_b, gelu=True, preact_out=h, preact_grad=STORE_GELU_GRAD, row_scale=k2, rows_per_scale=N)
-            if _wgrad8_ok(a, fc2_w):
-                aq = w8[3] = _fp8_input(a, fc2_w, aq)
-            y = _linear_fwd(a, fc2_w, x8=aq, bias=fc2_b, row_scale=rs2, rows_per_scale=N, residual=x1)
-        if rs1 is not None and tm1 is None:
-            tm1 = token_mask(k1, N)
-        if rs2 is not None and tm2 is None:
-            tm2 = token_mask(k2, N)
-        if fused is None:
-            # a bf16 layer input that only its weight gradient reads is not kept once that gradient runs on the e4m3 copy
-            xn1 = None if w8[0] is not None else xn1
-            xn2 = None if w8[2] is not None else xn2
-            a = None if w8[3] is not None else a
+        params = (n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b)
+        y, kept, w8 = _transformer_forward(x, rs1, rs2, *params, B, N, heads, eps, k1, k2, tm1, tm2, inv_keep, keep=True)
         # the e4m3 inputs go with the saved tensors; their dq (views of the scale vector, which later quantisation sites write) as attributes
-        ctx.save_for_backward(x2, m1, r1, xn1, qkv, o, lse, x1, m2, r2, xn2, h, a, rs1, rs2, tm1, tm2,
-                              n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b,
-                              *[q[0] if q is not None else None for q in w8])
-        ctx.cfg = (B, N, heads, scale, float(inv_keep))
+        ctx.save_for_backward(*kept, *params, *[q[0] if q is not None else None for q in w8])
+        ctx.cfg = (B, N, heads, (x.shape[-1] // heads) ** -0.5, 1.0 if inv_keep is None else float(inv_keep))
         ctx.w8dq = [q[1] if q is not None else None for q in w8]
-        return y.view(x.shape)
+        return y
 
     @staticmethod
     def backward(ctx, dy):
@@ -503,65 +542,47 @@ class TransformerBlockFn(torch.autograd.Function):
         return (dx.view(dy.shape), None, None, *wgrad._finish_param_grads(params, bufs, sunk, batch.deferred), None, None, None, None, None, None, None, None, None)
 
 
-def infer_mode():
-    """does a block take its forward-only body?  Decided where the block Functions are applied (inside Function.forward grad mode is always off).
-    An fp8 forward keeps the training Function even under no_grad."""
-    return INFER and not FP8_LINEAR and not torch.is_grad_enabled()
-
-
-def _fc1_infer(x, fc1_w, fc1_b, **kw):
-    """gelu(x fc1^T + b) with the bits of the training forward's launch and no side tensor (8-bit codes configuration; under AP_GELU_STORE_GRAD = 0 / 1
-    the training launch's value is another kernel path's, so that launch itself runs, with its side buffer)"""
-    if STORE_GELU_GRAD == 2:
-        return ops.gemm_nt(x, bank.get(fc1_w), bias=fc1_b, gelu="table", **kw)
-    h = _gelu_side_buffer(x.shape[0], fc1_w.shape[0], x.device)
-    return ops.gemm_nt(x, bank.get(fc1_w), bias=fc1_b, gelu=True, preact_out=h, preact_grad=STORE_GELU_GRAD, **kw)
-
-
-def _transformer_block_infer(x, rs1, rs2, n1w, n1b, qkv_w, qkv_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b,
-                             B, N, heads, eps, k1=None, k2=None, tm1=None, tm2=None, inv_keep=None):
-    """TransformerBlockFn.forward without what only its backward reads (hidden activation, gelu' codes, LN copies and statistics of the fused MLP,
-    token masks); every intermediate is dropped once the launch that reads it is enqueued.  rs / k are the DropPath factors and masks of a
-    train-mode no_grad forward (the search's probes): the same launches take them, so the numbers are the training forward's."""
-    C = x.shape[-1]
-    x2 = x.reshape(B * N, C).contiguous()
-    scale = (C // heads) ** -0.5
-    if rs1 is not None and k1 is None:
-        k1 = (rs1 != 0).float()
-    if rs2 is not None and k2 is None:
-        k2 = (rs2 != 0).float()
-    xn1 = ops.layernorm_fwd(x2, n1w, n1b, eps)[0]
-    qkv = ops.gemm_nt(xn1, bank.get(qkv_w), bias=qkv_b)
-    del xn1
-    o = ops.mhsa_fwd(qkv, B, N, heads, scale, out_row_scale=k1)[0]
-    del qkv
-    x1 = ops.gemm_nt(o, bank.get(proj_w), bias=proj_b, row_scale=rs1, rows_per_scale=N, residual=x2)
-    del o, x2
-    use_fused = FUSED_MLP and STORE_GELU_GRAD == 2 and B * N >= FUSED_MLP_MIN_ROWS and ops.mlp_fused_ok(B * N, C, fc1_w.shape[0])
-    y = None
-    if use_fused and FUSED_MLP_LN:
-        y = ops.mlp_fused_infer(None, bank.get(fc1_w), bank.get(fc2_w), bias1=fc1_b, bias2=fc2_b, row_scale_hidden=k2, row_scale_out=rs2,
-                                rows_per_scale=N, residual=x1, ln=(x1, n2w, n2b, eps))
-    if y is None:
-        xn2 = ops.layernorm_fwd(x1, n2w, n2b, eps)[0]
-        if use_fused:
-            y = ops.mlp_fused_infer(xn2, bank.get(fc1_w), bank.get(fc2_w), bias1=fc1_b, bias2=fc2_b, row_scale_hidden=k2, row_scale_out=rs2,
-                                    rows_per_scale=N, residual=x1)
-        if y is None:
-            a = _fc1_infer(xn2, fc1_w, fc1_b, row_scale=k2, rows_per_scale=N)
-            del xn2
-            y = ops.gemm_nt(a, bank.get(fc2_w), bias=fc2_b, row_scale=rs2, rows_per_scale=N, residual=x1)
-    return y.view(x.shape)
-
-
 def transformer_block(x, *args):
-    """TransformerBlockFn.apply, or the forward-only body when no backward can follow (see infer_mode)"""
+    """TransformerBlockFn.apply, or its forward body alone when no backward can follow (see infer_mode)"""
     if infer_mode():
-        return _transformer_block_infer(x, *args)
+        return _transformer_forward(x, *args, keep=False)
     return TransformerBlockFn.apply(x, *args)
 
 
 # ----------------------------------------------------------------------------- class block
+def _class_forward(cls, tok, n1w, n1b, kv_w, kv_b, q_w, q_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, B, N, heads, eps, *, keep):
+    """The forward of ClassBlockFn.  keep: a backward follows -> (c2, the tensors it reads in save_for_backward order).  Otherwise -> c2: the same
+    launches in the same order, every intermediate dropped once its reader is enqueued (fc1 has B <= 256 rows, a launch the library serves with its
+    skinny kernel: ops.gemm_nt runs it with a side buffer of its own)"""
+    C = cls.shape[-1]
+    c0 = cls.reshape(B, C).contiguous()
+    t0 = tok.reshape(B * N, C).contiguous()
+    scale = (q_w.shape[0] // heads) ** -0.5
+    nc, mc, rc = ops.layernorm_fwd(c0, n1w, n1b, eps)
+    nt, mt, rt = ops.layernorm_fwd(t0, n1w, n1b, eps)
+    kv_t = ops.gemm_nt(nt, bank.get(kv_w), bias=kv_b)
+    if not keep:
+        del t0, nt, mc, rc, mt, rt
+    kv_c = ops.gemm_nt(nc, bank.get(kv_w), bias=kv_b)
+    q = ops.gemm_nt(nc, bank.get(q_w), bias=q_b)
+    if not keep:
+        del nc
+    o, probs = ops.class_attn_fwd(q, kv_t, B, N + 1, heads, scale, kv_cls=kv_c)
+    if not keep:
+        del q, kv_t, kv_c, probs
+    c1 = ops.gemm_nt(o, bank.get(proj_w), bias=proj_b, residual=c0)
+    if not keep:
+        del o, c0
+    n2, m2, r2 = ops.layernorm_fwd(c1, n2w, n2b, eps)
+    a, h = _fc1_fwd(n2, fc1_w, fc1_b, keep)
+    if not keep:
+        del n2, m2, r2
+    c2 = ops.gemm_nt(a, bank.get(fc2_w), bias=fc2_b, residual=c1)
+    if not keep:
+        return c2
+    return c2, (c0, t0, mc, rc, mt, rt, nc, nt, kv_t, kv_c, q, o, probs, c1, m2, r2, n2, h, a)
+
+
 class ClassBlockFn(torch.autograd.Function):
     """ClassBlock.forward (models/volo.py:304-308) on SEPARATE class token [B,C] and tokens [B*N,C]:
         cls += proj(class_attn(LN1([cls; tokens])));  cls += fc2(gelu(fc1(LN2(cls))))
@@ -574,25 +595,10 @@ class ClassBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cls, tok, n1w, n1b, kv_w, kv_b, q_w, q_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, B, N, heads, eps):
-        C = cls.shape[-1]
-        c0 = cls.reshape(B, C).contiguous()
-        t0 = tok.reshape(B * N, C).contiguous()
-        inner = q_w.shape[0]
-        scale = (inner // heads) ** -0.5
-        nc, mc, rc = ops.layernorm_fwd(c0, n1w, n1b, eps)
-        nt, mt, rt = ops.layernorm_fwd(t0, n1w, n1b, eps)
-        kv_t = ops.gemm_nt(nt, bank.get(kv_w), bias=kv_b)
-        kv_c = ops.gemm_nt(nc, bank.get(kv_w), bias=kv_b)
-        q = ops.gemm_nt(nc, bank.get(q_w), bias=q_b)
-        o, probs = ops.class_attn_fwd(q, kv_t, B, N + 1, heads, scale, kv_cls=kv_c)
-        c1 = ops.gemm_nt(o, bank.get(proj_w), bias=proj_b, residual=c0)
-        n2, m2, r2 = ops.layernorm_fwd(c1, n2w, n2b, eps)
-        h = _gelu_side_buffer(B, fc1_w.shape[0], cls.device)
-        a = ops.gemm_nt(n2, bank.get(fc1_w), bias=fc1_b, gelu=True, preact_out=h, preact_grad=STORE_GELU_GRAD)
-        c2 = ops.gemm_nt(a, bank.get(fc2_w), bias=fc2_b, residual=c1)
-        ctx.save_for_backward(c0, t0, mc, rc, mt, rt, nc, nt, kv_t, kv_c, q, o, probs, c1, m2, r2, n2, h, a,
-                              n1w, n1b, kv_w, kv_b, q_w, q_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b)
-        ctx.cfg = (B, N, heads, scale)
+        params = (n1w, n1b, kv_w, kv_b, q_w, q_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b)
+        c2, kept = _class_forward(cls, tok, *params, B, N, heads, eps, keep=True)
+        ctx.save_for_backward(*kept, *params)
+        ctx.cfg = (B, N, heads, (q_w.shape[0] // heads) ** -0.5)
         ctx.shapes = (cls.shape, tok.shape)
         ctx.set_materialize_grads(False)          # an unused output hands None to backward, not a zero tensor
         return c2, tok
@@ -623,35 +629,10 @@ class ClassBlockFn(torch.autograd.Function):
         return (dcls.view(ctx.shapes[0]), dtok.view(ctx.shapes[1]), *wgrad._finish_param_grads(params, bufs, sunk, batch.deferred), None, None, None, None)
 
 
-def _class_block_infer(cls, tok, n1w, n1b, kv_w, kv_b, q_w, q_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, B, N, heads, eps):
-    """ClassBlockFn.forward without what only its backward reads; the same launches in the same order otherwise (fc1 has B <= 256 rows, a launch
-    the library serves with its skinny kernel: ops.gemm_nt runs it with a side buffer of its own)"""
-    C = cls.shape[-1]
-    c0 = cls.reshape(B, C).contiguous()
-    t0 = tok.reshape(B * N, C).contiguous()
-    scale = (q_w.shape[0] // heads) ** -0.5
-    nc = ops.layernorm_fwd(c0, n1w, n1b, eps)[0]
-    nt = ops.layernorm_fwd(t0, n1w, n1b, eps)[0]
-    kv_t = ops.gemm_nt(nt, bank.get(kv_w), bias=kv_b)
-    del nt
-    kv_c = ops.gemm_nt(nc, bank.get(kv_w), bias=kv_b)
-    q = ops.gemm_nt(nc, bank.get(q_w), bias=q_b)
-    del nc
-    o = ops.class_attn_fwd(q, kv_t, B, N + 1, heads, scale, kv_cls=kv_c)[0]
-    del q, kv_t, kv_c
-    c1 = ops.gemm_nt(o, bank.get(proj_w), bias=proj_b, residual=c0)
-    del o
-    n2 = ops.layernorm_fwd(c1, n2w, n2b, eps)[0]
-    a = _fc1_infer(n2, fc1_w, fc1_b)
-    del n2
-    c2 = ops.gemm_nt(a, bank.get(fc2_w), bias=fc2_b, residual=c1)
-    return c2, tok
-
-
 def class_block(cls, tok, *args):
-    """ClassBlockFn.apply, or the forward-only body when no backward can follow (see infer_mode)"""
+    """ClassBlockFn.apply, or its forward body alone when no backward can follow (see infer_mode)"""
     if infer_mode():
-        return _class_block_infer(cls, tok, *args)
+        return _class_forward(cls, tok, *args, keep=False), tok
     return ClassBlockFn.apply(cls, tok, *args)
 
 
@@ -659,6 +640,37 @@ FUSE_POOL_BWD = os.environ.get("AP_FUSE_POOL_BWD", "1") != "0"      # 0: the ave
 
 
 # ------------------------------------------------------------------------- outlooker block
+def _outlooker_forward(x, n1w, n1b, v_w, v_b, attn_w, attn_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, heads, eps, *, keep):
+    """The forward of OutlookerBlockFn.  keep: a backward follows -> (y, the tensors it reads in save_for_backward order).  Otherwise -> y, without
+    the gelu' codes (T x 3 C bytes per block) and with every intermediate dropped once its reader is enqueued"""
+    B, H, W, C = x.shape
+    T = B * H * W
+    x2 = x.reshape(T, C).contiguous()
+    scale = (C // heads) ** -0.5
+    xn1, m1, r1 = ops.layernorm_fwd(x2, n1w, n1b, eps)
+    v = ops.gemm_nt(xn1, bank.get(v_w), bias=v_b)
+    pooled2 = ops.avgpool2_fwd(xn1.view(B, H, W, C)).view(-1, C)
+    if not keep:
+        del xn1, m1, r1
+    logits = ops.gemm_nt(pooled2, bank.get(attn_w), bias=attn_b)                 # [B*h*w, ld(heads*81)]
+    if not keep:
+        del pooled2
+    yo = ops.outlook_fwd(v.view(B, H, W, C), logits, heads, scale)
+    if not keep:
+        del v, logits
+    x1 = ops.gemm_nt(yo.view(T, C), bank.get(proj_w), bias=proj_b, residual=x2)
+    if not keep:
+        del yo, x2
+    xn2, m2, r2 = ops.layernorm_fwd(x1, n2w, n2b, eps)
+    a, h = _fc1_fwd(xn2, fc1_w, fc1_b, keep)
+    if not keep:
+        del xn2, m2, r2
+    y = ops.gemm_nt(a, bank.get(fc2_w), bias=fc2_b, residual=x1).view(x.shape)
+    if not keep:
+        return y
+    return y, (x2, m1, r1, xn1, v, pooled2, logits, yo, x1, m2, r2, xn2, h, a)
+
+
 class OutlookerBlockFn(torch.autograd.Function):
     """Outlooker.forward (models/volo.py:140-144) with OutlookAttention (models/volo.py:77-103):
     x += proj(outlook(v(LN1 x), attn(pool(LN1 x)))) ; x += fc2(gelu(fc1(LN2 x)))."""
@@ -666,25 +678,12 @@ class OutlookerBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, n1w, n1b, v_w, v_b, attn_w, attn_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b,
                 heads, eps):
+        params = (n1w, n1b, v_w, v_b, attn_w, attn_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b)
+        y, kept = _outlooker_forward(x, *params, heads, eps, keep=True)
+        ctx.save_for_backward(*kept, *params)
         B, H, W, C = x.shape
-        T = B * H * W
-        x2 = x.reshape(T, C).contiguous()
-        scale = (C // heads) ** -0.5
-        xn1, m1, r1 = ops.layernorm_fwd(x2, n1w, n1b, eps)
-        v = ops.gemm_nt(xn1, bank.get(v_w), bias=v_b)
-        pooled = ops.avgpool2_fwd(xn1.view(B, H, W, C))
-        pooled2 = pooled.view(-1, C)
-        logits = ops.gemm_nt(pooled2, bank.get(attn_w), bias=attn_b)                 # [B*h*w, ld(heads*81)]
-        yo = ops.outlook_fwd(v.view(B, H, W, C), logits, heads, scale)
-        x1 = ops.gemm_nt(yo.view(T, C), bank.get(proj_w), bias=proj_b, residual=x2)
-        xn2, m2, r2 = ops.layernorm_fwd(x1, n2w, n2b, eps)
-        h = _gelu_side_buffer(T, fc1_w.shape[0], x.device)
-        a = ops.gemm_nt(xn2, bank.get(fc1_w), bias=fc1_b, gelu=True, preact_out=h, preact_grad=STORE_GELU_GRAD)
-        y = ops.gemm_nt(a, bank.get(fc2_w), bias=fc2_b, residual=x1)
-        ctx.save_for_backward(x2, m1, r1, xn1, v, pooled2, logits, yo, x1, m2, r2, xn2, h, a,
-                              n1w, n1b, v_w, v_b, attn_w, attn_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b)
-        ctx.cfg = (B, H, W, C, heads, scale)
-        return y.view(x.shape)
+        ctx.cfg = (B, H, W, C, heads, (C // heads) ** -0.5)
+        return y
 
     @staticmethod
     def backward(ctx, dy):
@@ -712,33 +711,10 @@ class OutlookerBlockFn(torch.autograd.Function):
         return (dx.view(dy.shape), *wgrad._finish_param_grads(params, bufs, sunk, batch.deferred), None, None)
 
 
-def _outlooker_block_infer(x, n1w, n1b, v_w, v_b, attn_w, attn_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, heads, eps):
-    """OutlookerBlockFn.forward without the gelu' codes (T x 3 C bytes per block) and with every intermediate dropped once its reader is enqueued"""
-    B, H, W, C = x.shape
-    T = B * H * W
-    x2 = x.reshape(T, C).contiguous()
-    scale = (C // heads) ** -0.5
-    xn1 = ops.layernorm_fwd(x2, n1w, n1b, eps)[0]
-    v = ops.gemm_nt(xn1, bank.get(v_w), bias=v_b)
-    pooled = ops.avgpool2_fwd(xn1.view(B, H, W, C))
-    del xn1
-    logits = ops.gemm_nt(pooled.view(-1, C), bank.get(attn_w), bias=attn_b)
-    del pooled
-    yo = ops.outlook_fwd(v.view(B, H, W, C), logits, heads, scale)
-    del v, logits
-    x1 = ops.gemm_nt(yo.view(T, C), bank.get(proj_w), bias=proj_b, residual=x2)
-    del yo, x2
-    xn2 = ops.layernorm_fwd(x1, n2w, n2b, eps)[0]
-    a = _fc1_infer(xn2, fc1_w, fc1_b)
-    del xn2
-    y = ops.gemm_nt(a, bank.get(fc2_w), bias=fc2_b, residual=x1)
-    return y.view(x.shape)
-
-
 def outlooker_block(x, *args):
-    """OutlookerBlockFn.apply, or the forward-only body when no backward can follow (see infer_mode)"""
+    """OutlookerBlockFn.apply, or its forward body alone when no backward can follow (see infer_mode)"""
     if infer_mode():
-        return _outlooker_block_infer(x, *args)
+        return _outlooker_forward(x, *args, keep=False)
     return OutlookerBlockFn.apply(x, *args)
 
 
@@ -1242,6 +1218,12 @@ def patch_conv_ok(x, weight, k):
             and weight.shape[2] == k and weight.shape[3] == k)
 
 
+def _z_and_partials(result, training):
+    """a stem convolution called with want_stats = training -> (z, partials): the partial BatchNorm statistics come next to z in training mode only;
+    in eval mode partials = None, bn_relu_fwd's default (it then takes the running statistics)"""
+    return result if training else (result, None)
+
+
 class Conv7BNReLUFn(torch.autograd.Function):
     """conv7x7 / stride 2 (3 -> 64, no bias) -> BatchNorm2d -> ReLU: the first triple of the VOLO stem (models/volo.py:355-358) on the
     space-to-depth image xs [B,H,W,16] (ops.resize_bilinear_s2d16) -- csrc/conv7.hip; the image needs no gradient."""
@@ -1249,12 +1231,8 @@ class Conv7BNReLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xs, conv_w, weight, bias, running_mean, running_var, training, momentum, eps):
         wp = ops.conv7_pack(conv_w.detach().float().contiguous())
-        if training:
-            z, partials = ops.conv7_s2d(xs, wp, True)
-            y, mean, rstd = ops.bn_relu_fwd(z, weight, bias, running_mean, running_var, True, momentum, eps, partials=partials)
-        else:
-            z = ops.conv7_s2d(xs, wp)
-            y, mean, rstd = ops.bn_relu_fwd(z, weight, bias, running_mean, running_var, False, momentum, eps)
+        z, partials = _z_and_partials(ops.conv7_s2d(xs, wp, training), training)
+        y, mean, rstd = ops.bn_relu_fwd(z, weight, bias, running_mean, running_var, training, momentum, eps, partials=partials)
         ctx.save_for_backward(xs, z, conv_w, weight, bias, mean, rstd)
         ctx.training = training
         return y
@@ -1281,12 +1259,8 @@ class Conv3x3BNReLUFn(torch.autograd.Function):
     def forward(ctx, x, conv_w, weight, bias, running_mean, running_var, training, momentum, eps):
         xc = x.contiguous()
         wf, wb = ops.conv3x3_pack(conv_w.detach().float().contiguous())
-        if training:
-            z, partials = ops.conv3x3_c64(xc, wf, True)
-            y, mean, rstd = ops.bn_relu_fwd(z, weight, bias, running_mean, running_var, True, momentum, eps, partials=partials)
-        else:
-            z = ops.conv3x3_c64(xc, wf)
-            y, mean, rstd = ops.bn_relu_fwd(z, weight, bias, running_mean, running_var, False, momentum, eps)
+        z, partials = _z_and_partials(ops.conv3x3_c64(xc, wf, training), training)
+        y, mean, rstd = ops.bn_relu_fwd(z, weight, bias, running_mean, running_var, training, momentum, eps, partials=partials)
         ctx.save_for_backward(xc, z, wb, conv_w, weight, bias, mean, rstd)
         ctx.training = training
         return y
@@ -1305,6 +1279,36 @@ class Conv3x3BNReLUFn(torch.autograd.Function):
         return dx, dw, dg, db, None, None, None, None, None
 
 
+def _stem64_forward(xs, w7, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2, w3, g3, b3, rm3, rv3, training, momentum, eps, apply_last=True, *, keep):
+    """The forward of Stem64Fn.  apply_last = False (round 5): the result is (z3, mean3, rstd3), the PRE-BatchNorm output of the last convolution and
+    its batch (or running) statistics, not y; the consumer -- PatchConvFn with bn_* -- applies relu(bn3(.)) while it stages z3 and returns dL/dz3
+    with the BatchNorm's backward already applied; g3 / b3 then get their gradients there, not here.
+    keep: a backward follows -> (result, the tensors it reads in save_for_backward order).  Otherwise -> result, from the same launches (a train-mode
+    probe still takes batch statistics and updates the running ones), but a convolution's pre-BatchNorm output (205 MB at B = 128, 224 px) is dropped
+    as soon as the next convolution is enqueued instead of living to the end of the node -- the three of them are the peak of a whole no_grad forward"""
+    wp7 = ops.conv7_pack(w7.detach().float().contiguous())
+    wf2, wb2 = ops.conv3x3_pack(w2.detach().float().contiguous())
+    wf3, wb3 = ops.conv3x3_pack(w3.detach().float().contiguous())
+    if not keep:
+        del wb2, wb3                       # the operands of the input-gradient convolutions
+    mom1, mom2, mom3 = momentum
+    eps1, eps2, eps3 = eps
+    z1, p1 = _z_and_partials(ops.conv7_s2d(xs, wp7, training), training)
+    _, mean1, rstd1 = ops.bn_relu_fwd(z1, g1, b1, rm1, rv1, training, mom1, eps1, partials=p1, apply=False)
+    z2, p2 = _z_and_partials(ops.conv3x3_c64(z1, wf2, training, bn_in=(mean1, rstd1, g1, b1)), training)
+    if not keep:
+        del z1
+    _, mean2, rstd2 = ops.bn_relu_fwd(z2, g2, b2, rm2, rv2, training, mom2, eps2, partials=p2, apply=False)
+    z3, p3 = _z_and_partials(ops.conv3x3_c64(z2, wf3, training, bn_in=(mean2, rstd2, g2, b2)), training)
+    if not keep:
+        del z2
+    y, mean3, rstd3 = ops.bn_relu_fwd(z3, g3, b3, rm3, rv3, training, mom3, eps3, partials=p3, apply=apply_last)
+    result = y if apply_last else (z3, mean3, rstd3)
+    if not keep:
+        return result
+    return result, (xs, z1, z2, z3, wb2, wb3, w7, g1, b1, w2, g2, b2, w3, g3, b3, mean1, rstd1, mean2, rstd2, mean3, rstd3)
+
+
 class Stem64Fn(torch.autograd.Function):
     """The whole 64-wide stem in front of the patch projection (models/volo.py:355-366): conv7x7/s2 -> BN -> ReLU -> conv3x3 -> BN -> ReLU
     -> conv3x3 -> BN -> ReLU on the space-to-depth image, as ONE autograd node so that the two activations between the convolutions
@@ -1315,35 +1319,13 @@ class Stem64Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xs, w7, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2, w3, g3, b3, rm3, rv3, training, momentum, eps, apply_last=True):
-        """apply_last = False (round 5): -> (z3, mean3, rstd3), the PRE-BatchNorm output of the last convolution and its batch (or running)
-        statistics; the consumer -- PatchConvFn with bn_* -- applies relu(bn3(.)) while it stages z3 and returns dL/dz3 with the BatchNorm's
-        backward already applied; g3 / b3 then get their gradients there, not here"""
-        wp7 = ops.conv7_pack(w7.detach().float().contiguous())
-        wf2, wb2 = ops.conv3x3_pack(w2.detach().float().contiguous())
-        wf3, wb3 = ops.conv3x3_pack(w3.detach().float().contiguous())
-        mom1, mom2, mom3 = momentum
-        eps1, eps2, eps3 = eps
-        if training:
-            z1, p1 = ops.conv7_s2d(xs, wp7, True)
-            _, mean1, rstd1 = ops.bn_relu_fwd(z1, g1, b1, rm1, rv1, True, mom1, eps1, partials=p1, apply=False)
-            z2, p2 = ops.conv3x3_c64(z1, wf2, True, bn_in=(mean1, rstd1, g1, b1))
-            _, mean2, rstd2 = ops.bn_relu_fwd(z2, g2, b2, rm2, rv2, True, mom2, eps2, partials=p2, apply=False)
-            z3, p3 = ops.conv3x3_c64(z2, wf3, True, bn_in=(mean2, rstd2, g2, b2))
-            y, mean3, rstd3 = ops.bn_relu_fwd(z3, g3, b3, rm3, rv3, True, mom3, eps3, partials=p3, apply=apply_last)
-        else:
-            z1 = ops.conv7_s2d(xs, wp7)
-            _, mean1, rstd1 = ops.bn_relu_fwd(z1, g1, b1, rm1, rv1, False, mom1, eps1, apply=False)
-            z2 = ops.conv3x3_c64(z1, wf2, bn_in=(mean1, rstd1, g1, b1))
-            _, mean2, rstd2 = ops.bn_relu_fwd(z2, g2, b2, rm2, rv2, False, mom2, eps2, apply=False)
-            z3 = ops.conv3x3_c64(z2, wf3, bn_in=(mean2, rstd2, g2, b2))
-            y, mean3, rstd3 = ops.bn_relu_fwd(z3, g3, b3, rm3, rv3, False, mom3, eps3, apply=apply_last)
-        ctx.save_for_backward(xs, z1, z2, z3, wb2, wb3, w7, g1, b1, w2, g2, b2, w3, g3, b3, mean1, rstd1, mean2, rstd2, mean3, rstd3)
+        result, kept = _stem64_forward(xs, w7, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2, w3, g3, b3, rm3, rv3, training, momentum, eps, apply_last, keep=True)
+        ctx.save_for_backward(*kept)
         ctx.training = training
         ctx.apply_last = apply_last
         if not apply_last:
-            ctx.mark_non_differentiable(mean3, rstd3)
-            return z3, mean3, rstd3
-        return y
+            ctx.mark_non_differentiable(*result[1:])          # mean3, rstd3
+        return result
 
     @staticmethod
     def backward(ctx, dy, *_unused):
@@ -1380,40 +1362,10 @@ class Stem64Fn(torch.autograd.Function):
         return (None, gr[0], gr[1], gr[2], None, None, gr[3], gr[4], gr[5], None, None, gr[6], gr[7], gr[8], None, None, None, None, None, None)
 
 
-def _stem64_infer(xs, w7, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2, w3, g3, b3, rm3, rv3, training, momentum, eps, apply_last=True):
-    """Stem64Fn.forward for a pass no backward follows: the same launches (the stem keeps the kernels it has; a train-mode probe still takes
-    batch statistics and updates the running ones), but a convolution's pre-BatchNorm output (205 MB at B = 128, 224 px) is dropped as soon as
-    the next convolution is enqueued instead of living to the end of the node -- the three of them are the peak of a whole no_grad forward"""
-    wp7 = ops.conv7_pack(w7.detach().float().contiguous())
-    wf2 = ops.conv3x3_pack(w2.detach().float().contiguous())[0]
-    wf3 = ops.conv3x3_pack(w3.detach().float().contiguous())[0]
-    mom1, mom2, mom3 = momentum
-    eps1, eps2, eps3 = eps
-    if training:
-        z1, p1 = ops.conv7_s2d(xs, wp7, True)
-        _, mean1, rstd1 = ops.bn_relu_fwd(z1, g1, b1, rm1, rv1, True, mom1, eps1, partials=p1, apply=False)
-        z2, p2 = ops.conv3x3_c64(z1, wf2, True, bn_in=(mean1, rstd1, g1, b1))
-        del z1
-        _, mean2, rstd2 = ops.bn_relu_fwd(z2, g2, b2, rm2, rv2, True, mom2, eps2, partials=p2, apply=False)
-        z3, p3 = ops.conv3x3_c64(z2, wf3, True, bn_in=(mean2, rstd2, g2, b2))
-        del z2
-        y, mean3, rstd3 = ops.bn_relu_fwd(z3, g3, b3, rm3, rv3, True, mom3, eps3, partials=p3, apply=apply_last)
-    else:
-        z1 = ops.conv7_s2d(xs, wp7)
-        _, mean1, rstd1 = ops.bn_relu_fwd(z1, g1, b1, rm1, rv1, False, mom1, eps1, apply=False)
-        z2 = ops.conv3x3_c64(z1, wf2, bn_in=(mean1, rstd1, g1, b1))
-        del z1
-        _, mean2, rstd2 = ops.bn_relu_fwd(z2, g2, b2, rm2, rv2, False, mom2, eps2, apply=False)
-        z3 = ops.conv3x3_c64(z2, wf3, bn_in=(mean2, rstd2, g2, b2))
-        del z2
-        y, mean3, rstd3 = ops.bn_relu_fwd(z3, g3, b3, rm3, rv3, False, mom3, eps3, apply=apply_last)
-    return y if apply_last else (z3, mean3, rstd3)
-
-
 def stem64(xs, *args):
-    """Stem64Fn.apply, or the forward-only body when no backward can follow (see infer_mode)"""
+    """Stem64Fn.apply, or its forward body alone when no backward can follow (see infer_mode)"""
     if infer_mode():
-        return _stem64_infer(xs, *args)
+        return _stem64_forward(xs, *args, keep=False)
     return Stem64Fn.apply(xs, *args)
 
 

@@ -232,10 +232,9 @@ def mlp_fused_ok(M, C, hidden):
     return C == 384 and hidden == 3 * C and M % 128 == 0 and M > 0
 
 
-def mlp_fused_infer(x, wa, wb, bias1=None, bias2=None, row_scale_hidden=None, row_scale_out=None, rows_per_scale=1, residual=None, ln=None):
-    """the forward of mlp_fused for a pass no backward follows (ap_mlp_fused_infer): -> out [M, C], bit-identical to mlp_fused(...)[0]; the hidden
-    activation, the gelu' codes and LN(rows) / mean / rstd are neither allocated nor written.  ln = (rows, gamma, beta, eps) with x = None as in mlp_fused.
-    -> None when the library does not take the launch"""
+def _mlp_fused_args(x, wa, wb, bias1, bias2, row_scale_hidden, row_scale_out, rows_per_scale, residual, ln):
+    """what mlp_fused and mlp_fused_infer hand to the library alike: -> (MlpFusedArgs without side outputs and direction, out [M, C], the rows read:
+    x, or ln[0]), or None where mlp_fused_ok refuses the shape"""
     from ._lib import MlpFusedArgs
     if ln is not None:
         x = _req(ln[0], BF16, "ln rows")
@@ -259,12 +258,24 @@ def mlp_fused_infer(x, wa, wb, bias1=None, bias2=None, row_scale_hidden=None, ro
     if residual is not None:
         _req(residual, BF16, "residual")
         a.residual, a.ldr = residual.data_ptr(), residual.shape[1]
-    a.m, a.c, a.hidden, a.backward = M, C, H, 0
+    a.m, a.c, a.hidden = M, C, H
     if ln is not None:
         a.x = None
         a.ln_in, a.ld_ln = x.data_ptr(), C
         a.ln_gamma, a.ln_beta = _req(ln[1], torch.float32, "ln gamma").data_ptr(), _req(ln[2], torch.float32, "ln beta").data_ptr()
         a.ln_eps = float(ln[3])
+    return a, out, x
+
+
+def mlp_fused_infer(x, wa, wb, bias1=None, bias2=None, row_scale_hidden=None, row_scale_out=None, rows_per_scale=1, residual=None, ln=None):
+    """the forward of mlp_fused for a pass no backward follows (ap_mlp_fused_infer): -> out [M, C], bit-identical to mlp_fused(...)[0]; the hidden
+    activation, the gelu' codes and LN(rows) / mean / rstd are neither allocated nor written.  ln = (rows, gamma, beta, eps) with x = None as in mlp_fused.
+    -> None when the library does not take the launch"""
+    args = _mlp_fused_args(x, wa, wb, bias1, bias2, row_scale_hidden, row_scale_out, rows_per_scale, residual, ln)
+    if args is None:
+        return None
+    a, out, _ = args
+    a.backward = 0
     code = lib.ap_mlp_fused_infer(ctypes.byref(a), _stream())
     if code == -2:                    # AP_ERR_UNSUPPORTED
         return None
@@ -280,44 +291,22 @@ def mlp_fused(x, wa, wb, backward=False, bias1=None, bias2=None, row_scale_hidde
     ln = (rows [M, C], gamma, beta, eps) (forward; x = None): the LayerNorm in front of fc1 runs inside the launch, bit-identical to
     layernorm_fwd -> (out, a, codes, LN(rows), mean, rstd)
     -> None when the library does not take the launch (the caller issues the two ap_gemm_nt launches)"""
-    from ._lib import MlpFusedArgs
-    if ln is not None:
-        x = _req(ln[0], BF16, "ln rows")
-    _req(x, BF16, "x"); _req(wa, BF16, "wa"); _req(wb, BF16, "wb")
-    M, C = x.shape
-    H = wa.shape[0]
-    if not mlp_fused_ok(M, C, H):
+    args = _mlp_fused_args(x, wa, wb, bias1, bias2, row_scale_hidden, row_scale_out, rows_per_scale, residual, ln)
+    if args is None:
         return None
-    out = torch.empty((M, C), dtype=BF16, device=x.device)
+    a, out, x = args
+    M, C, H = a.m, a.c, a.hidden
     hid = torch.empty((M, H), dtype=BF16, device=x.device)
     if backward:
         _req(codes, torch.uint8, "codes")
     else:
         codes = torch.empty((M, H), dtype=torch.uint8, device=x.device)
-    a = MlpFusedArgs()
-    a.x, a.ldx = x.data_ptr(), x.shape[1]
-    a.wa, a.ldwa = wa.data_ptr(), wa.shape[1]
-    a.wb, a.ldwb = wb.data_ptr(), wb.shape[1]
-    a.out, a.ldo = out.data_ptr(), C
-    a.hidden_out, a.ldh = hid.data_ptr(), H
-    a.codes = codes.data_ptr()
-    a.bias1 = _req(bias1, torch.float32, "bias1").data_ptr() if bias1 is not None else None
-    a.bias2 = _req(bias2, torch.float32, "bias2").data_ptr() if bias2 is not None else None
-    a.row_scale_hidden = _req(row_scale_hidden, torch.float32, "row_scale_hidden").data_ptr() if row_scale_hidden is not None else None
-    a.row_scale_out = _req(row_scale_out, torch.float32, "row_scale_out").data_ptr() if row_scale_out is not None else None
-    a.rows_per_scale = int(rows_per_scale)
-    if residual is not None:
-        _req(residual, BF16, "residual")
-        a.residual, a.ldr = residual.data_ptr(), residual.shape[1]
-    a.m, a.c, a.hidden, a.backward = M, C, H, 1 if backward else 0
+    a.hidden_out, a.codes, a.backward = hid.data_ptr(), codes.data_ptr(), 1 if backward else 0
     if ln is not None:
         xn = torch.empty((M, C), dtype=BF16, device=x.device)
         mean = torch.empty(M, dtype=torch.float32, device=x.device)
         rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-        a.x = None
-        a.ln_in, a.ld_ln, a.ln_out, a.ld_lno = x.data_ptr(), C, xn.data_ptr(), C
-        a.ln_gamma, a.ln_beta = _req(ln[1], torch.float32, "ln gamma").data_ptr(), _req(ln[2], torch.float32, "ln beta").data_ptr()
-        a.ln_eps, a.ln_mean, a.ln_rstd = float(ln[3]), mean.data_ptr(), rstd.data_ptr()
+        a.ln_out, a.ld_lno, a.ln_mean, a.ln_rstd = xn.data_ptr(), C, mean.data_ptr(), rstd.data_ptr()
     code = lib.ap_mlp_fused(ctypes.byref(a), _stream())
     if code == -2:                    # AP_ERR_UNSUPPORTED (e.g. the GELU table cannot be built inside a stream capture)
         return None

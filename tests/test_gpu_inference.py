@@ -195,6 +195,37 @@ def test_class_block_forward_only_equals_training_forward(monkeypatch):
     assert torch.equal(got, blk.forward_split(cls, tok).detach())
 
 
+@pytest.mark.parametrize("mode,fuse_proj", [("train", True), ("eval", True), ("train", False)])
+def test_stem_forward_only_equals_training_forward_with_its_running_statistics(monkeypatch, mode, fuse_proj):
+    """the 64-wide stem under no_grad, forward-only body against the training Function from the same state_dict: the output and every buffer after
+    the pass (a train-mode pass takes batch statistics and updates the running ones), on an odd batch and a map that does not divide the
+    convolution tiles.  fuse_proj: the last BatchNorm + ReLU inside the patch projection (Stem64Fn apply_last = False), or applied by the stem"""
+    from autoprog_amd import functional as AF
+    from autoprog_amd.models.volo import PatchEmbed
+    monkeypatch.setattr(AF, "STEM_FUSE_BN_PROJ", fuse_proj)
+    torch.manual_seed(11)
+    pe = PatchEmbed(stem_conv=True, stem_stride=2, patch_size=8, in_chans=3, hidden_dim=64, embed_dim=192).cuda()
+    with torch.no_grad():
+        for name, b in pe.named_buffers():                        # running statistics away from their initial 0 / 1: an eval pass reads them
+            if name.endswith("running_mean"):
+                b.normal_(std=0.2)
+            elif name.endswith("running_var"):
+                b.uniform_(0.5, 1.5)
+    pe.train(mode == "train")
+    state = {k: v.clone() for k, v in pe.state_dict().items()}
+    x = torch.randn(3, 3, 80, 80, device="cuda", generator=torch.Generator(device="cuda").manual_seed(3))
+
+    def run():
+        pe.load_state_dict(state)
+        return pe(x).clone(), {n: b.clone() for n, b in pe.named_buffers()}
+    (y, bufs), (y_ref, bufs_ref) = _both_paths(monkeypatch, run)
+    assert torch.equal(y, y_ref) and bool(torch.isfinite(y.float()).all())
+    assert set(bufs) == set(bufs_ref) and len(bufs) == 9          # three BatchNorms: running_mean, running_var, num_batches_tracked
+    for n in bufs:
+        assert torch.equal(bufs[n], bufs_ref[n]), n
+        assert torch.equal(bufs[n], state[n]) == (mode == "eval"), n      # train mode moved every one of them, eval none
+
+
 # ------------------------------------------------------------------------------------------------ 4 / 5. whole models
 def _outs(o):
     return [t for t in (o if isinstance(o, (tuple, list)) else [o]) if torch.is_tensor(t)]
