@@ -99,7 +99,10 @@ int ap_layernorm_bwd_reduce_batched(const ap_ln_reduce* items, int count, ap_str
 /* ---- Linear layers (nn.Linear: models/volo.py:67,68,71,156,158,180,182,253,256,258,547,553)
  * C[M,N] = epilogue( A[M,K] . B[N,K]^T )   bf16 in, fp32 MFMA accumulate, bf16 out
  * epilogue order: +bias[n]; GELU (optionally also storing the pre-activation); * gelu'(h[m,n]);
- * * row_scale[m / rows_per_scale] (DropPath, timm); + residual[m,n]                         */
+ * * row_scale[m / rows_per_scale] (DropPath, timm); + residual[m,n]
+ * Only the N logical columns are written: columns N .. ldc-1 of C (and of preact_out / q8_out, whose leading dimension is ldc) keep what
+ * they held, also inside the last 16-byte chunk when N % 8 != 0; nothing is read from the columns K .. lda-1 / K .. ldb-1 of A / B, the
+ * columns N .. ldr-1 of residual or N .. ldc-1 of dgelu_of / mul_by / mul_by8 in a way that reaches the output (padding may hold anything) */
 /* Patch addressing: a k x k / stride k convolution on an NHWC feature map [B,H,W,C] (PatchEmbed.proj, Downsample:
  * models/volo.py:368-372,383-396) is a GEMM whose row m = (b, i, j) and column kk = (dy, dx, c) live at element offset
  *   (m / group) * group_stride + (m % group) * row_stride + (kk / kseg) * kseg_stride + (kk % kseg)
@@ -203,7 +206,8 @@ int ap_debug_poison_lds(unsigned pattern, unsigned* scratch2, ap_stream_t stream
 int ap_gemm_nt_fp8(const unsigned char* A, int lda, const unsigned char* B, int ldb, ap_bf16* C, int ldc, int M, int N, int K,
                    const float* dq_a, const float* dq_b, const struct ap_gemm_epilogue* epi, ap_stream_t stream);
 /* weight gradient: C[N1,N2] += A[M,N1]^T . B[M,N2]   (fp32 accumulate into C, atomics);
- * optional fused bias gradient: colsum_A[n] += sum_m A[m,n] (NULL to skip) */
+ * optional fused bias gradient: colsum_A[n] += sum_m A[m,n] (NULL to skip).  Columns N2 .. ldc-1 of C are neither read nor written;
+ * the columns N1 .. lda-1 / N2 .. ldb-1 of A / B may hold anything */
 int ap_gemm_tn_acc(const ap_bf16* A, int lda, const ap_bf16* B, int ldb, float* C, int ldc,
                    int M, int N1, int N2, float* colsum_A, ap_stream_t stream);
 /* the same for up to AP_TN_MAX_GROUP problems in ONE launch (all Linear layers of a block, or of several blocks: the
@@ -269,7 +273,8 @@ int ap_colsum_acc(const ap_bf16* A, int lda, float* out, int M, int N, ap_stream
 
 /* ---- Outlook attention core (models/volo.py:83-98: unfold, softmax, attn@v, fold) -------
  * v [B,H,W,C], logits [B*h*w, ldl] with channel = head*81 + p*9 + q (kernel 3, pad 1, stride 2),
- * y [B,H,W,C].  C = heads*hd.                                                               */
+ * y [B,H,W,C].  C = heads*hd.  ldl >= heads*81, a multiple of 8; the logits' columns heads*81 .. ldl-1 may hold anything.
+ * dlogits [B*h*w, ldl] has the logits' leading dimension: its columns heads*81 .. ldl-1 are zeroed.  */
 int ap_outlook_fwd(const ap_bf16* v, const ap_bf16* logits, int ldl, ap_bf16* y,
                    int B, int H, int W, int heads, int hd, float scale, ap_stream_t stream);
 int ap_outlook_bwd(const ap_bf16* v, const ap_bf16* logits, int ldl, const ap_bf16* dy,

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from oracle import ref_cpu as R
+from tests._tilecheck import assert_tiled
 
 pytestmark = pytest.mark.gpu
 TOL_BF16 = 1e-2
@@ -73,14 +74,14 @@ def test_layernorm(ops, rows, C, eps):
     yr = R.layernorm(xr, gr, br, eps)
     yr.backward(dy.double())
     y, mean, rstd = ops.layernorm_fwd(dev(x), dev(g), dev(b), eps)
-    assert rel(y, yr) < TOL_BF16
+    assert_tiled(y, yr, TOL_BF16, "y")
     dg = torch.zeros(C, device="cuda")
     db = torch.zeros(C, device="cuda")
     dx = ops.layernorm_bwd(dev(dy), dev(x), dev(g), mean, rstd, dev(dres), dg, db)
-    assert rel(dx, xr.grad + dres.double()) < TOL_BF16
+    assert_tiled(dx, xr.grad + dres.double(), TOL_BF16, "dx")
     assert rel(dg, gr.grad) < TOL_F32 and rel(db, br.grad) < TOL_F32
     dx2 = ops.layernorm_bwd(dev(dy), dev(x), dev(g), mean, rstd, None, dg, db)
-    assert rel(dx2, xr.grad) < TOL_BF16
+    assert_tiled(dx2, xr.grad, TOL_BF16, "dx without dres")
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 128, 64), (1000, 192, 192), (300, 486, 192), (128, 1152, 384), (77, 1000, 384),
@@ -93,9 +94,9 @@ def test_gemm_nt_plain_and_bias(ops, M, N, K):
     ref = a.double() @ w.double().t()
     out = ops.gemm_nt(dev(a), dev(w))
     assert out.shape == (M, ops.round_up(N, 8))
-    assert rel(out[:, :N], ref) < TOL_BF16
+    assert_tiled(out[:, :N], ref, TOL_BF16, "plain")
     out = ops.gemm_nt(dev(a), dev(w), bias=dev(bias))
-    assert rel(out[:, :N], ref + bias.double()) < TOL_BF16
+    assert_tiled(out[:, :N], ref + bias.double(), TOL_BF16, "bias")
 
 
 @pytest.mark.parametrize("M,N,K", [(392, 576, 192), (128, 1152, 384), (1, 384, 384), (200, 200, 1152), (256, 32, 32),
@@ -113,19 +114,19 @@ def test_gemm_nt_epilogues(ops, M, N, K):
     assert N % 8 == 0
     h = torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
     out = ops.gemm_nt(dev(a), dev(w), bias=dev(bias), gelu=True, preact_out=h)
-    assert rel(h, lin) < TOL_BF16
-    assert rel(out, R.gelu(h.double().cpu())) < TOL_BF16          # activation of the ROUNDED pre-activation
+    assert_tiled(h, lin, TOL_BF16, "pre-activation")
+    assert_tiled(out, R.gelu(h.double().cpu()), TOL_BF16, "gelu")          # activation of the ROUNDED pre-activation
     # residual + row scale (DropPath)
     out = ops.gemm_nt(dev(a), dev(w), bias=dev(bias), row_scale=dev(rs), rows_per_scale=rps, residual=dev(res))
     ref = lin * rs.double().repeat_interleave(rps)[:M, None] + res.double()
-    assert rel(out, ref) < TOL_BF16
+    assert_tiled(out, ref, TOL_BF16, "row scale + residual")
     assert torch.equal(out[:rps].cpu(), res[:rps])               # dropped samples pass the residual through exactly
     # dgelu epilogue
     hh = rnd(M, N, seed=6)
     hr = hh.double().requires_grad_(True)
     R.gelu(hr).backward(torch.ones(M, N, dtype=torch.float64))
     out = ops.gemm_nt(dev(a), dev(w), dgelu_of=dev(hh))
-    assert rel(out, (a.double() @ w.double().t()) * hr.grad) < TOL_BF16
+    assert_tiled(out, (a.double() @ w.double().t()) * hr.grad, TOL_BF16, "dgelu_of")
     # the same pair with the activation DERIVATIVE stored by the forward (gelu = 2) and multiplied in by the backward (mul_by): what the
     # blocks use -- gelu'(h) is all the backward needs of h (autograd of models/volo.py:157)
     gp = torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
@@ -135,7 +136,7 @@ def test_gemm_nt_epilogues(ops, M, N, K):
     assert rel(gp, hb.grad) < TOL_BF16
     assert rel(out2, R.gelu(hb.detach()) * rs.double().repeat_interleave(rps)[:M, None]) < TOL_BF16
     out3 = ops.gemm_nt(dev(a), dev(w), mul_by=gp, row_scale=dev(rs), rows_per_scale=rps)
-    assert rel(out3, (a.double() @ w.double().t()) * gp.double().cpu() * rs.double().repeat_interleave(rps)[:M, None]) < TOL_BF16
+    assert_tiled(out3, (a.double() @ w.double().t()) * gp.double().cpu() * rs.double().repeat_interleave(rps)[:M, None], TOL_BF16, "mul_by")
     # round 5 (ABI 6): the derivative as 8-bit fixed-point codes (gelu = 3 / mul_by8): code = clamp(rint(202 g') + 26, 0, 255) -- EXACT against
     # that formula on the bf16-rounded pre-activation except where fp32 rounding puts 202 g' + 26 within 1e-3 of a half-integer, the
     # output identical to the gelu = 2 launch, and the backward multiplies by (code - 26) / 202
@@ -160,7 +161,7 @@ def test_gemm_nt_epilogues(ops, M, N, K):
     # against the launch's OWN derivative (the gelu = 2 output, a bf16 rounding of the same fp32 value): within half a code + that rounding
     assert float((got - (gp.double().cpu() * ops.GELU_CODE_SCALE + ops.GELU_CODE_ZERO)).abs().max()) <= 0.5 + ops.GELU_CODE_SCALE * 2.0 ** -8
     out5 = ops.gemm_nt(dev(a), dev(w), mul_by=codes, row_scale=dev(rs), rows_per_scale=rps)
-    assert rel(out5, (a.double() @ w.double().t()) * dec * rs.double().repeat_interleave(rps)[:M, None]) < TOL_BF16
+    assert_tiled(out5, (a.double() @ w.double().t()) * dec * rs.double().repeat_interleave(rps)[:M, None], TOL_BF16, "mul_by8")
     with pytest.raises(Exception):
         ops.gemm_nt(dev(a), dev(w), bias=dev(bias), gelu=True, preact_out=gp, preact_grad=2)          # codes need a uint8 tensor
 
@@ -197,7 +198,7 @@ def test_layernorm_bwd_with_the_average_pools_gradient(ops, B, H, W, C):
         return
     assert dx is not None
     ops.layernorm_bwd_reduce_batched(items)
-    assert rel(dx.view(B, H, W, C), want_dx) < TOL_BF16
+    assert_tiled(dx.view(B, H, W, C), want_dx, TOL_BF16, "dx")
     assert rel(dg, g64.grad) < 1e-4 and rel(db, b64.grad) < 1e-4
     # the two launches it replaces
     dy2 = dev(dy).clone()
@@ -222,11 +223,11 @@ def test_gemm_nt_224_row_tiles(ops, M, K):
     lin = a.double() @ w.double().t()
     rsr = rs.double().repeat_interleave(rps)[:M, None]
     da, dw_ = dev(a), dev(w)
-    assert rel(ops.gemm_nt(da, dw_), lin) < TOL_BF16
-    assert rel(ops.gemm_nt(da, dw_, row_scale=dev(rs), rows_per_scale=rps), lin * rsr) < TOL_BF16
-    assert rel(ops.gemm_nt(da, dw_, bias=dev(bias), residual=dev(res)), lin + bias.double() + res.double()) < TOL_BF16
+    assert_tiled(ops.gemm_nt(da, dw_), lin, TOL_BF16, "plain")
+    assert_tiled(ops.gemm_nt(da, dw_, row_scale=dev(rs), rows_per_scale=rps), lin * rsr, TOL_BF16, "row scale")
+    assert_tiled(ops.gemm_nt(da, dw_, bias=dev(bias), residual=dev(res)), lin + bias.double() + res.double(), TOL_BF16, "bias + residual")
     out = ops.gemm_nt(da, dw_, bias=dev(bias), row_scale=dev(rs), rows_per_scale=rps, residual=dev(res))
-    assert rel(out, (lin + bias.double()) * rsr + res.double()) < TOL_BF16
+    assert_tiled(out, (lin + bias.double()) * rsr + res.double(), TOL_BF16, "bias + row scale + residual")
     dropped = (rs == 0).repeat_interleave(rps)[:M]
     assert torch.equal(out.cpu()[dropped], res[dropped])            # dropped samples pass the residual through exactly
 
@@ -245,7 +246,7 @@ def test_gemm_nt_weight_stationary_k192(ops, M, N):
     codes = torch.empty(M, N, device="cuda", dtype=torch.uint8)
     y = ops.gemm_nt(da, dw_, bias=db, gelu=True, preact_out=codes, preact_grad=2)
     h = (a.double() @ w.double().t() + bias.double()).to(torch.bfloat16).double()
-    assert rel(y, F.gelu(h)) < TOL_BF16
+    assert_tiled(y, F.gelu(h), TOL_BF16, "gelu")
     hg = h.clone().requires_grad_(True)
     F.gelu(hg).sum().backward()
     want = torch.clamp(torch.round(hg.grad * ops.GELU_CODE_SCALE) + ops.GELU_CODE_ZERO, 0, 255)
@@ -255,7 +256,7 @@ def test_gemm_nt_weight_stationary_k192(ops, M, N):
     mul = torch.randint(0, 256, (M, N), dtype=torch.uint8, generator=torch.Generator().manual_seed(4))
     dmul = dev(mul)
     d = ops.gemm_nt(da, dw_, mul_by=dmul)
-    assert rel(d, (a.double() @ w.double().t()) * ((mul.double() - ops.GELU_CODE_ZERO) / ops.GELU_CODE_SCALE)) < TOL_BF16
+    assert_tiled(d, (a.double() @ w.double().t()) * ((mul.double() - ops.GELU_CODE_ZERO) / ops.GELU_CODE_SCALE), TOL_BF16, "mul_by8")
     # the same problem in pieces below the kernel's row threshold (-> the 8-phase kernel, unless an environment-switch run has taken it away)
     if os.environ.get("AP_GEMM_8P", "1") == "0":
         return
@@ -379,11 +380,11 @@ def test_gemm_tn_acc(ops, M, N1, N2):
     cs = dev(cs0)
     ops.gemm_tn_acc(dev(a), dev(b), c, colsum=cs)
     ref = c0.double() + a[:, :N1].double().t() @ b[:, :N2].double()
-    assert rel(c, ref) < TOL_F32
+    assert_tiled(c, ref, TOL_F32, "C")
     assert rel(cs, cs0.double() + a[:, :N1].double().sum(0)) < TOL_F32
     c2 = dev(c0)
     ops.gemm_tn_acc(dev(a), dev(b), c2)                      # without the fused bias gradient
-    assert rel(c2, ref) < TOL_F32
+    assert_tiled(c2, ref, TOL_F32, "C without the column sum")
 
 
 def test_gemm_tn_acc_grouped(ops):
@@ -561,10 +562,10 @@ def test_outlook_core(ops, B, H, W, heads):
     yr = R.outlook_core(vr, lr, heads)
     yr.backward(dy.double())
     y = ops.outlook_fwd(dev(v), dev(logits), heads, scale)
-    assert rel(y, yr) < TOL_BF16
+    assert_tiled(y, yr, TOL_BF16, "y")
     dv, dl = ops.outlook_bwd(dev(v), dev(logits), dev(dy), heads, scale)
-    assert rel(dv, vr.grad) < TOL_BF16
-    assert rel(dl[:, :heads * 81], lr.grad.reshape(B * h * w, heads * 81)) < TOL_BF16
+    assert_tiled(dv, vr.grad, TOL_BF16, "dv")
+    assert_tiled(dl[:, :heads * 81], lr.grad.reshape(B * h * w, heads * 81), TOL_BF16, "dlogits")
     if ldl > heads * 81:
         assert float(dl[:, heads * 81:].float().abs().sum()) == 0.0
 
@@ -600,7 +601,7 @@ def test_mhsa(ops, B, N, heads, hd):
     orf = R.mhsa_core(qr, heads)
     orf.backward(do.double().reshape(B, N, C))
     o, lse = ops.mhsa_fwd(dev(qkv), B, N, heads, scale)
-    assert rel(o, orf.reshape(B * N, C)) < TOL_BF16
+    assert_tiled(o, orf.reshape(B * N, C), TOL_BF16, "out")
     q, k, _ = qkv.double().reshape(B, N, 3, heads, hd).permute(2, 0, 3, 1, 4)
     lse_ref = torch.logsumexp(q @ k.transpose(-1, -2) * scale, dim=-1)
     assert float((lse.cpu().double() - lse_ref).abs().max()) < 2e-3
@@ -608,7 +609,7 @@ def test_mhsa(ops, B, N, heads, hd):
     g = qr.grad.reshape(B * N, 3, C)
     d = dqkv.reshape(B * N, 3, C)
     for i, nm in enumerate("qkv"):
-        assert rel(d[:, i], g[:, i]) < 1.5e-2, nm
+        assert_tiled(d[:, i], g[:, i], 1.5e-2, "d" + nm)
 
 
 @pytest.mark.parametrize("B,N,heads,hd", [(2, 197, 12, 32), (3, 65, 2, 32), (4, 17, 1, 32), (2, 785, 16, 48), (3, 197, 3, 64), (2, 50, 2, 48)])
@@ -623,11 +624,11 @@ def test_class_attention(ops, B, N, heads, hd):
     orf = (att @ vv).transpose(1, 2).reshape(B, C)
     orf.backward(do.double())
     o, probs = ops.class_attn_fwd(dev(q), dev(kv), B, N, heads, scale)
-    assert rel(o, orf) < TOL_BF16
+    assert_tiled(o, orf, TOL_BF16, "out")
     assert rel(probs, att.reshape(B, heads, N)) < 1e-3
     dq, dkv = ops.class_attn_bwd(dev(q), dev(kv), probs, dev(do), B, N, heads, scale)
-    assert rel(dq, qr.grad) < TOL_BF16
-    assert rel(dkv, kvr.grad.reshape(B * N, 2 * C)) < TOL_BF16
+    assert_tiled(dq, qr.grad, TOL_BF16, "dq")
+    assert_tiled(dkv, kvr.grad.reshape(B * N, 2 * C), TOL_BF16, "dkv")
 
 
 def test_mix_token_swap_exact(ops):
@@ -1191,22 +1192,22 @@ def test_gemm_nt_fp8_vs_dequantised_reference(M, N, K):
     h = torch.empty(M, ops.round_up(N, 8), dtype=torch.bfloat16, device="cuda")
     y = ops.gemm_nt_fp8(a8, w8, dq_a, dq_w, bias=bias, gelu=True, preact_out=h)[:, :N]
     pre = a_dq @ w_dq.t() + bias
-    assert rel(h[:, :N], pre) < 4e-3
-    assert rel(y, F.gelu(pre.to(torch.bfloat16).float())) < 4e-3
+    assert_tiled(h[:, :N], pre, 4e-3, "pre-activation")
+    assert_tiled(y, F.gelu(pre.to(torch.bfloat16).float()), 4e-3, "gelu")
     y2 = ops.gemm_nt_fp8(a8, w8, dq_a, dq_w, residual=res)[:, :N]
-    assert rel(y2, a_dq @ w_dq.t() + res[:, :N].float()) < 4e-3
-    assert rel(ops.gemm_nt_fp8(a8, w8, dq_a, dq_w)[:, :N], a.float() @ w.float().t()) < 6e-2
+    assert_tiled(y2, a_dq @ w_dq.t() + res[:, :N].float(), 4e-3, "residual")
+    assert_tiled(ops.gemm_nt_fp8(a8, w8, dq_a, dq_w)[:, :N], a.float() @ w.float().t(), 6e-2, "against the un-quantised product")
     # bias + DropPath row scale + residual (proj / fc2), and GELU with the stored derivative + row scale (fc1)
     rps = max(1, M // 2)
     rs = torch.tensor([0.0, 1.0 / 0.9, 1.0 / 0.9], device="cuda")
     y3 = ops.gemm_nt_fp8(a8, w8, dq_a, dq_w, bias=bias, row_scale=rs, rows_per_scale=rps, residual=res)[:, :N]
-    assert rel(y3, pre * rs.repeat_interleave(rps)[:M, None] + res[:, :N].float()) < 4e-3
+    assert_tiled(y3, pre * rs.repeat_interleave(rps)[:M, None] + res[:, :N].float(), 4e-3, "bias + row scale + residual")
     gp = torch.empty_like(h)
     y4 = ops.gemm_nt_fp8(a8, w8, dq_a, dq_w, bias=bias, gelu=True, preact_out=gp, preact_grad=True, row_scale=rs, rows_per_scale=rps)[:, :N]
     hb = pre.to(torch.bfloat16).float().requires_grad_(True)
     F.gelu(hb).sum().backward()
     assert rel(gp[:, :N], hb.grad) < 4e-3
-    assert rel(y4, F.gelu(hb.detach()) * rs.repeat_interleave(rps)[:M, None]) < 4e-3
+    assert_tiled(y4, F.gelu(hb.detach()) * rs.repeat_interleave(rps)[:M, None], 4e-3, "gelu + row scale")
     if ops.gemm_nt_fp8_emits(M, N, K):
         # the GELU output a second time as e4m3 (the operand of the next fp8 GEMM): bit-equal to the quantiser run on the bf16 output
         qs, qa, qa_ref = torch.tensor([93.0], device="cuda"), torch.zeros(1, device="cuda"), torch.zeros(1, device="cuda")
