@@ -164,6 +164,10 @@ _SIGNATURES["ap_classify_stats"] = (_I, [_P, _I, _I, _P, _P, _P, _L, _P])
 _SIGNATURES["ap_input_prep"] = (_I, [POINTER(InputPrepArgs), _P])
 _SIGNATURES["ap_calib_copy"] = (_I, [_P, _P, _L, _P])
 _SIGNATURES["ap_calib_mfma"] = (_I, [_P, _P, _I, _P])
+# non-finite gradient guard (csrc/optim.hip): ap_grad_health(g, n, seg_off, n_seg, seg_sumsq, seg_nonfinite, state, beta1, beta2, ws, ws_bytes, stream)
+_SIGNATURES["ap_grad_health_workspace"] = (ctypes.c_size_t, [_L, _I])
+_SIGNATURES["ap_grad_health"] = (_I, [_P, _L, _P, _I, _P, _P, _P, _F, _F, _P, ctypes.c_size_t, _P])
+_SIGNATURES["ap_adamw_ema_step_guarded"] = (_I, _SIGNATURES["ap_adamw_ema_step"][1][:-1] + [_P, _P])
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 EXPECTED_ABI = 7                     # ap_abi_version() of the library these ctypes Structures mirror (include/autoprog_hip.h)

@@ -17,12 +17,22 @@ struct AdamArgs {
     float* ema[4];
 };
 
+// Guarded arguments (ap_adamw_ema_step_guarded): the bias corrections and the skip decision come from the ap_guard_state that
+// ap_grad_health committed for this step.  A skipped step (a non-finite gradient element) reads neither g, m nor v and writes neither
+// p, m, v nor p16; the EMA copies still take their lerp towards the unchanged parameters (the reference updates its ModelEma list whether
+// or not apex skipped the step, main_prog.py:1030-1033).  With plain AdamArgs `skip` is a constant and the kernel is the one it was.
+struct AdamGuardArgs : AdamArgs { const ap_guard_state* guard; };
+
+template <class Args>
 __global__ void __launch_bounds__(256)
 k_adamw_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-            const unsigned char* __restrict__ wd_mask, int64_t n, AdamArgs a, bf16_t* __restrict__ p16) {
+            const unsigned char* __restrict__ wd_mask, int64_t n, Args a, bf16_t* __restrict__ p16) {
+    constexpr bool GUARD = !__is_same(Args, AdamArgs);
     const int64_t nv = n >> 2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     if (a.step_dev) { a.lr = a.step_dev[0]; a.bc1 = a.step_dev[1]; a.bc2_sqrt = a.step_dev[2]; }
+    bool skip = false;
+    if constexpr (GUARD) { skip = a.guard->nonfinite != 0; a.bc1 = a.guard->bc1; a.bc2_sqrt = a.guard->bc2_sqrt; }
     const float step_size = a.lr / a.bc1;
     // gradient clipping folded into the update (prog/scaler.py:60-68 -> timm dispatch_clip_grad, main_prog.py:1019-1027):
     // mode 'norm' = torch.nn.utils.clip_grad_norm_: coef = min(1, max_norm / (||g|| + 1e-6)) with ||g|| the norm of the MEAN gradient
@@ -35,27 +45,29 @@ k_adamw_ema(float* __restrict__ p, const float* __restrict__ g, float* __restric
     const float cv = a.clip_value;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
         float4 pp = reinterpret_cast<float4*>(p)[i];
-        float4 gg = reinterpret_cast<const float4*>(g)[i];
-        gg.x *= gs; gg.y *= gs; gg.z *= gs; gg.w *= gs;
-        if (cv > 0.f) { gg.x = fminf(fmaxf(gg.x, -cv), cv); gg.y = fminf(fmaxf(gg.y, -cv), cv); gg.z = fminf(fmaxf(gg.z, -cv), cv); gg.w = fminf(fmaxf(gg.w, -cv), cv); }
-        float4 mm = reinterpret_cast<float4*>(m)[i];
-        float4 vv = reinterpret_cast<float4*>(v)[i];
-        const uchar4 wm = reinterpret_cast<const uchar4*>(wd_mask)[i];
-        float* P = &pp.x; const float* G = &gg.x; float* M = &mm.x; float* V = &vv.x;
-        const unsigned char W[4] = {wm.x, wm.y, wm.z, wm.w};
+        if (!skip) {
+            float4 gg = reinterpret_cast<const float4*>(g)[i];
+            gg.x *= gs; gg.y *= gs; gg.z *= gs; gg.w *= gs;
+            if (cv > 0.f) { gg.x = fminf(fmaxf(gg.x, -cv), cv); gg.y = fminf(fmaxf(gg.y, -cv), cv); gg.z = fminf(fmaxf(gg.z, -cv), cv); gg.w = fminf(fmaxf(gg.w, -cv), cv); }
+            float4 mm = reinterpret_cast<float4*>(m)[i];
+            float4 vv = reinterpret_cast<float4*>(v)[i];
+            const uchar4 wm = reinterpret_cast<const uchar4*>(wd_mask)[i];
+            float* P = &pp.x; const float* G = &gg.x; float* M = &mm.x; float* V = &vv.x;
+            const unsigned char W[4] = {wm.x, wm.y, wm.z, wm.w};
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float x = P[k];
-            if (W[k]) x *= (1.0f - a.lr * a.wd);                         // decoupled weight decay (torch AdamW order)
-            M[k] = a.beta1 * M[k] + (1.0f - a.beta1) * G[k];
-            V[k] = a.beta2 * V[k] + (1.0f - a.beta2) * G[k] * G[k];
-            const float denom = sqrtf(V[k]) / a.bc2_sqrt + a.eps;
-            P[k] = x - step_size * (M[k] / denom);
+            for (int k = 0; k < 4; ++k) {
+                float x = P[k];
+                if (W[k]) x *= (1.0f - a.lr * a.wd);                         // decoupled weight decay (torch AdamW order)
+                M[k] = a.beta1 * M[k] + (1.0f - a.beta1) * G[k];
+                V[k] = a.beta2 * V[k] + (1.0f - a.beta2) * G[k] * G[k];
+                const float denom = sqrtf(V[k]) / a.bc2_sqrt + a.eps;
+                P[k] = x - step_size * (M[k] / denom);
+            }
+            reinterpret_cast<float4*>(p)[i] = pp;
+            if (p16) { u32x2 o; o[0] = pack_bf2(pp.x, pp.y); o[1] = pack_bf2(pp.z, pp.w); reinterpret_cast<u32x2*>(p16)[i] = o; }
+            reinterpret_cast<float4*>(m)[i] = mm;
+            reinterpret_cast<float4*>(v)[i] = vv;
         }
-        reinterpret_cast<float4*>(p)[i] = pp;
-        if (p16) { u32x2 o; o[0] = pack_bf2(pp.x, pp.y); o[1] = pack_bf2(pp.z, pp.w); reinterpret_cast<u32x2*>(p16)[i] = o; }
-        reinterpret_cast<float4*>(m)[i] = mm;
-        reinterpret_cast<float4*>(v)[i] = vv;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             if (e < a.n_ema) {
@@ -113,14 +125,15 @@ extern "C" int ap_sumsq_f32(const float* x, int64_t n, float* out, void* workspa
     return ap_check_launch();
 }
 
-extern "C" int ap_adamw_ema_step(float* p, const float* g, float* m, float* v, const unsigned char* wd_mask, int64_t n,
-                                 float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
-                                 const float* gnorm_sq, float max_norm, float clip_value, const float* step_scalars_dev,
-                                 float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, ap_stream_t stream) {
+// the argument checks and the launch both entry points share; `guard` selects the guarded instantiation
+static int adamw_ema_launch(float* p, const float* g, float* m, float* v, const unsigned char* wd_mask, int64_t n,
+                            float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                            const float* gnorm_sq, float max_norm, float clip_value, const float* step_scalars_dev,
+                            float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, const ap_guard_state* guard, ap_stream_t stream) {
     if (!p || !g || !m || !v || !wd_mask) return AP_ERR_NULL;
     if (n <= 0 || (n & 3) || n_ema < 0 || n_ema > 4 || step < 1) return AP_ERR_SHAPE;
     if (gnorm_sq && !(max_norm > 0.f)) return AP_ERR_SHAPE;
-    AdamArgs a;
+    AdamGuardArgs a;
     a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay; a.gscale = grad_scale;
     a.gnorm_sq = gnorm_sq; a.max_norm = max_norm; a.clip_value = clip_value > 0.f ? clip_value : 0.f; a.step_dev = step_scalars_dev;
     // (in double from the float arguments, rounded once: graph.StepScalars.set_adam forms the SAME two numbers on the host, so a step
@@ -129,10 +142,180 @@ extern "C" int ap_adamw_ema_step(float* p, const float* g, float* m, float* v, c
     a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     a.n_ema = n_ema;
     for (int e = 0; e < 4; ++e) { a.ema[e] = (e < n_ema) ? ema[e] : nullptr; a.decay[e] = (e < n_ema) ? ema_decay[e] : 0.f; if (e < n_ema && !ema[e]) return AP_ERR_NULL; }
+    a.guard = guard;
     int64_t grid = (n / 4 + 255) / 256;
     if (grid > 256 * 16) grid = 256 * 16;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_adamw_ema, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, wd_mask, n, a, p_bf16);
+    if (guard) hipLaunchKernelGGL(k_adamw_ema<AdamGuardArgs>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, wd_mask, n, a, p_bf16);
+    else hipLaunchKernelGGL(k_adamw_ema<AdamArgs>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, wd_mask, n, static_cast<const AdamArgs&>(a), p_bf16);
+    return ap_check_launch();
+}
+
+extern "C" int ap_adamw_ema_step(float* p, const float* g, float* m, float* v, const unsigned char* wd_mask, int64_t n,
+                                 float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                                 const float* gnorm_sq, float max_norm, float clip_value, const float* step_scalars_dev,
+                                 float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, ap_stream_t stream) {
+    return adamw_ema_launch(p, g, m, v, wd_mask, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, gnorm_sq, max_norm, clip_value,
+                            step_scalars_dev, ema, ema_decay, n_ema, p_bf16, nullptr, stream);
+}
+
+// the bias corrections of the guarded step are the ones ap_grad_health wrote for t = applied: `step` is only checked (>= 1), and of
+// step_scalars_dev only the learning rate is used
+extern "C" int ap_adamw_ema_step_guarded(float* p, const float* g, float* m, float* v, const unsigned char* wd_mask, int64_t n,
+                                         float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                                         const float* gnorm_sq, float max_norm, float clip_value, const float* step_scalars_dev,
+                                         float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, const ap_guard_state* guard,
+                                         ap_stream_t stream) {
+    if (!guard) return AP_ERR_NULL;
+    return adamw_ema_launch(p, g, m, v, wd_mask, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, gnorm_sq, max_norm, clip_value,
+                            step_scalars_dev, ema, ema_decay, n_ema, p_bf16, guard, stream);
+}
+
+// ---- gradient health (ap_grad_health): per parameter tensor the sum of squares of the finite elements (fp64) and the number of
+// non-finite ones, in one pass over the gradient slab, and the skip decision of the guarded step.  The slab is cut into chunks of
+// GH_CHUNK elements; a workgroup owns a contiguous run of them (all runs equally long), finds the segment its first chunk starts in by
+// one binary search and from there only steps forward.  A chunk that lies inside one segment -- nearly all of them -- is 8 independent
+// 16-byte loads per lane and one workgroup reduction.  A chunk that meets segment bounds hands its segments to its four waves in turn,
+// each a strided sweep and a wave reduction.  The partial of (chunk c, segment s) goes to slot c + s of the workspace: c and s both
+// only grow along the slab, so the slot is unique, and n_chunks + n_seg slots hold every pair.  k_grad_health_final adds a segment's
+// slots in chunk order (one wave per segment, fixed tree): no floating-point atomics, the same bits every run.  x * x is exact in fp64,
+// so only the order of the additions separates the result from a serial fp64 loop.  The step's total is an INTEGER: the workgroups of
+// the second kernel add theirs with integer atomics and the one that draws the last ticket commits the step.
+constexpr int GH_CHUNK = 8192;          // 256 lanes x 8 float4
+constexpr int GH_MAX_GRID = 2048;       // 8 workgroups on each of 256 CUs
+
+__device__ __forceinline__ void gh_add(float x, double& s, int& c) {
+    const bool bad = (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u;          // exponent all ones: +-inf, NaN
+    const double d = bad ? 0.0 : (double)x;
+    s = fma(d, d, s);
+    c += bad ? 1 : 0;
+}
+
+__device__ __forceinline__ void gh_wave_reduce(double& s, int& c) {
+    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o, 64); c += __shfl_xor(c, o, 64); }
+}
+
+__global__ void __launch_bounds__(256)
+k_grad_health(const float* __restrict__ g, int64_t n, const int64_t* __restrict__ seg_off, int n_seg, int64_t n_chunks, int per_wg,
+              double* __restrict__ part_s, int* __restrict__ part_c, int* __restrict__ ticket) {
+    __shared__ double red_s[4];
+    __shared__ int red_c[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { ticket[0] = 0; ticket[1] = 0; }  // (the second kernel's total and ticket counter)
+    const int64_t first = (int64_t)blockIdx.x * per_wg;
+    const int64_t last = (first + per_wg < n_chunks) ? first + per_wg : n_chunks;
+    int lo = 0, hi = n_seg - 1;                                                  // the last segment that starts at or before the run
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (seg_off[mid] <= first * GH_CHUNK) lo = mid; else hi = mid - 1; }
+    int s0 = lo;
+    for (int64_t c = first; c < last; ++c) {
+        const int64_t c0 = c * GH_CHUNK;
+        const int64_t c1 = (c0 + GH_CHUNK < n) ? c0 + GH_CHUNK : n;
+        while (s0 + 1 < n_seg && seg_off[s0 + 1] <= c0) ++s0;                    // ... at or before this chunk
+        if (seg_off[s0 + 1] >= c1) {                                             // the whole chunk lies in segment s0
+            const int len = (int)(c1 - c0), nv = len >> 2;                       // (c0 is a multiple of 4, the slab 16-byte aligned)
+            const float4* gv = reinterpret_cast<const float4*>(g + c0);
+            float4 x[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { const int i = threadIdx.x + 256 * k; x[k] = (i < nv) ? gv[i] : make_float4(0.f, 0.f, 0.f, 0.f); }
+            double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+            int cnt = 0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { gh_add(x[k].x, a0, cnt); gh_add(x[k].y, a1, cnt); gh_add(x[k].z, a2, cnt); gh_add(x[k].w, a3, cnt); }
+            double s = (a0 + a1) + (a2 + a3);
+            if ((int)threadIdx.x < (len & 3)) gh_add(g[c0 + (nv << 2) + threadIdx.x], s, cnt);      // (the slab's n % 4 tail)
+            gh_wave_reduce(s, cnt);
+            if (lane == 0) { red_s[wave] = s; red_c[wave] = cnt; }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                part_s[c + s0] = ((red_s[0] + red_s[1]) + red_s[2]) + red_s[3];
+                part_c[c + s0] = red_c[0] + red_c[1] + red_c[2] + red_c[3];
+            }
+            __syncthreads();
+        } else {
+            for (int s = s0 + wave; s < n_seg; s += 4) {
+                const int64_t b = seg_off[s];
+                if (b >= c1) break;
+                const int64_t e = seg_off[s + 1];
+                const int64_t from = b > c0 ? b : c0, to = e < c1 ? e : c1;      // (clamped to the chunk: a malformed table reads nothing outside the slab)
+                if (to <= from) continue;
+                double acc = 0.0;
+                int cnt = 0;
+#pragma unroll 4
+                for (int64_t i = from + lane; i < to; i += 64) gh_add(g[i], acc, cnt);
+                gh_wave_reduce(acc, cnt);
+                if (lane == 0) { part_s[c + s] = acc; part_c[c + s] = cnt; }
+            }
+        }
+    }
+}
+
+// wave w of the grid adds the slots of segment w in chunk order; a workgroup then adds its count to the step's total and draws a ticket,
+// and the workgroup with the last ticket -- every other one's total is in by then -- commits the step
+__global__ void __launch_bounds__(256)
+k_grad_health_final(const double* __restrict__ part_s, const int* __restrict__ part_c, const int64_t* __restrict__ seg_off, int n_seg,
+                    int64_t n_chunks, double* __restrict__ seg_sumsq, int* __restrict__ seg_nonfinite, ap_guard_state* __restrict__ st,
+                    float beta1, float beta2, int* __restrict__ ticket) {
+    __shared__ int tot[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int s = blockIdx.x * 4 + wave;
+    int cnt = 0;
+    if (s < n_seg) {
+        const int64_t b = seg_off[s], e = seg_off[s + 1];
+        double acc = 0.0;
+        if (e > b) {
+            int64_t cl = b / GH_CHUNK, ch = (e - 1) / GH_CHUNK;
+            if (cl < 0) cl = 0;
+            if (ch > n_chunks - 1) ch = n_chunks - 1;
+            for (int64_t c = cl + lane; c <= ch; c += 64) { acc += part_s[c + s]; cnt += part_c[c + s]; }
+        }
+        gh_wave_reduce(acc, cnt);
+        if (lane == 0) { seg_sumsq[s] = acc; seg_nonfinite[s] = cnt; }
+    }
+    if (lane == 0) tot[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&ticket[0], tot[0] + tot[1] + tot[2] + tot[3]);
+        __threadfence();
+        if (atomicAdd(&ticket[1], 1) == (int)gridDim.x - 1) {
+            __threadfence();
+            const int total = atomicAdd(&ticket[0], 0);
+            int applied = st->applied;
+            if (total == 0) { applied += 1; st->applied = applied; st->consecutive = 0; }
+            else { st->skipped += 1; st->consecutive += 1; }
+            st->nonfinite = total;
+            // the expressions of ap_adamw_ema_step for t = applied (a skipped step's values are not used; t >= 1 keeps them finite)
+            const double t = (double)(applied > 0 ? applied : 1);
+            st->bc1 = (float)(1.0 - pow((double)beta1, t));
+            st->bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, t));
+        }
+    }
+}
+
+static int64_t gh_chunks(int64_t n) { return (n + GH_CHUNK - 1) / GH_CHUNK; }
+
+// workspace: n_chunks + n_seg fp64 slots, as many int32 slots, two int32 counters
+extern "C" size_t ap_grad_health_workspace(int64_t n, int n_seg) {
+    if (n <= 0 || n_seg <= 0) return 0;
+    const size_t slots = (size_t)gh_chunks(n) + (size_t)n_seg;
+    return (slots * (sizeof(double) + sizeof(int)) + 2 * sizeof(int) + 15) & ~(size_t)15;
+}
+
+extern "C" int ap_grad_health(const float* g, int64_t n, const int64_t* seg_off, int n_seg, double* seg_sumsq, int* seg_nonfinite,
+                              ap_guard_state* state, float beta1, float beta2, void* workspace, size_t ws_bytes, ap_stream_t stream) {
+    if (!g || !seg_off || !seg_sumsq || !seg_nonfinite || !state || !workspace) return AP_ERR_NULL;
+    if (n <= 0 || n_seg <= 0 || ws_bytes < ap_grad_health_workspace(n, n_seg) || ((uintptr_t)g & 15) || ((uintptr_t)workspace & 7)) return AP_ERR_SHAPE;
+    const int64_t chunks = gh_chunks(n);
+    if (chunks > (int64_t)GH_MAX_GRID * 0x7fffffff / 2) return AP_ERR_SHAPE;
+    const size_t slots = (size_t)chunks + (size_t)n_seg;
+    double* part_s = static_cast<double*>(workspace);
+    int* part_c = reinterpret_cast<int*>(part_s + slots);
+    int* ticket = part_c + slots;
+    const int per_wg = (int)((chunks + GH_MAX_GRID - 1) / GH_MAX_GRID);         // equally long runs: no workgroup does one chunk more than the rest
+    const int64_t grid = (chunks + per_wg - 1) / per_wg;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_grad_health, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, g, n, seg_off, n_seg, chunks, per_wg, part_s, part_c, ticket);
+    hipLaunchKernelGGL(k_grad_health_final, dim3((unsigned)((n_seg + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const double*)part_s, (const int*)part_c,
+                       seg_off, n_seg, chunks, seg_sumsq, seg_nonfinite, state, beta1, beta2, ticket);
     return ap_check_launch();
 }
 

@@ -109,11 +109,14 @@ class DeviceBox:
 
 
 class GraphedStep:
-    def __init__(self, model, loss_fn, reducer, opt, images, target, clip_grad=None, clip_mode="norm"):
+    def __init__(self, model, loss_fn, reducer, opt, images, target, clip_grad=None, clip_mode="norm", skip_nonfinite=False):
+        """skip_nonfinite: FlatAdamWEma.step's flag.  The guarded launch sequence reads its decision, its counters and Adam's step number
+        from device memory (ap_guard_state), so a replay skips or applies like an eager step and needs no further per-step copy."""
         if getattr(reducer, "world", 1) > 1:
             raise ValueError("GraphedStep: single-rank only (the gradient exchange is not captured)")
         self.model, self.loss_fn, self.reducer, self.opt = model, loss_fn, reducer, opt
         self.clip_grad, self.clip_mode = clip_grad, clip_mode
+        self.skip_nonfinite = bool(skip_nonfinite)
         # a data.PreparedBatch in place of the images: a static uint8 buffer and a static copy of the step's parameter block (mix mode, lam,
         # CutMix box, noise key, erase records), refreshed by ONE device copy in front of every replay; the loss reads lam from that block
         self.images = _clone_images(images)
@@ -154,11 +157,16 @@ class GraphedStep:
         loss = self.loss_fn(self.model(self.images), self.target)
         loss.backward()
         self.reducer.finish()
-        self.opt.step(clip_grad=self.clip_grad, clip_mode=self.clip_mode, scalars=self.scalars)
+        if self.skip_nonfinite:
+            self.opt.step(clip_grad=self.clip_grad, clip_mode=self.clip_mode, scalars=self.scalars, skip_nonfinite=True)
+        else:
+            self.opt.step(clip_grad=self.clip_grad, clip_mode=self.clip_mode, scalars=self.scalars)
         return loss
 
     def capture(self, warmup=3):
         self.model.step_scalars = self.scalars
+        if self.skip_nonfinite:
+            self.opt._guard_workspace(self.images.device)         # (the same rule for the guard's table, outputs, record and workspace)
         if self.clip_grad is not None and float(self.clip_grad) > 0 and self.clip_mode == "norm":
             self.opt._clip_workspace(self.images.device)          # (never first allocated inside the capture: optim.FlatAdamWEma._clip_workspace)
         s = torch.cuda.Stream()

@@ -1137,3 +1137,33 @@ def conv7_s2d_wgrad(xs, dz, dw):
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=xs.device)
     check(lib.ap_conv7_s2d_wgrad(xs.data_ptr(), dz.data_ptr(), dw.data_ptr(), B, H, W, ws.data_ptr(), ws_bytes, _stream()), "ap_conv7_s2d_wgrad")
     return dw
+
+
+def sumsq(x, out=None, workspace=None):
+    """sum of squares of a flat fp32 slab (ap_sumsq_f32) -> fp32 device scalar [1]; `out` / `workspace` (fp64, ap_sumsq_workspace bytes) are
+    allocated when not given"""
+    _req(x, torch.float32, "x")
+    out = torch.empty(1, dtype=torch.float32, device=x.device) if out is None else _req(out, torch.float32, "out")
+    ws = torch.empty(lib.ap_sumsq_workspace() // 8, dtype=torch.float64, device=x.device) if workspace is None else _req(workspace, torch.float64, "workspace")
+    check(lib.ap_sumsq_f32(x.data_ptr(), x.numel(), out.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()), "ap_sumsq_f32")
+    return out
+
+
+def grad_health_workspace(n, n_seg):
+    """bytes of workspace ap_grad_health needs for a slab of n elements in n_seg segments"""
+    return int(lib.ap_grad_health_workspace(int(n), int(n_seg)))
+
+
+def grad_health(g, seg_off, seg_sumsq, seg_nonfinite, state, workspace, beta1=0.9, beta2=0.999):
+    """ap_grad_health: one pass over the fp32 gradient slab `g` against the device table `seg_off` (int64 [n_seg + 1], ascending from 0 to
+    g.numel()).  Writes seg_sumsq (fp64 [n_seg]: sum of x^2 over the finite elements of each segment), seg_nonfinite (int32 [n_seg]: the
+    inf / NaN elements) and commits the step into `state` (int32 [8], ap_guard_state: nonfinite, applied, skipped, consecutive, then the
+    two bias corrections as fp32).  Every buffer is the caller's (workspace: fp64, grad_health_workspace bytes): nothing is allocated."""
+    _req(g, torch.float32, "g"); _req(seg_off, torch.int64, "seg_off"); _req(seg_sumsq, torch.float64, "seg_sumsq")
+    _req(seg_nonfinite, torch.int32, "seg_nonfinite"); _req(state, torch.int32, "state"); _req(workspace, torch.float64, "workspace")
+    n_seg = seg_off.numel() - 1
+    if n_seg < 1 or seg_sumsq.numel() != n_seg or seg_nonfinite.numel() != n_seg or state.numel() != 8:
+        raise AutoProgHipError("grad_health: a table of n_seg + 1 bounds, n_seg sums, n_seg counts and a state of 8 words")
+    check(lib.ap_grad_health(g.data_ptr(), g.numel(), seg_off.data_ptr(), n_seg, seg_sumsq.data_ptr(), seg_nonfinite.data_ptr(), state.data_ptr(),
+                             float(beta1), float(beta2), workspace.data_ptr(), workspace.numel() * 8, _stream()), "ap_grad_health")
+    return seg_sumsq, seg_nonfinite

@@ -14,6 +14,27 @@ from ._lib import check, lib
 from . import ops
 
 
+def grad_segments(reducer, model=None):
+    """the segment table of the gradient health pass (ap_grad_health): one segment per parameter tensor of the reducer's slab, in slab
+    order -- the reversed parameter order (dist.GradientBucketReducer) -- read from where each gradient view sits, not from an assumed
+    order.  -> (offsets, names): offsets has one entry more than there are tensors, ascending from 0 to the slab's length; names[i] is the
+    name `model.named_parameters()` gives tensor i (a shared parameter appears once, under its first name; "" without a model).
+    Raises ValueError when the gradient views do not tile the slab exactly once."""
+    flat = reducer.flat
+    base, total = flat.data_ptr(), flat.numel()
+    names = {id(p): n for n, p in model.named_parameters()} if model is not None else {}
+    items = sorted(((p.grad.data_ptr() - base) // flat.element_size(), p.numel(), names.get(id(p), "")) for p in reducer.params)
+    offsets, out_names = [0], []
+    for off, n, name in items:
+        if off != offsets[-1]:
+            raise ValueError("grad_segments: the gradient of %r starts at %d, the slab is covered up to %d" % (name, off, offsets[-1]))
+        offsets.append(off + n)
+        out_names.append(name)
+    if offsets[-1] != total:
+        raise ValueError("grad_segments: the gradients cover %d of the slab's %d elements" % (offsets[-1], total))
+    return offsets, out_names
+
+
 class FlatAdamWEma:
     def __init__(self, model, reducer, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, ema_decays=()):
         assert len(ema_decays) <= 4
@@ -81,6 +102,7 @@ class FlatAdamWEma:
         self.ema_buffers = [[b.detach().clone() for b in self._buffers] for _ in self.ema_decays]
         # model.load_state_dict() copies INTO the slab views (pointers unchanged): re-derive the bf16 copies afterwards
         self._load_hook = model.register_load_state_dict_post_hook(lambda module, incompatible: self.resync())
+        self._guard = None                                       # the non-finite guard's device buffers (_guard_workspace)
 
     # ------------------------------------------------------------------ properties kept for callers of the round-1 API
     @property
@@ -117,6 +139,8 @@ class FlatAdamWEma:
                 self.m.zero_()
                 self.v.zero_()
                 self.step_count = 0
+                if self._guard is not None:
+                    self._guard["state"].zero_()                 # applied / skipped / consecutive restart with the optimizer
         self._stamp_versions()
         from . import functional
         functional._WeightBank.generation += 1
@@ -136,7 +160,48 @@ class FlatAdamWEma:
             self._sumsq_ws = torch.empty(lib.ap_sumsq_workspace() // 8, dtype=torch.float64, device=device)
             self._gnorm_sq = torch.zeros(1, dtype=torch.float32, device=device)
 
-    def step(self, clip_grad=None, clip_mode="norm", scalars=None):
+    def _guard_workspace(self, device):
+        """the buffers of the non-finite guard, allocated once and OUTSIDE any stream capture (see _clip_workspace; GraphedStep.capture()
+        calls this first): the segment table, ONE buffer holding the per-tensor sums of squares (fp64) and non-finite counts (int32) --
+        one read-back for grad_health() --, the ap_guard_state record and the pass's workspace.  The record's applied count starts at
+        `step_count`: a run that turns the guard on after a resume continues Adam's bias corrections where they were."""
+        if self._guard is None:
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FlatAdamWEma: the guard's buffers must exist before a step is captured (call _guard_workspace first)")
+            offsets, names = grad_segments(self.reducer, self.model)
+            n, n_seg = offsets[-1], len(names)
+            out = torch.zeros(12 * n_seg, dtype=torch.uint8, device=device)
+            state = torch.zeros(8, dtype=torch.int32, device=device)
+            state[1] = int(self.step_count)
+            ws_bytes = int(lib.ap_grad_health_workspace(n, n_seg))
+            self._guard = {"names": names, "n": n, "n_seg": n_seg, "gscale": 1.0, "used": False,
+                           "table": torch.tensor(offsets, dtype=torch.int64).to(device), "out": out,
+                           "sumsq": out[:8 * n_seg].view(torch.float64), "count": out[8 * n_seg:].view(torch.int32), "state": state,
+                           "ws": torch.empty(ws_bytes // 8, dtype=torch.float64, device=device), "ws_bytes": ws_bytes}
+        return self._guard
+
+    def guard_counts(self):
+        """{"applied", "skipped", "consecutive"} of the guarded steps so far: optimizer updates made, steps skipped for a non-finite
+        gradient, and the length of the current run of skipped steps.  The counters live on the device; this is ONE read-back."""
+        if self._guard is None:
+            return {"applied": int(self.step_count), "skipped": 0, "consecutive": 0}
+        st = self._guard["state"].cpu()
+        return {"applied": int(st[1]), "skipped": int(st[2]), "consecutive": int(st[3])}
+
+    def grad_health(self):
+        """the last guarded step's gradient, tensor by tensor in slab order: [(parameter name, norm of the MEAN gradient over the tensor's
+        finite elements, number of non-finite elements)].  The norms carry the step's gradient scale (1/world under a deferred mean) as
+        `last_grad_norm` does.  ONE read-back."""
+        if self._guard is None or not self._guard["used"]:
+            raise RuntimeError("FlatAdamWEma.grad_health: no step(skip_nonfinite=True) has run yet")
+        gd = self._guard
+        host = gd["out"].cpu()
+        n_seg = gd["n_seg"]
+        sumsq = host[:8 * n_seg].view(torch.float64).sqrt().mul_(gd["gscale"]).tolist()
+        count = host[8 * n_seg:].view(torch.int32).tolist()
+        return list(zip(gd["names"], sumsq, count))
+
+    def step(self, clip_grad=None, clip_mode="norm", scalars=None, skip_nonfinite=False):
         """one AdamW + EMA update from the gradient slab.  clip_grad / clip_mode: the reference's `--clip-grad` / `--clip-mode`
         (main_prog.py:129-132; prog/scaler.py:60-68 calls timm's dispatch_clip_grad between backward and optimizer.step()):
           'norm'  -- torch.nn.utils.clip_grad_norm_(parameters, clip_grad): ONE pass over the flat slab for the global norm
@@ -146,14 +211,30 @@ class FlatAdamWEma:
         1/world factor is applied first -- clipping the slab from outside before step() would be off by `world`.
         `last_grad_norm` (device scalar, 'norm' mode) is the norm of the mean gradient before clipping.
         scalars: graph.StepScalars -- the learning rate and Adam's bias corrections are read from device memory (the caller refreshed
-        them for this step): nothing in the launch changes from step to step, the step can be replayed from a HIP graph."""
-        self.step_count += 1
+        them for this step): nothing in the launch changes from step to step, the step can be replayed from a HIP graph.
+        skip_nonfinite: the step contract of the reference's apex loss scaler (prog/scaler.py:20-26) without the scaler: one extra pass over
+        the gradient slab (ap_grad_health) counts the inf / NaN elements per parameter tensor, and when there is one the update leaves
+        the parameters, both Adam moments and the bf16 weight copies untouched; the EMA copies and the BatchNorm buffer averages still
+        move, as the reference's ModelEma.update does after a skipped step (main_prog.py:1030-1033).  The decision, the counters and
+        Adam's step number t (the APPLIED steps, for the bias corrections) stay on the device: nothing is read back, a replayed graph
+        skips like an eager step.  `step_count` keeps counting calls; guard_counts() / grad_health() report.  `last_grad_norm` of a
+        skipped step is non-finite (it is the norm of the whole slab).  Use the flag for every step of a run or for none: an unguarded
+        step takes t from `step_count`."""
         g = self.reducer.flat
+        gd = self._guard_workspace(g.device) if skip_nonfinite else None     # (before the count moves: the record starts at the steps made so far)
+        self.step_count += 1
+        if skip_nonfinite:                                   # (on the slab itself: the true length, a padded copy's tail never counts)
+            check(lib.ap_grad_health(g.data_ptr(), gd["n"], gd["table"].data_ptr(), gd["n_seg"], gd["sumsq"].data_ptr(), gd["count"].data_ptr(),
+                                     gd["state"].data_ptr(), self.betas[0], self.betas[1], gd["ws"].data_ptr(), gd["ws_bytes"], ops._stream()),
+                  "ap_grad_health")
+            gd["used"] = True
         if self.g is None:                                   # slab length not a multiple of 4: padded copy
             gp = torch.zeros(self.n_pad, dtype=torch.float32, device=g.device)
             gp[:g.numel()] = g
             g = gp
         gscale = float(self.reducer.take_pending_scale())
+        if skip_nonfinite:
+            gd["gscale"] = gscale
         gnorm_ptr, max_norm, clip_value = None, 0.0, 0.0
         if clip_grad is not None and float(clip_grad) > 0:
             if clip_mode == "norm":
@@ -169,10 +250,13 @@ class FlatAdamWEma:
         lr, wd = float(self.param_groups[0]["lr"]), float(self.param_groups[0]["weight_decay"])
         if float(self.param_groups[1]["lr"]) != lr:
             raise ValueError("FlatAdamWEma: both parameter groups must share one learning rate (timm schedulers do)")
-        check(lib.ap_adamw_ema_step(self.p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.wd_mask.data_ptr(),
-                                    self.n_pad, lr, self.betas[0], self.betas[1], self.eps, wd, self.step_count, gscale,
-                                    gnorm_ptr, max_norm, clip_value, scalars.adam_ptr if scalars is not None else None, self._ema_ptrs, self._ema_decay, len(self.ema), self.p16.data_ptr(),
-                                    ops._stream()), "ap_adamw_ema_step")
+        args = (self.p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.wd_mask.data_ptr(),
+                self.n_pad, lr, self.betas[0], self.betas[1], self.eps, wd, self.step_count, gscale,
+                gnorm_ptr, max_norm, clip_value, scalars.adam_ptr if scalars is not None else None, self._ema_ptrs, self._ema_decay, len(self.ema), self.p16.data_ptr())
+        if skip_nonfinite:
+            check(lib.ap_adamw_ema_step_guarded(*args, gd["state"].data_ptr(), ops._stream()), "ap_adamw_ema_step_guarded")
+        else:
+            check(lib.ap_adamw_ema_step(*args, ops._stream()), "ap_adamw_ema_step")
         self._refresh_transposes()
         from . import functional
         functional._WeightBank.generation += 1             # the kernel wrote the parameters behind autograd's back
@@ -270,11 +354,13 @@ class FlatAdamWEma:
         in group order, plus the EMA slabs under "ema" (the reference keeps those in separate ModelEma objects)."""
         state, groups, idx = {}, [], 0
         offs = {id(p): off for p, (_, off, _) in zip(self.reducer.params, self._views)}
+        # Adam's t: once the guard has been used, the APPLIED steps (the device counter), not the calls of step()
+        t = self.guard_counts()["applied"] if (self._guard is not None and self._guard["used"]) else self.step_count
         for g in self.param_groups:
             ids = []
             for p in g["params"]:
                 off, n = offs[id(p)], p.numel()
-                state[idx] = {"step": torch.tensor(float(self.step_count)), "exp_avg": self.m[off:off + n].view_as(p).clone(),
+                state[idx] = {"step": torch.tensor(float(t)), "exp_avg": self.m[off:off + n].view_as(p).clone(),
                               "exp_avg_sq": self.v[off:off + n].view_as(p).clone()}
                 ids.append(idx)
                 idx += 1
@@ -305,3 +391,6 @@ class FlatAdamWEma:
             for bufs, saved in zip(self.ema_buffers, sd.get("ema_buffers", [])):
                 for dst, src in zip(bufs, saved):
                     dst.copy_(src)
+            if self._guard is not None:                          # the restored t goes into the device record; the skip counters restart
+                self._guard["state"].zero_()
+                self._guard["state"][1] = int(self.step_count)

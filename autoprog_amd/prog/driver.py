@@ -32,7 +32,7 @@ class AutoProgDriver:
     def __init__(self, model, loss_fn, optimizer, reducer, get_batch, r_list, l_list, dp_list, grow_epochs, steps_per_epoch,
                  search_epochs=2, auto_grow=True, probe_batches=4, time_steps=4, seed=0, log=None, original_batch_splits=1,
                  r_max=None, dist_bn="", use_graphs=False, graph_after=2, clip_grad=None, clip_mode="norm", get_val_batches=None,
-                 batch_prep=None, re_list=None):
+                 batch_prep=None, re_list=None, skip_nonfinite=False):
         """model: supernet sized for l_list[-1] (e.g. volo_h12_l18); optimizer: FlatAdamWEma over it; reducer: its
         GradientBucketReducer; r_list / l_list / dp_list / grow_epochs: the stage schedule (prog/progressive.py:4-31);
         get_batch(r): a training batch (images at ANY size -- the stem resizes to r -- and a token-label target for r // 16).
@@ -59,7 +59,13 @@ class AutoProgDriver:
         CutMix, RandomErasing and the stage's resize become one launch inside the patch embedding) and integer labels [B] that come
         with it become its MixedLabelTarget; anything else passes as it is.  re_list: the per-stage RandomErasing probability (the
         seventh value of prog.progressive.progressive_schedule, beside r_list / l_list / dp_list): batch_prep.re_prob is set to
-        re_list[stage] at every stage change.  Both None (default): batches pass untouched."""
+        re_list[stage] at every stage change.  Both None (default): batches pass untouched.
+        skip_nonfinite: every update, eager or replayed, runs FlatAdamWEma.step(skip_nonfinite=True): a step whose gradient holds an inf or a
+        NaN leaves the weights and the Adam moments alone, as apex's loss scaler does in the reference (prog/scaler.py:20-26).  Nothing is
+        read back per step; where an epoch ends (the loss read-back) guard_counts() is read once, the epoch's `history` entry and log line
+        get `skipped_steps`, and an epoch that skipped anything also gets `worst_grads`: the three worst entries of grad_health()."""
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._skipped_seen = 0
         if re_list is not None and (batch_prep is None or len(re_list) != len(r_list)):
             raise ValueError("re_list needs a batch_prep and one entry per stage")
         self.batch_prep, self.re_list = batch_prep, (list(re_list) if re_list is not None else None)
@@ -111,6 +117,7 @@ class AutoProgDriver:
         self._drop_graphs()                                           # (a graph holds the kernels of ONE configuration and optimizer layout)
         if self.mask is not None and (l != self.current_l or dp != self.current_dp):
             self.opt.grow(self.mask, new_mask, model_source="ema_last" if l >= self.current_l else "model")
+            self._skipped_seen = 0                                    # (the guard's counters restart with the optimizer)
         self.mask = self._activate(l, r, dp)
         self.current_l, self.current_r, self.current_dp = l, r, dp
         self.batch_splits = self.splits_for(l, r)
@@ -155,7 +162,8 @@ class AutoProgDriver:
         images, target = self.get_batch(r)
         self.reducer.zero_grad()
         self._set_splits(1)
-        gs = GraphedStep(self.model, self.loss_fn, self.reducer, self.opt, images, target, clip_grad=self.clip_grad, clip_mode=self.clip_mode).capture(warmup=0)
+        gs = GraphedStep(self.model, self.loss_fn, self.reducer, self.opt, images, target, clip_grad=self.clip_grad, clip_mode=self.clip_mode,
+                         **self._guard_kw()).capture(warmup=0)
         self._graphs[key] = gs
         return gs.step().detach().clone()                          # the batch the graph was built on is this step's batch
 
@@ -182,10 +190,25 @@ class AutoProgDriver:
             self.reducer.finish()
             total = loss.detach() if total is None else total + loss.detach()
         if self.clip_grad is not None:
-            self.opt.step(clip_grad=self.clip_grad, clip_mode=self.clip_mode)
+            self.opt.step(clip_grad=self.clip_grad, clip_mode=self.clip_mode, **self._guard_kw())
         else:
-            self.opt.step()                       # (any optimizer with the plain step() of the reference's loop works when nothing is clipped)
+            self.opt.step(**self._guard_kw())     # (any optimizer with the plain step() of the reference's loop works when nothing is clipped or guarded)
         return total if k == 1 else total / k
+
+    def _guard_kw(self):
+        return {"skip_nonfinite": True} if self.skip_nonfinite else {}
+
+    def _guard_report(self):
+        """end of an epoch, behind its loss read-back: -> the entries the guard adds to the epoch's record (the steps skipped since the
+        last reading; the steps of a search count towards the first training epoch after it)"""
+        if not self.skip_nonfinite:
+            return {}
+        skipped = self.opt.guard_counts()["skipped"]
+        out = {"skipped_steps": max(0, skipped - self._skipped_seen)}
+        self._skipped_seen = skipped
+        if out["skipped_steps"]:                                      # most non-finite elements first, then the largest norm
+            out["worst_grads"] = sorted(self.opt.grad_health(), key=lambda h: (-h[2], -h[1]))[:3]
+        return out
 
     def _eager(self):
         """an eager forward between replays (a step at a configuration without a graph yet, a probe, a timing pass): the mix-token box and
@@ -303,7 +326,11 @@ class AutoProgDriver:
             tot = float(tot)
             self.history.append(dict(epoch=epoch, kind="train", r=self.current_r, l=self.current_l, dp=self.current_dp,
                                      loss=tot / self.steps_per_epoch))
-            self.log("epoch %d: r=%d l=%d loss %.4f" % (epoch, self.current_r, self.current_l, tot / self.steps_per_epoch))
+            guard = self._guard_report()
+            self.history[-1].update(guard)
+            self.log("epoch %d: r=%d l=%d loss %.4f" % (epoch, self.current_r, self.current_l, tot / self.steps_per_epoch)
+                     + ("" if not guard else " skipped_steps %d%s" % (guard["skipped_steps"], "".join(
+                         " %s(norm %.3g, nonfinite %d)" % w for w in guard.get("worst_grads", [])))))
             self._distribute_bn()
             if self.get_val_batches is not None:
                 self.history[-1].update(self._validate())

@@ -505,6 +505,36 @@ int ap_adamw_ema_step(float* p, const float* g, float* m, float* v, const unsign
                       float* const* ema, const float* ema_decay, int n_ema,
                       ap_bf16* p_bf16 /* nullable: bf16 copy of the updated parameters, same offsets */,
                       ap_stream_t stream);
+
+/* ---- non-finite gradient guard of the fused step (additive in ABI version 7).  The reference trains under apex's dynamic loss scaler,
+ * which skips optimizer.step() for an iteration whose backward pass produced an inf or a NaN (prog/scaler.py:20-26) while
+ * ModelEmaV2.update still runs (main_prog.py:1030-1033).  ap_grad_health is one pass over the fp32 gradient slab g[n] (16-byte aligned,
+ * any n) against a DEVICE table seg_off[n_seg + 1] of ascending segment bounds (seg_off[0] = 0, seg_off[n_seg] = n; one segment per
+ * parameter tensor in slab order; lengths arbitrary, empty segments allowed):
+ *   seg_sumsq[s]     (fp64)  sum of x^2 over the FINITE elements of segment s (x^2 formed in fp64: a finite 3e38 is an ordinary element)
+ *   seg_nonfinite[s] (int32) elements of segment s whose exponent field is all ones (+-inf, NaN)
+ * and the step's decision in `state`, committed by the last thread of the pass:
+ *   nonfinite = this step's total; total == 0: applied += 1, consecutive = 0; else: skipped += 1, consecutive += 1;
+ *   bc1 = 1 - beta1^applied, bc2_sqrt = sqrt(1 - beta2^applied) as ap_adamw_ema_step forms them (double arithmetic on the fp32 betas,
+ *   rounded once to float).
+ * The counters live on the device: zero the record once, the host never writes it during a run.  Deterministic: ordered partials in
+ * `workspace` (ap_grad_health_workspace bytes, 8-byte aligned), no floating-point atomics; nothing is allocated. */
+typedef struct ap_guard_state {
+    int32_t nonfinite, applied, skipped, consecutive;
+    float bc1, bc2_sqrt;
+    int32_t reserved[2];
+} ap_guard_state;
+size_t ap_grad_health_workspace(int64_t n, int n_seg);
+int ap_grad_health(const float* g, int64_t n, const int64_t* seg_off, int n_seg, double* seg_sumsq, int32_t* seg_nonfinite,
+                   ap_guard_state* state, float beta1, float beta2, void* workspace, size_t ws_bytes, ap_stream_t stream);
+/* ap_adamw_ema_step with the decision of ap_grad_health (same stream, launched before it): state->nonfinite == 0 is the ordinary update
+ * with the record's bias corrections (`step` is only checked, of step_scalars_dev only the learning rate is read); otherwise p, m, v and
+ * p_bf16 are not written at all and every EMA copy takes its lerp towards the unchanged parameters. */
+int ap_adamw_ema_step_guarded(float* p, const float* g, float* m, float* v, const unsigned char* wd_mask, int64_t n,
+                              float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                              const float* gnorm_sq, float max_norm, float clip_value, const float* step_scalars_dev,
+                              float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, const ap_guard_state* guard,
+                              ap_stream_t stream);
 /* transpose `count` bf16 matrices of one slab in one launch: desc_dev = device array of
  * {int64 src_off, int64 dst_off, int rows, int cols, int ld_dst, int first_tile} (32x32 tiles, first_tile
  * = running tile prefix); dst[dst_off + c*ld_dst + r] = src[src_off + r*cols + c], pad columns zeroed */
