@@ -801,11 +801,11 @@ int ap_conv3x3_c64_wgrad_bn(const ap_bf16* x, const ap_bn_input* bn_in, const ap
     }
     static int use_p = -1;
     if (use_p < 0) { const char* e = getenv("AP_CONV_WGRAD_P"); use_p = e ? atoi(e) : 1; }
-    if (use_p || bn_in) {       // one prefetching workgroup per CU, 32 x 16 tiles (the only kernel with the BatchNorm input transform)
+    if (use_p || bn_in) {       // the prefetching kernel: at most 256 workgroups on CW_PTR x 16 = 16 x 16 tiles (the only one with the BatchNorm input transform)
         const int tyy = (H + PTR - 1) / PTR;
         const int64_t np = (int64_t)B * tiles_x * tyy;
         ntiles = (int)np;
-        const int gp = ntiles < 256 ? ntiles : 256;
+        const int gp = cw_grid(ntiles < 256 ? ntiles : 256);     // (under AP_CONV_WGRAD_GRID too: the workspace is sized by cw_grid)
         if ((size_t)gp * CV_WELEMS * sizeof(float) > ws_bytes) return AP_ERR_SHAPE;
         grid = gp;
         static int waves = 0;
@@ -848,7 +848,7 @@ int ap_conv3x3_c128_wgrad(const ap_bf16* x, const ap_bf16* dy, float* dw_oihw, i
     const int tiles_x = (W + CW_T - 1) / CW_T, tyy = (H + PTR - 1) / PTR;
     const int64_t np = (int64_t)B * tiles_x * tyy;
     if (np > 0x7fffffff) return AP_ERR_SHAPE;
-    const int ntiles = (int)np, grid = ntiles < 256 ? ntiles : 256;
+    const int ntiles = (int)np, grid = cw_grid(ntiles < 256 ? ntiles : 256);
     if ((size_t)grid * CV_WELEMS * sizeof(float) > ws_bytes) return AP_ERR_SHAPE;
     static int attr_done = 0;
     (void)hipGetLastError();

@@ -838,10 +838,15 @@ def test_grouped_wgrad_launch_carries_the_layernorm_reductions(ops):
                                  {"AP_STEM_HIP_CONV": "0"}, {"AP_ASYNC_WGRAD": "1"}, {"AP_GEMM_TN_PLACE": "0"}, {"AP_FUSE_LN_REDUCE": "0"}, {"AP_CONV_WGRAD_P": "0"},
                                  {"AP_GEMM_8P": "0"}, {"AP_GEMM_8P": "2"}, {"AP_GEMM_TN_8P": "0"}, {"AP_GELU_STORE_GRAD": "0"}, {"AP_GELU_STORE_GRAD": "1"}, {"AP_LN_BWD_PF": "0"}, {"AP_GEMM_BM224": "0"}, {"AP_GEMM_WS": "0"}, {"AP_GELU_TABLE": "0"}, {"AP_FUSE_POOL_BWD": "0"}, {"AP_STEM_FUSE_BN_PROJ": "0"}, {"AP_STEM_FUSE_BN_BWD_STATS": "0"}, {"AP_BN_PROJ_ACT_IN_BWD": "0"}, {"AP_WGRAD_WINDOW": "0"}, {"AP_STEM_FUSE_BN": "0"},
                                  {"AP_OUTLOOK_P": "0"}, {"AP_OUTLOOK_P": "2"}, {"AP_LN_FWD_LP": "0"}, {"AP_CONV_WAVES": "4"},
-                                 {"AP_FUSED_MLP": "0"}, {"AP_FUSED_MLP": "2"}, {"AP_FUSED_MLP_LN": "0"}, {"AP_FUSED_MLP_MIN_ROWS": "0"}, {"AP_MLP_FUSED_V": "1"}])
+                                 {"AP_FUSED_MLP": "0"}, {"AP_FUSED_MLP": "2"}, {"AP_FUSED_MLP_LN": "0"}, {"AP_FUSED_MLP_MIN_ROWS": "0"}, {"AP_MLP_FUSED_V": "1"},
+                                 {"AP_CONV_GRID": "3"}, {"AP_CONV_WGRAD_GRID": "3", "AP_CONV_WGRAD_P": "0"}, {"AP_CONV128_GRID": "3"},
+                                 {"AP_CONV7_GRID": "3", "AP_CONV7_WGRAD_GRID": "3"}, {"AP_LN_BWD_GRID": "8"}])
 def test_experimental_kernel_paths_stay_parity_green(env):
     """the kernels kept behind environment switches (DESIGN.md 'What bounds the GEMMs') must keep computing the same thing:
-    re-run the GEMM / block tests in a child process with the switch set (the switches are read once per process)"""
+    re-run the GEMM / block tests in a child process with the switch set (the switches are read once per process).
+    The grid caps (AP_CONV_GRID, AP_CONV_WGRAD_GRID, AP_CONV128_GRID, AP_CONV7_GRID / _WGRAD_GRID = 3, AP_LN_BWD_GRID = 8) make a workgroup
+    of the persistent kernels walk dozens of tiles of the 112 x 112 cases (hundreds of rows of the LayerNorm cases): deep trips through
+    the work loops, next to the two or three of tests/test_gpu_multi_item.py"""
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     key = next(iter(env))
@@ -857,8 +862,10 @@ def test_experimental_kernel_paths_stay_parity_green(env):
         sel, files = "layernorm or ln_", ["tests/test_gpu_kernels.py", "tests/test_gpu_fullsize.py"]
     elif "OUTLOOK" in key or "POOL" in key:
         sel, files = "outlook", ["tests/test_gpu_kernels.py", "tests/test_gpu_blocks.py"]
-    elif "CONV_WGRAD" in key or "CONV_WAVES" in key:
-        sel, files = "conv3x3 or stem64", ["tests/test_gpu_kernels.py", "tests/test_gpu_blocks.py"]
+    elif "CONV_WGRAD" in key or "CONV_WAVES" in key or key in ("AP_CONV_GRID", "AP_CONV128_GRID"):
+        sel, files = "conv3x3 or stem64" + (" or stem128" if "128" in key else ""), ["tests/test_gpu_kernels.py", "tests/test_gpu_blocks.py"]
+    elif key == "AP_CONV7_GRID":
+        sel, files = "conv7 or stem64 or stem128", ["tests/test_gpu_kernels.py", "tests/test_gpu_blocks.py"]
     elif "STEM" in key:          # AP_STEM_HIP_CONV, AP_STEM_FUSE_BN
         sel, files = "d1_shapes or hip_stem or patch_embed", ["tests/test_gpu_model.py", "tests/test_gpu_blocks.py"]
     elif "WGRAD" in key or "FUSE_LN" in key or ("GELU" in key and "TABLE" not in key):
@@ -1031,8 +1038,10 @@ def test_conv3x3_c64_input_gradient_with_the_batchnorm_backward_sums(B, H, W):
 def test_conv3x3_c128_fwd_dgrad_wgrad_vs_torch_fp32(B, H, W):
     """csrc/conv128.hip (ap_conv3x3_c128: the 3x3 convolutions of the 128-wide VOLO-D4 / D5 stem, models/volo.py:359-366 with
     stem_hidden_dim = 128) and ap_conv3x3_c128_wgrad against torch's fp32 convolution on the same bf16-rounded operands.  Ragged sizes
-    exercise the 16 x 16 tile edges and workgroups that walk several tiles (the weight-slab ring runs across tiles; (5, 56, 56) is more
-    tiles than CUs).  Tolerances as at 64 channels: outputs 5e-3 rel-L2, the partial BatchNorm sums 1e-5, the fp32 weight gradient 1e-5."""
+    exercise the 16 x 16 tile edges; (5, 56, 56) is 5 x 4 x 4 = 80 tiles, one per workgroup -- a workgroup's second and third tile (the
+    weight-slab ring runs across tiles) are the case of tests/test_gpu_multi_item.py, dozens of tiles that of AP_CONV128_GRID=3 in
+    test_experimental_kernel_paths_stay_parity_green.  Tolerances as at 64 channels: outputs 5e-3 rel-L2, the partial BatchNorm sums 1e-5,
+    the fp32 weight gradient 1e-5."""
     import torch.nn.functional as F
     from autoprog_amd import ops
     torch.manual_seed(B * 1000 + H)
