@@ -203,6 +203,310 @@ k_soft_ce_sparse(const bf16_t* __restrict__ logits, int ldx, const int* __restri
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- rows wider than 1024
+// ldx > 64 * 2 * CE_MAXV: a row no longer fits one wave's registers (21 843 classes: 43.7 KB of bf16).  The row is staged in LDS ONCE
+// (16-byte chunks, the loads of the next batch issued before the previous one is written and reduced) and every later walk reads LDS:
+// logits once in, gradient once out, whatever the caches do.  Three walks: maximum (while staging), sums, gradient -- the exact
+// max-then-sum order of the narrow kernels, no running rescale.  A TEAM of WPR waves owns a row:
+//   WPR = 1 (ldx <= CE_WIDE_TEAM1_MAXLD): four rows per workgroup, 4 * ldx * 2 B of LDS (<= 32 KB);
+//   WPR = 4: one row per workgroup, ldx * 2 B of LDS -- three workgroups per CU at 21 848 columns, one at CE_WIDE_MAXLD = 65 536.
+// Plain grid, one workgroup per row group; two barriers per workgroup (every wave reaches both: rows beyond M are clamped and only
+// their stores are masked).  Padding columns C .. ldx-1 of the logits reach LDS and registers but are replaced by a select before
+// any use; their gradient is stored as zeros with the last chunks of the row.
+//   SPARSE: a lane owns the 8 classes of a 16-byte chunk (16-byte stores).  The pairs sit one per lane (as in k_soft_ce_sparse);
+//     sum t = s + sum_k v_k and sum t x = (s / C) sum x + sum_k v_k x[i_k] need no scan, and in the gradient walk a wave's 64 chunks
+//     are one 512-class window: one ballot per window finds the pairs inside it, and each of those lands in ONE (lane, element).
+//   DENSE: a lane owns a class pair (the 4-byte mapping of k_soft_ce) and reads its two target values straight from global memory
+//     through (t_sb, t_sc, t_sn) -- any strides, coalesced when the target is row-major [M, C] (t_sc = 1: timm's Mixup target).  The
+//     target is walked twice (sums, gradient): 8 B per class of one row, the second walk comes from L2.  The class-major token-label
+//     tensor (t_sn = 1) is correct here and uncoalesced; it takes k_soft_ce_wide_cm below where its token tile fits LDS.
+#define CE_WIDE_MAXLD 65536
+#define CE_WIDE_TEAM1_MAXLD 4096
+
+template <int T>
+__device__ __forceinline__ float ce_wide_stage(const u32x4* __restrict__ xg, u32x4* xs, int nch, int C, int tt) {
+    constexpr int U = 4;
+    float mx = -3.0e38f;
+    u32x4 cur[U], nxt[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) cur[u] = xg[min(tt + T * u, nch - 1)];          // clamped, unconditional
+    for (int base = 0; base < nch; base += U * T) {
+        const bool more = base + U * T < nch;                                    // team-uniform: one branch around the whole batch
+        if (more) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) nxt[u] = xg[min(base + U * T + tt + T * u, nch - 1)];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int q = base + tt + T * u;
+            if (q < nch) {
+                xs[q] = cur[u];
+                float f[8];
+                unpack8(cur[u], f);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) mx = fmaxf(mx, 8 * q + j < C ? f[j] : -3.0e38f);
+            }
+        }
+        if (more) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        }
+    }
+    return mx;
+}
+
+// the dense target of class pairs g = tt, tt + T, .. < ngr, four pairs per lane in flight, the next batch requested before f(g, t0, t1)
+// runs on the previous one.  mixed: t = lam1 * t[b] + lam2 * t[B-1-b] (one wave-uniform branch per batch)
+template <int T, class F>
+__device__ __forceinline__ void ce_wide_walk_target(const float* __restrict__ tb, const float* __restrict__ tb2, bool mixed, float lam1, float lam2,
+                                                    int64_t t_sc, int C, int ngr, int tt, F&& f) {
+    constexpr int U = 4;
+    float cur[U][2], nxt[U][2];
+    auto load = [&](float (&o)[U][2], int base) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int c = 2 * (base + tt + T * u);
+            const int64_t o0 = (int64_t)min(c, C - 1) * t_sc, o1 = (int64_t)min(c + 1, C - 1) * t_sc;
+            o[u][0] = tb[o0];
+            o[u][1] = tb[o1];
+        }
+        if (mixed) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int c = 2 * (base + tt + T * u);
+                const int64_t o0 = (int64_t)min(c, C - 1) * t_sc, o1 = (int64_t)min(c + 1, C - 1) * t_sc;
+                o[u][0] = lam1 * o[u][0] + lam2 * tb2[o0];
+                o[u][1] = lam1 * o[u][1] + lam2 * tb2[o1];
+            }
+        }
+    };
+    load(cur, 0);
+    for (int base = 0; base < ngr; base += U * T) {
+        const bool more = base + U * T < ngr;
+        if (more) load(nxt, base + U * T);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int g = base + tt + T * u;
+            if (g < ngr) f(g, cur[u][0], cur[u][1]);
+        }
+        if (more) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) { cur[u][0] = nxt[u][0]; cur[u][1] = nxt[u][1]; }
+        }
+    }
+}
+
+template <int WPR, bool DENSE>
+__global__ void __launch_bounds__(256)
+k_soft_ce_wide(const bf16_t* __restrict__ logits, int ldx, const float* __restrict__ target, int64_t t_sb, int64_t t_sc, int64_t t_sn,
+               const int* __restrict__ idx, const float* __restrict__ val, int K, int64_t p_sb, int64_t p_sn, float smoothing,
+               int rows_per_batch, float* __restrict__ row_loss, bf16_t* __restrict__ dlogits, float gscale, int64_t M, int C,
+               float mix_lam, int mix_batches, const float* __restrict__ lam_dev) {
+    if (lam_dev) mix_lam = lam_dev[0];
+    extern __shared__ __attribute__((aligned(16))) u32x4 ce_wide_rows[];       // [4 / WPR][ldx / 8]
+    __shared__ float red_mx[4], red_a[4], red_b[4], red_c[4];
+    constexpr int T = 64 * WPR;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int team = wave / WPR, tw = wave % WPR, tt = tw * 64 + lane;
+    const int64_t row_raw = (int64_t)blockIdx.x * (4 / WPR) + team;
+    const bool live = row_raw < M;
+    const int64_t row = min(row_raw, M - 1);
+    const int nch = ldx >> 3;
+    u32x4* xs = ce_wide_rows + (size_t)team * nch;
+    const int64_t b = row / rows_per_batch, n = row - b * rows_per_batch;
+    const bool mixed = mix_batches > 0;
+    // SPARSE: lane k holds pair k of the row (lanes K .. 2K-1: the partner image's, weighted 1 - lam); a pair outside [0, C) is dropped here
+    int my_i = -1;
+    float my_v = 0.f;
+    if (!DENSE) {
+        const int KK = mixed ? 2 * K : K;
+        const bool other = lane >= K;
+        const int64_t po = ((mixed && other) ? (int64_t)(mix_batches - 1) - b : b) * p_sb + n * p_sn + (other ? lane - K : lane);
+        const float wgt = mixed ? (other ? 1.0f - mix_lam : mix_lam) : 1.0f;
+        if (lane < KK) { my_i = idx[po]; my_v = val[po] * wgt * (1.0f - smoothing); }
+        if (my_i < 0 || my_i >= C) { my_i = -1; my_v = 0.f; }
+    }
+    // ---- walk 1: global -> LDS, the maximum on the way
+    float mx = group_max<64>(ce_wide_stage<T>(reinterpret_cast<const u32x4*>(logits + row * ldx), xs, nch, C, tt));
+    if (lane == 0) red_mx[wave] = mx;
+    __syncthreads();
+    mx = red_mx[team * WPR];
+#pragma unroll
+    for (int w = 1; w < WPR; ++w) mx = fmaxf(mx, red_mx[team * WPR + w]);
+    // ---- walk 2: sum exp, sum t, sum t x
+    const float* tb = DENSE ? target + b * t_sb + n * t_sn : nullptr;
+    const float* tb2 = (DENSE && mixed) ? target + (int64_t)(mix_batches - 1 - b) * t_sb + n * t_sn : tb;
+    const float lam1 = mix_lam, lam2 = 1.0f - mix_lam;
+    const unsigned* xw = reinterpret_cast<const unsigned*>(xs);
+    float se = 0.f, st = 0.f, stx = 0.f;
+    if (DENSE) {
+        ce_wide_walk_target<T>(tb, tb2, mixed, lam1, lam2, t_sc, C, (C + 1) >> 1, tt, [&](int g, float t0, float t1) {
+            const unsigned w = xw[g];
+            const float x0 = bf_lo(w), x1 = bf_hi(w);
+            se += __expf(x0 - mx); st += t0; stx += t0 * x0;                      // 2 g < C always
+            if (2 * g + 1 < C) { se += __expf(x1 - mx); st += t1; stx += t1 * x1; }
+        });
+    } else {
+        float sx = 0.f;
+#pragma unroll 2
+        for (int q = tt; q < nch; q += T) {
+            float f[8];
+            unpack8(xs[q], f);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (8 * q + j < C) { se += __expf(f[j] - mx); sx += f[j]; }
+        }
+        st = sx;                                                                  // (reduced below; scaled after)
+    }
+    se = group_sum<64>(se); st = group_sum<64>(st); stx = group_sum<64>(stx);
+    if (lane == 0) { red_a[wave] = se; red_b[wave] = st; red_c[wave] = stx; }
+    __syncthreads();
+    se = red_a[team * WPR]; st = red_b[team * WPR]; stx = red_c[team * WPR];
+#pragma unroll
+    for (int w = 1; w < WPR; ++w) { se += red_a[team * WPR + w]; st += red_b[team * WPR + w]; stx += red_c[team * WPR + w]; }
+    const float base = smoothing / (float)C;
+    if (!DENSE) {
+        // t = base + the pairs: sum t = C base + sum_k v_k,  sum t x = base sum x + sum_k v_k x[i_k]  (every wave of the team, same values)
+        const float xk = bf2f(reinterpret_cast<const bf16_t*>(xs)[max(my_i, 0)]);
+        const float pst = group_sum<64>(my_v), pstx = group_sum<64>(my_i >= 0 ? my_v * xk : 0.f);
+        stx = base * st + pstx;
+        st = base * (float)C + pst;
+    }
+    const float lse = mx + __logf(se);
+    if (live && tt == 0) row_loss[row] = lse * st - stx;
+    // ---- walk 3: the gradient, columns C .. ldx-1 as zeros
+    bf16_t* dr = dlogits + row * ldx;
+    if (DENSE) {
+        ce_wide_walk_target<T>(tb, tb2, mixed, lam1, lam2, t_sc, C, ldx >> 1, tt, [&](int g, float t0, float t1) {
+            const unsigned w = xw[g];
+            const int c = 2 * g;
+            float d0 = 0.f, d1 = 0.f;
+            if (c < C) d0 = gscale * (__expf(bf_lo(w) - lse) * st - t0);
+            if (c + 1 < C) d1 = gscale * (__expf(bf_hi(w) - lse) * st - t1);
+            if (live) *reinterpret_cast<unsigned*>(dr + c) = pack_bf2(d0, d1);
+        });
+    } else {
+        const int my_win = my_i >= 0 ? my_i >> 9 : -1;
+        for (int q0 = 0; q0 < nch; q0 += T) {
+            const int q = q0 + tt;
+            float tv[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) tv[j] = base;
+            // this wave's 64 chunks are classes [512 win, 512 win + 512); the pairs are wave-uniform once read with v_readlane
+            unsigned long long hits = __ballot(my_win == (q0 >> 6) + tw);
+            while (hits) {
+                const int k = __builtin_ctzll(hits);
+                hits &= hits - 1;
+                const int ci = __builtin_amdgcn_readlane(my_i, k);
+                const float cv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_v), k));
+                const float add = lane == ((ci >> 3) & 63) ? cv : 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) tv[j] += (j == (ci & 7)) ? add : 0.f;
+            }
+            if (q < nch) {
+                float f[8], d[8];
+                unpack8(xs[q], f);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) d[j] = 8 * q + j < C ? gscale * (__expf(f[j] - lse) * st - tv[j]) : 0.f;
+                if (live) st16_nt(dr + 8 * q, pack8(d));
+            }
+        }
+    }
+}
+
+// The class-major token-label tensor [B, C, 2 + N] (t_sn = 1) at 1024 < ldx <= 128 * MAXV: k_soft_ce's own structure with more class
+// pairs per lane (k_soft_ce itself stays as it is, bit for bit, for the rows it takes).  The 16-token target tile is transposed
+// through LDS -- 16 * (C | 1) * 4 B, which is what bounds this form: 70 KB at 1100 classes (two workgroups per CU), 160 KB at
+// CE_WIDE_CM_MAXC -- and a wave keeps its four logits rows in registers (MAXV words each).  Wider class-major targets take
+// k_soft_ce_wide through their strides.
+#define CE_WIDE_CM_MAXC 2559
+template <int MAXV>
+__global__ void __launch_bounds__(256)
+k_soft_ce_wide_cm(const bf16_t* __restrict__ logits, int ldx, const float* __restrict__ target, int64_t t_sb, int64_t t_sc,
+                  int64_t t_sn, int rows_per_batch, float* __restrict__ row_loss, bf16_t* __restrict__ dlogits,
+                  float gscale, int64_t M, int C, int tiles_per_batch, float mix_lam, int mix_batches, const float* __restrict__ lam_dev) {
+    if (lam_dev) mix_lam = lam_dev[0];
+    extern __shared__ __attribute__((aligned(16))) float ce_cm_tile[];      // [CE_TN][Cp] Cp odd
+    const int Cp = C | 1;
+    const int64_t b = blockIdx.x / tiles_per_batch;
+    const int n0 = (blockIdx.x % tiles_per_batch) * CE_TN;
+    const int ntok = min(CE_TN, rows_per_batch - n0);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // the logits of this wave's (up to) four rows first: their latency hides behind phase A (clamped, unconditional 4-byte loads)
+    unsigned lraw[CE_TN / 4][MAXV];
+#pragma unroll
+    for (int r = 0; r < CE_TN / 4; ++r) {
+        const int64_t rowc = min(b * rows_per_batch + n0 + min(wave + 4 * r, ntok - 1), M - 1);
+        const bf16_t* xr = logits + rowc * ldx;
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) lraw[r][i] = *reinterpret_cast<const unsigned*>(xr + min(2 * (lane + 64 * i), ldx - 2));
+    }
+    // ---- phase A: target tile -> LDS (token-major), 32 independent loads in flight per thread
+    {
+        const int tn = threadIdx.x & (CE_TN - 1), cl = threadIdx.x / CE_TN;
+        const int tnc = min(tn, ntok - 1);
+        const bool mixed = mix_batches > 0;
+        const float* tb = target + b * t_sb + (int64_t)(n0 + tnc) * t_sn;
+        const float* tb2 = mixed ? target + (int64_t)(mix_batches - 1 - b) * t_sb + (int64_t)(n0 + tnc) * t_sn : tb;
+        const float lam2 = mixed ? 1.0f - mix_lam : 0.f, lam1 = mixed ? mix_lam : 1.0f;
+        constexpr int CSTEP = 256 / CE_TN, INFLIGHT = 32;
+        for (int c0 = cl; c0 < C; c0 += INFLIGHT * CSTEP) {
+            float v[INFLIGHT], v2[INFLIGHT];
+#pragma unroll
+            for (int u = 0; u < INFLIGHT; ++u) v[u] = tb[(int64_t)min(c0 + u * CSTEP, C - 1) * t_sc];
+            if (mixed) {
+#pragma unroll
+                for (int u = 0; u < INFLIGHT; ++u) v2[u] = tb2[(int64_t)min(c0 + u * CSTEP, C - 1) * t_sc];
+            } else {
+#pragma unroll
+                for (int u = 0; u < INFLIGHT; ++u) v2[u] = 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < INFLIGHT; ++u) {
+                const int c = c0 + u * CSTEP;
+                if (tn < ntok && c < C) ce_cm_tile[tn * Cp + c] = lam1 * v[u] + lam2 * v2[u];
+            }
+        }
+    }
+    __syncthreads();
+    // ---- phase B
+#pragma unroll
+    for (int r = 0; r < CE_TN / 4; ++r) {
+        const int tn = wave + 4 * r;
+        const int64_t row = b * rows_per_batch + n0 + tn;
+        if (tn >= ntok || row >= M) break;
+        const float* tr = ce_cm_tile + tn * Cp;
+        float mx = -3.0e38f;
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int c = 2 * (lane + 64 * i);
+            mx = fmaxf(mx, fmaxf(c < C ? bf_lo(lraw[r][i]) : -3.0e38f, c + 1 < C ? bf_hi(lraw[r][i]) : -3.0e38f));
+        }
+        mx = group_max<64>(mx);
+        float se = 0.f, st = 0.f, stx = 0.f;
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int c = 2 * (lane + 64 * i);
+            if (c < C) { const float x = bf_lo(lraw[r][i]), t = tr[c]; se += __expf(x - mx); st += t; stx += t * x; }
+            if (c + 1 < C) { const float x = bf_hi(lraw[r][i]), t = tr[c + 1]; se += __expf(x - mx); st += t; stx += t * x; }
+        }
+        se = group_sum<64>(se); st = group_sum<64>(st); stx = group_sum<64>(stx);
+        const float lse = mx + __logf(se);
+        if (lane == 0) row_loss[row] = lse * st - stx;
+        bf16_t* dr = dlogits + row * ldx;
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int c = 2 * (lane + 64 * i);
+            if (c < ldx) {      // ldx is even: pairs never straddle the row end
+                float d0 = 0.f, d1 = 0.f;
+                if (c < C) d0 = gscale * (__expf(bf_lo(lraw[r][i]) - lse) * st - tr[c]);
+                if (c + 1 < C) d1 = gscale * (__expf(bf_hi(lraw[r][i]) - lse) * st - tr[c + 1]);
+                *reinterpret_cast<unsigned*>(dr + c) = pack_bf2(d0, d1);
+            }
+        }
+    }
+}
+
 // loss = wa * sum(a[0:na]) + wb * sum(b[0:nb]) in one workgroup (the two CE terms of the token-label loss, loss/cross_entropy.py:154-156)
 __global__ void __launch_bounds__(1024)
 k_loss_combine(const float* __restrict__ a, int64_t na, float wa, const float* __restrict__ b, int64_t nb, float wb, float* __restrict__ out) {
@@ -229,6 +533,59 @@ extern "C" int ap_loss_combine(const float* a, int64_t na, float wa, const float
     return ap_check_launch();
 }
 
+// rows wider than the register kernels take: k_soft_ce_wide, a team of one wave per row up to CE_WIDE_TEAM1_MAXLD columns and of four beyond
+template <bool DENSE>
+static int ce_wide_launch(const ap_bf16* logits, int ldx, const float* target, int64_t t_sb, int64_t t_sc, int64_t t_sn, const int* idx, const float* val,
+                          int K, int64_t p_sb, int64_t p_sn, float smoothing, int rows_per_batch, float* row_loss, ap_bf16* dlogits, float grad_scale,
+                          int64_t M, int C, float mix_lam, int mix_batches, const float* mix_lam_dev, ap_stream_t stream) {
+    if (ldx > CE_WIDE_MAXLD) return AP_ERR_UNSUPPORTED;
+    if (((uintptr_t)logits | (uintptr_t)dlogits) & 15) return AP_ERR_SHAPE;       // rows are moved in 16-byte chunks
+    if (M == 0) return AP_OK;
+    const bool team1 = ldx <= CE_WIDE_TEAM1_MAXLD;
+    const int rpb = team1 ? 4 : 1;
+    const int64_t blocks = (M + rpb - 1) / rpb;
+    if (blocks > 0x7fffffffLL) return AP_ERR_SHAPE;
+    const size_t lds = (size_t)rpb * ldx * sizeof(bf16_t);
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute((const void*)k_soft_ce_wide<4, DENSE>, hipFuncAttributeMaxDynamicSharedMemorySize, CE_WIDE_MAXLD * (int)sizeof(bf16_t));
+        attr = true;
+    }
+    (void)hipGetLastError();
+    if (team1)
+        hipLaunchKernelGGL((k_soft_ce_wide<1, DENSE>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, logits, ldx, target, t_sb, t_sc, t_sn, idx, val, K,
+                           p_sb, p_sn, smoothing, rows_per_batch, row_loss, dlogits, grad_scale, M, C, mix_lam, mix_batches, mix_lam_dev);
+    else
+        hipLaunchKernelGGL((k_soft_ce_wide<4, DENSE>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, logits, ldx, target, t_sb, t_sc, t_sn, idx, val, K,
+                           p_sb, p_sn, smoothing, rows_per_batch, row_loss, dlogits, grad_scale, M, C, mix_lam, mix_batches, mix_lam_dev);
+    return ap_check_launch();
+}
+
+// the class-major token-label tensor while its 16-token tile fits LDS: 12 or 20 class pairs per lane
+static int ce_wide_cm_launch(const ap_bf16* logits, int ldx, const float* target, int64_t t_sb, int64_t t_sc, int64_t t_sn, int rows_per_batch,
+                             float* row_loss, ap_bf16* dlogits, float grad_scale, int64_t M, int C, float mix_lam, int mix_batches,
+                             const float* mix_lam_dev, ap_stream_t stream) {
+    if (M == 0) return AP_OK;
+    const int tiles = (rows_per_batch + CE_TN - 1) / CE_TN;
+    const int64_t blocks = (M / rows_per_batch) * tiles;
+    if (blocks > 0x7fffffffLL) return AP_ERR_SHAPE;
+    const size_t lds = (size_t)CE_TN * (C | 1) * sizeof(float);
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute((const void*)k_soft_ce_wide_cm<12>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_soft_ce_wide_cm<20>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr = true;
+    }
+    (void)hipGetLastError();
+    if (ldx <= 128 * 12)
+        hipLaunchKernelGGL(k_soft_ce_wide_cm<12>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, logits, ldx, target, t_sb, t_sc, t_sn, rows_per_batch,
+                           row_loss, dlogits, grad_scale, M, C, tiles, mix_lam, mix_batches, mix_lam_dev);
+    else
+        hipLaunchKernelGGL(k_soft_ce_wide_cm<20>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, logits, ldx, target, t_sb, t_sc, t_sn, rows_per_batch,
+                           row_loss, dlogits, grad_scale, M, C, tiles, mix_lam, mix_batches, mix_lam_dev);
+    return ap_check_launch();
+}
+
 extern "C" int ap_soft_ce_fwd_bwd(const ap_bf16* logits, int ldx, const float* target, int64_t t_sb, int64_t t_sc,
                                   int64_t t_sn, int rows_per_batch, float* row_loss, ap_bf16* dlogits,
                                   float grad_scale, int64_t M, int C, float mix_lam, int mix_batches, ap_stream_t stream) {
@@ -241,7 +598,11 @@ extern "C" int ap_soft_ce_fwd_bwd_dev(const ap_bf16* logits, int ldx, const floa
     if (!logits || !target || !row_loss || !dlogits) return AP_ERR_NULL;
     if (mix_batches != 0 && (mix_batches < 0 || (int64_t)mix_batches * rows_per_batch != M)) return AP_ERR_SHAPE;
     if (C <= 0 || ldx < C || (ldx & 7) || rows_per_batch <= 0 || M % rows_per_batch) return AP_ERR_SHAPE;
-    if (ldx > 64 * 2 * CE_MAXV) return AP_ERR_UNSUPPORTED;
+    if (ldx > 64 * 2 * CE_MAXV && t_sn == 1 && rows_per_batch > 1 && C <= CE_WIDE_CM_MAXC && ldx <= 128 * 20)
+        return ce_wide_cm_launch(logits, ldx, target, t_sb, t_sc, t_sn, rows_per_batch, row_loss, dlogits, grad_scale, M, C, mix_lam, mix_batches, mix_lam_dev, stream);
+    if (ldx > 64 * 2 * CE_MAXV)
+        return ce_wide_launch<true>(logits, ldx, target, t_sb, t_sc, t_sn, nullptr, nullptr, 0, 0, 0, 0.f, rows_per_batch, row_loss, dlogits, grad_scale, M, C,
+                                    mix_lam, mix_batches, mix_lam_dev, stream);
     if (M == 0) return AP_OK;
     const int tiles = (rows_per_batch + CE_TN - 1) / CE_TN;
     const int64_t blocks = (M / rows_per_batch) * tiles;
@@ -265,7 +626,9 @@ extern "C" int ap_soft_ce_sparse_fwd_bwd_dev(const ap_bf16* logits, int ldx, con
     if (!logits || !idx || !val || !row_loss || !dlogits) return AP_ERR_NULL;
     if (C <= 0 || ldx < C || (ldx & 7) || rows_per_batch <= 0 || M < 0 || K <= 0 || K > CE_MAXK || smoothing < 0.f || smoothing >= 1.f) return AP_ERR_SHAPE;
     if (mix_batches != 0 && (mix_batches < 0 || (int64_t)mix_batches * rows_per_batch != M || 2 * K > CE_MAXK)) return AP_ERR_SHAPE;
-    if (ldx > 64 * 2 * CE_MAXV) return AP_ERR_UNSUPPORTED;
+    if (ldx > 64 * 2 * CE_MAXV)
+        return ce_wide_launch<false>(logits, ldx, nullptr, 0, 0, 0, idx, val, K, p_sb, p_sn, smoothing, rows_per_batch, row_loss, dlogits, grad_scale, M, C,
+                                     mix_lam, mix_batches, mix_lam_dev, stream);
     if (M == 0) return AP_OK;
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_soft_ce_sparse, dim3((unsigned)((M + 4 * CE_SR - 1) / (4 * CE_SR))), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const bf16_t*>(logits), ldx,

@@ -33,10 +33,10 @@ class SoftTargetCrossEntropy(nn.Module):
     def forward(self, x, target):
         from ..data import MixedLabelTarget
         if isinstance(target, MixedLabelTarget):
-            # a Mixup / CutMix batch of data.DeviceBatchPrep: (labels, lam) go to the sparse kernel as they are; rows wider than it takes
-            # are densified (timm's mixup_target) and take the dense kernel
+            # a Mixup / CutMix batch of data.DeviceBatchPrep: (labels, lam) go to the sparse kernel as they are, at every class count; only a
+            # target that does not pair up with the logits row for row is densified (timm's mixup_target) and takes the dense kernel
             C = x.shape[-1]
-            if x.dim() == 2 and target.labels.is_cuda and x.shape[0] == target.labels.shape[0] and -(-C // 8) * 8 <= SPARSE_CE_MAX_CLASSES:
+            if x.dim() == 2 and target.labels.is_cuda and x.shape[0] == target.labels.shape[0]:
                 lam = target if target.from_device else target.lam
                 return AF.MixedLabelCEFn.apply(x.to(torch.bfloat16), target.labels, target.ones, target.smoothing, lam)
             if target.from_device:
@@ -54,7 +54,7 @@ class TokenLabelSoftTargetCrossEntropy(nn.Module):
         return _dense_ce(x.to(torch.bfloat16), target)
 
 
-SPARSE_CE_MAX_PAIRS, SPARSE_CE_MAX_CLASSES = 16, 1024        # CE_MAXK and 64 * 2 * CE_MAXV of csrc/softce.hip
+SPARSE_CE_MAX_PAIRS = 16        # CE_MAXK of csrc/softce.hip; the class count is not limited here (rows of up to 65 536 padded columns)
 
 
 class _TokenLabelBase(nn.Module):
@@ -76,11 +76,11 @@ class _TokenLabelBase(nn.Module):
         bbx1, bby1, bbx2, bby2 = (0, 0, 0, 0) if dev_box is not None else bb
         B, N, C = aux_output.shape
         if isinstance(target, SparseTokenLabelTarget):
-            # the sparse kernel takes up to 16 (class, score) pairs per row -- the mix-token class row carries 2K -- and rows of up to
-            # 1024 (padded) classes; anything beyond is densified and takes the dense kernels
+            # the sparse kernel takes up to 16 (class, score) pairs per row -- the mix-token class row carries 2K -- at every class count (a
+            # dense [B, C, 2 + N] tensor at 21 843 classes could not exist); more pairs are densified and take the dense kernels
             K = target.idx.shape[-1]
             if (type(self)._adjust_cls is _TokenLabelBase._adjust_cls and target.idx.is_cuda and target.idx.shape[1] == 2 + N
-                    and 2 * K <= SPARSE_CE_MAX_PAIRS and -(-C // 8) * 8 <= SPARSE_CE_MAX_CLASSES):
+                    and 2 * K <= SPARSE_CE_MAX_PAIRS):
                 lam = dev_box if dev_box is not None else float(1 - ((bbx2 - bbx1) * (bby2 - bby1) / N))
                 return AF.SparseTokenLabelCEFn.apply(output.to(torch.bfloat16), aux_output.to(torch.bfloat16), target.idx, target.val,
                                                      target.smoothing, lam, float(self.cls_weight), float(self.dense_weight))

@@ -331,7 +331,13 @@ int ap_mix_token_swap_dev(const ap_bf16* x, ap_bf16* y, int B, int H, int W, int
  * row_loss[row] = -sum_c t*log_softmax(x);  dlogits = grad_scale*(softmax*sum_c t - t)
  * (columns C..ldx-1 of dlogits are zeroed).
  * mix_batches = B > 0: the target of batch b is mix_lam * t[b] + (1 - mix_lam) * t[B-1-b] (the mix-token image label,
- * loss/cross_entropy.py:151-152) -- no mixed copy of the target is materialised; 0: plain.       */
+ * loss/cross_entropy.py:151-152) -- no mixed copy of the target is materialised; 0: plain.
+ * Widths (both losses, all four entry points; ldx % 8 == 0): ldx <= 1024 runs the register kernels, a row in one wave.  1024 < ldx <= 65 536
+ * (ImageNet-21k: 21 843 classes; iNaturalist: 8 142 / 10 000) runs the wide kernels on the same contract -- fp32 statistics, columns C..ldx-1
+ * of dlogits zeroed, mix_batches / mix_lam / mix_lam_dev, any target strides, no atomics, no workspace, no host synchronisation; they move
+ * rows in 16-byte chunks: logits and dlogits 16-byte aligned (AP_ERR_SHAPE otherwise).  ldx > 65 536: AP_ERR_UNSUPPORTED (a row is staged
+ * in LDS, 2 B per column of the 160 KB).  The dense wide kernel is fast on a row-major target (t_sc == 1: [M, C] soft targets) and, up to
+ * 2559 classes, on the class-major token-label tensor (t_sn == 1, rows_per_batch > 1); other strides are correct and uncoalesced. */
 /* Validation statistics, per row (additive in ABI version 7): logits bf16 [rows, ld], n_classes <= ld valid columns, labels int64 [rows] ->
  *   loss[row] = logsumexp(z) - z[label]                                    (fp32 accumulation)
  *   rank[row] = #{c : z[c] > z[label]}   -- STRICTLY greater: a row is top-k correct iff 0 <= rank < k.  On ties this is the most favourable
