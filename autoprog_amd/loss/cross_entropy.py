@@ -113,6 +113,17 @@ class TokenLabelCrossEntropy(_TokenLabelBase):
     """reference TokenLabelCrossEntropy (loss/cross_entropy.py:112-156)"""
 
 
+def _chunked_rows(x2d):
+    """logits [M, C] as ops.softmax_topk reads them: bf16, unit column stride, rows of a multiple of 8 columns that start 16-byte aligned --
+    what functional.linear returns is passed as it is; anything else is copied into zero-padded rows"""
+    M, C = x2d.shape
+    if (x2d.dtype == torch.bfloat16 and x2d.stride(1) == 1 and x2d.stride(0) % 8 == 0 and x2d.stride(0) >= C and x2d.data_ptr() % 16 == 0):
+        return x2d
+    xp = torch.zeros((M, (C + 7) // 8 * 8), dtype=torch.bfloat16, device=x2d.device)
+    xp[:, :C] = x2d
+    return xp[:, :C]
+
+
 class SparseTokenLabelTarget:
     """The token-label target before it is densified: `idx` int32 and `val` fp32, both [B, 2 + N, K] (slot 0 ground truth, slot 1
     image level, slots 2.. tokens: SURVEY.md appendix A.2), and the label-smoothing strength.  dense() is what the reference's
@@ -122,6 +133,45 @@ class SparseTokenLabelTarget:
         if idx.shape != val.shape or idx.dim() != 3:
             raise ValueError("SparseTokenLabelTarget: idx and val must both be [B, 2 + N, K]")
         self.idx, self.val, self.smoothing = idx.to(torch.int32), val.float(), float(smoothing)
+
+    @classmethod
+    def from_logits(cls, labels, cls_logits, aux_logits, k=5, temperature=1.0, smoothing=0.1, out=None):
+        """The target a teacher network gives: labels int [B], cls_logits [B, C], aux_logits [B, N, C] (bf16; the last dimension may be a
+        padded view, as functional.linear returns it at a class count that is no multiple of 8) -> [B, 2 + N, k] with slot 0 the ground
+        truth ((label, 1.0), then (-1, 0.0): an index outside [0, C) adds nothing), slot 1 the top-k of softmax(cls_logits / temperature)
+        and slots 2.. those of every token -- two launches of ops.softmax_topk that write in place, equal logits by ascending class.
+        out: a target [B, 2 + N, k] of an earlier call to fill (nothing is allocated then; graph-capturable).
+        k <= 8: the mix-token class row of TokenLabelCrossEntropy carries 2 k pairs and the sparse kernel takes SPARSE_CE_MAX_PAIRS = 16 --
+        beyond that the loss would densify the target, which the wide label sets this exists for cannot do."""
+        from .. import ops
+        k = int(k)
+        if not 1 <= k <= SPARSE_CE_MAX_PAIRS // 2:
+            raise ValueError("from_logits: k must be 1 .. %d (2 k pairs of the mix-token class row), got %d" % (SPARSE_CE_MAX_PAIRS // 2, k))
+        if not float(temperature) > 0:
+            raise ValueError("from_logits: temperature must be positive")
+        if aux_logits.dim() != 3 or cls_logits.dim() != 2 or labels.dim() != 1:
+            raise ValueError("from_logits: labels [B], cls_logits [B, C], aux_logits [B, N, C]")
+        B, N, C = aux_logits.shape
+        if tuple(cls_logits.shape) != (B, C) or labels.shape[0] != B or k > C:
+            raise ValueError("from_logits: labels [B], cls_logits [B, C], aux_logits [B, N, C] with k <= C")
+        if not (cls_logits.is_cuda and aux_logits.is_cuda and labels.is_cuda):
+            raise ops.AutoProgHipError("from_logits: CUDA tensors (the HIP path has no CPU fallback)")
+        if out is None:
+            out = cls(torch.empty((B, 2 + N, k), dtype=torch.int32, device=aux_logits.device),
+                      torch.empty((B, 2 + N, k), dtype=torch.float32, device=aux_logits.device), smoothing)
+        elif not (isinstance(out, cls) and tuple(out.idx.shape) == (B, 2 + N, k) and out.idx.is_contiguous() and out.val.is_contiguous()
+                  and out.idx.device == aux_logits.device):
+            raise ValueError("from_logits: out must be a contiguous SparseTokenLabelTarget [%d, %d, %d] on the logits' device" % (B, 2 + N, k))
+        out.smoothing = float(smoothing)
+        out.idx[:, 0].fill_(-1)
+        out.idx[:, 0, 0].copy_(labels)
+        out.val[:, 0].zero_()
+        out.val[:, 0, 0].fill_(1.0)
+        fi, fv, S = out.idx.view(-1), out.val.view(-1), (2 + N) * k
+        inv_temp = 1.0 / float(temperature)
+        ops.softmax_topk(_chunked_rows(aux_logits.reshape(B * N, C)), C, k, inv_temp, fi[2 * k:], fv[2 * k:], S, k, N)
+        ops.softmax_topk(_chunked_rows(cls_logits), C, k, inv_temp, fi[k:], fv[k:], S, 0, 1)
+        return out
 
     def dense(self, classes):
         B, S, K = self.idx.shape

@@ -625,6 +625,24 @@ class VOLO(nn.Module):
             cls, x = block.forward_split(cls, x, pass_tokens=True)      # the tokens come back unchanged: one gradient chain, no fan-out
         return cls.unsqueeze(1), x
 
+    def forward_dense(self, x):
+        """-> (x_cls [B, classes], x_aux [B, N, classes]) in either mode: the forward without the mix-token swap and without the eval-mode
+        fusion x_cls + 0.5 * max_n x_aux -- what a teacher hands to SparseTokenLabelTarget.from_logits (prog/teacher.py).  The same calls in
+        the same order as forward(): in eval() under no_grad these are the forward-only block bodies, and x_cls + 0.5 * x_aux.max(1)[0] is
+        forward(x) bit for bit."""
+        if not self.return_dense:
+            raise ValueError("forward_dense needs a model built with return_dense=True (the aux head)")
+        x = self.forward_tokens(self.forward_embeddings(x))            # [B,N,C]
+        if self.post_network is not None:
+            cls, x = self.forward_cls(x)
+            cls = AF.layer_norm(cls, self.norm.weight, self.norm.bias, self.norm.eps)
+        else:
+            cls = None
+        x = AF.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
+        x_cls = AF.linear(cls[:, 0] if cls is not None else x[:, 0], self.head.weight, self.head.bias)
+        x_aux = AF.linear(x if cls is not None else x[:, 1:], self.aux_head.weight, self.aux_head.bias)
+        return x_cls, x_aux
+
     def forward(self, x):
         x = self.forward_embeddings(x)
         patch_h = patch_w = 0

@@ -792,6 +792,29 @@ def classify_stats(logits, labels, n_classes=None):
     return loss, rank
 
 
+def softmax_topk(logits, C, K, inv_temp, idx_out, val_out, o_sb, o_sn, rows_per_batch):
+    """row-wise softmax + top-K (include/autoprog_hip.h ap_softmax_topk_rows): logits bf16 [M, ld] with C valid columns (a padded view: unit
+    column stride, ld = its row stride, ld % 8 == 0); row r = (b, n), b = r // rows_per_batch, writes its K (class, score) pairs in descending
+    order -- equal logits by ascending class -- at idx_out / val_out (int32 / fp32, any shape) + b * o_sb + n * o_sn elements.  Nothing is
+    allocated; the caller's strides must keep every pair inside the two outputs (checked here against their sizes)."""
+    _req(idx_out, torch.int32, "idx_out"); _req(val_out, torch.float32, "val_out")
+    if not (torch.is_tensor(logits) and logits.is_cuda):
+        raise AutoProgHipError("logits must be a CUDA tensor (the HIP path has no CPU fallback)")
+    if logits.dtype != BF16 or logits.dim() != 2 or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise AutoProgHipError("softmax_topk: logits bf16 [M, >= C] with unit column stride")
+    M = logits.shape[0]
+    ld = logits.stride(0)                     # (a row stride that is no multiple of 8 or below C is the library's AP_ERR_SHAPE)
+    C, K, rows_per_batch = int(C), int(K), int(rows_per_batch)
+    if C > logits.shape[1]:
+        raise AutoProgHipError("softmax_topk: C = %d valid columns of %d" % (C, logits.shape[1]))
+    if M > 0 and rows_per_batch > 0 and K > 0:
+        last = ((M - 1) // rows_per_batch) * int(o_sb) + min(M - 1, rows_per_batch - 1) * int(o_sn) + K
+        if int(o_sb) < 0 or int(o_sn) < 0 or last > min(idx_out.numel(), val_out.numel()):
+            raise AutoProgHipError("softmax_topk: the output strides reach element %d of %d" % (last, min(idx_out.numel(), val_out.numel())))
+    check(lib.ap_softmax_topk_rows(logits.data_ptr(), ld, C, K, float(inv_temp), idx_out.data_ptr(), val_out.data_ptr(), int(o_sb), int(o_sn),
+                                   rows_per_batch, M, _stream()), "ap_softmax_topk_rows")
+
+
 def soft_ce_fwd_bwd(logits, C, target, t_sb, t_sc, t_sn, rows_per_batch, grad_scale, mix_lam=1.0, mix_batches=0, mix_lam_ptr=None):
     """returns (row_loss fp32 [M], dlogits bf16 like logits); mix_batches = B: target of batch b is lam*t[b] + (1-lam)*t[B-1-b].
     mix_lam_ptr: device address of lam (overrides mix_lam: graph.StepScalars)"""

@@ -32,7 +32,7 @@ class AutoProgDriver:
     def __init__(self, model, loss_fn, optimizer, reducer, get_batch, r_list, l_list, dp_list, grow_epochs, steps_per_epoch,
                  search_epochs=2, auto_grow=True, probe_batches=4, time_steps=4, seed=0, log=None, original_batch_splits=1,
                  r_max=None, dist_bn="", use_graphs=False, graph_after=2, clip_grad=None, clip_mode="norm", get_val_batches=None,
-                 batch_prep=None, re_list=None, skip_nonfinite=False):
+                 batch_prep=None, re_list=None, skip_nonfinite=False, teacher=None):
         """model: supernet sized for l_list[-1] (e.g. volo_h12_l18); optimizer: FlatAdamWEma over it; reducer: its
         GradientBucketReducer; r_list / l_list / dp_list / grow_epochs: the stage schedule (prog/progressive.py:4-31);
         get_batch(r): a training batch (images at ANY size -- the stem resizes to r -- and a token-label target for r // 16).
@@ -63,7 +63,19 @@ class AutoProgDriver:
         skip_nonfinite: every update, eager or replayed, runs FlatAdamWEma.step(skip_nonfinite=True): a step whose gradient holds an inf or a
         NaN leaves the weights and the Adam moments alone, as apex's loss scaler does in the reference (prog/scaler.py:20-26).  Nothing is
         read back per step; where an epoch ends (the loss read-back) guard_counts() is read once, the epoch's `history` entry and log line
-        get `skipped_steps`, and an epoch that skipped anything also gets `worst_grads`: the three worst entries of grad_health()."""
+        get `skipped_steps`, and an epoch that skipped anything also gets `worst_grads`: the three worst entries of grad_health().
+        teacher: a prog.teacher.TeacherLabeler.  Integer labels [B] from get_batch then become teacher(images, labels, r), the
+        SparseTokenLabelTarget of the teacher's top-k scores on this batch at the step's resolution (after batch_prep, when there is one:
+        the teacher sees the erased, normalised pixels); any other target passes as it is.  Under use_graphs the labeler runs eagerly in
+        front of every replay and the graph's copy of the target is refreshed as for any sparse target.  Token labels are not cut with
+        the images: a batch_prep with Mixup / CutMix enabled is refused here.  None (default): nothing changes."""
+        if teacher is not None:
+            if batch_prep is not None and getattr(batch_prep, "mix_enabled", False):
+                raise ValueError("a teacher's token labels cannot follow Mixup / CutMix: build the batch_prep with mixup_alpha = cutmix_alpha = 0")
+            tc, mc = getattr(teacher, "num_classes", None), getattr(model, "num_classes", None)
+            if tc is not None and mc is not None and int(tc) != int(mc):
+                raise ValueError("the teacher labels %d classes, the model has %d" % (tc, mc))
+        self.teacher = teacher
         self.skip_nonfinite = bool(skip_nonfinite)
         self._skipped_seen = 0
         if re_list is not None and (batch_prep is None or len(re_list) != len(r_list)):
@@ -72,6 +84,8 @@ class AutoProgDriver:
         self._raw_get_batch = get_batch
         if batch_prep is not None:
             get_batch = self._prepared_batch
+        if teacher is not None:
+            self._untaught_get_batch, get_batch = get_batch, self._taught_batch
         self.get_val_batches = get_val_batches
         self.use_graphs, self.graph_after = bool(use_graphs), int(graph_after)
         self.clip_grad, self.clip_mode = clip_grad, clip_mode
@@ -95,8 +109,14 @@ class AutoProgDriver:
         images, target = self._raw_get_batch(*a)
         if torch.is_tensor(images) and images.dtype == torch.uint8:
             images = self.batch_prep.prep(images)
-            if torch.is_tensor(target) and target.dim() == 1 and not target.dtype.is_floating_point:
+            if self.teacher is None and torch.is_tensor(target) and target.dim() == 1 and not target.dtype.is_floating_point:
                 target = images.target(target)
+        return images, target
+
+    def _taught_batch(self, r, *a):
+        images, target = self._untaught_get_batch(r, *a)
+        if torch.is_tensor(target) and target.dim() == 1 and not target.dtype.is_floating_point:
+            target = self.teacher(images, target, r)
         return images, target
 
     # ------------------------------------------------------------------ elastic plumbing

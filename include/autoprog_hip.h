@@ -346,6 +346,18 @@ int ap_mix_token_swap_dev(const ap_bf16* x, ap_bf16* y, int B, int H, int W, int
  * rows = 0 succeeds without a launch.  No atomics, no host synchronisation. */
 int ap_classify_stats(const ap_bf16* logits, int ld, int n_classes, const int64_t* labels, float* loss, int* rank, int64_t rows,
                       ap_stream_t stream);
+/* Row-wise softmax + top-K (additive in ABI version 7; csrc/topk.hip): the (class, score) pairs of a token-label target from a teacher's
+ * logits.  logits bf16 [M, ld], columns 0 .. C-1 valid (C .. ld-1 are never interpreted: they may hold NaN or inf).  For row r = (b, n),
+ * b = r / rows_per_batch, n = r % rows_per_batch, o = b * o_sb + n * o_sn and k < K:
+ *   idx[o + k] = the class with the k-th largest logit; EQUAL logits rank by ascending class (torch.sort(descending=True, stable=True))
+ *   val[o + k] = softmax(inv_temp * x)[idx[o + k]] over all C columns (fp32, maximum subtracted, fixed reduction order: bit-reproducible)
+ * so the K entries are in descending order.  The strides let one launch write straight into slots of a [B, 2 + N, K] target.
+ * ld % 8 == 0, logits 16-byte aligned, 1 <= K <= min(16, C), C <= ld, rows_per_batch > 0, 0 < inv_temp < inf (AP_ERR_SHAPE otherwise);
+ * ld > 65 536: AP_ERR_UNSUPPORTED (rows beyond 1024 columns are staged in LDS, 2 B per column).  M = 0 succeeds without a launch.
+ * A NaN among the valid columns or a row of all -inf gives unspecified values; the indices stay inside [0, C).  The row is read from
+ * global memory once.  No atomics, no workspace, no allocation, no host synchronisation. */
+int ap_softmax_topk_rows(const ap_bf16* logits, int ld, int C, int K, float inv_temp, int* idx, float* val, int64_t o_sb, int64_t o_sn,
+                         int rows_per_batch, int64_t M, ap_stream_t stream);
 int ap_soft_ce_fwd_bwd(const ap_bf16* logits, int ldx, const float* target, int64_t t_sb,
                        int64_t t_sc, int64_t t_sn, int rows_per_batch, float* row_loss,
                        ap_bf16* dlogits, float grad_scale, int64_t M, int C,
