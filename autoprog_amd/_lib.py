@@ -170,6 +170,8 @@ _SIGNATURES["ap_grad_health"] = (_I, [_P, _L, _P, _I, _P, _P, _P, _F, _F, _P, ct
 _SIGNATURES["ap_adamw_ema_step_guarded"] = (_I, _SIGNATURES["ap_adamw_ema_step"][1][:-1] + [_P, _P])
 # row-wise softmax + top-K (csrc/topk.hip): ap_softmax_topk_rows(logits, ld, C, K, inv_temp, idx, val, o_sb, o_sn, rows_per_batch, M, stream)
 _SIGNATURES["ap_softmax_topk_rows"] = (_I, [_P, _I, _I, _I, _F, _P, _P, _L, _L, _I, _L, _P])
+# distillation loss (csrc/distill.hip): ap_distill_fwd_bwd(student, ld_s, teacher, ld_t, C, mode, inv_temp, row_loss, dstudent, grad_scale, M, stream)
+_SIGNATURES["ap_distill_fwd_bwd"] = (_I, [_P, _I, _P, _I, _I, _I, _F, _P, _P, _F, _L, _P])
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 EXPECTED_ABI = 7                     # ap_abi_version() of the library these ctypes Structures mirror (include/autoprog_hip.h)

@@ -1072,6 +1072,41 @@ class MixedLabelCEFn(torch.autograd.Function):
         return (out if out.shape[1] == ctx.C else out[:, :ctx.C]), None, None, None, None
 
 
+class DistillCEFn(torch.autograd.Function):
+    """The distillation term of DeiT's DistillationLoss (and its sum with the base term) on ops.distill_fwd_bwd: loss and d(loss)/d(student
+    logits) from one read of the student and teacher rows, where the published code runs two log_softmax, an exp, a kl_div (or an argmax and a
+    cross_entropy), a reduction and their backward.  mode 0: soft, T^2 KL(softmax(teacher / T) || softmax(student / T)); 1: hard, CE against
+    the teacher's argmax.  -> base_weight * base + weight * sum_r row_loss[r] in one launch of ops.loss_combine (base: a scalar of the
+    graph, or None); `weight` travels into the kernel as grad_scale, so backward is ONE row-scale by the incoming scalar.  No gradient
+    flows to the teacher."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, mode, inv_temp, weight, base, base_weight):
+        M, C = student.shape
+        ld = ops.round_up(C, 8)
+        if ld != C or not student.is_contiguous():
+            xp = torch.zeros((M, ld), dtype=BF16, device=student.device)
+            xp[:, :C] = student
+        else:
+            xp = student
+        if not (teacher.stride(1) == 1 and teacher.stride(0) % 8 == 0 and teacher.stride(0) >= C and teacher.data_ptr() % 16 == 0):
+            tp = torch.zeros((M, ld), dtype=BF16, device=teacher.device)          # (a padded view, as functional.linear returns it, is taken as it is)
+            tp[:, :C] = teacher
+            teacher = tp[:, :C]
+        row_loss, dl = ops.distill_fwd_bwd(xp, C, teacher, mode, inv_temp, weight)
+        ctx.save_for_backward(dl)
+        ctx.C, ctx.base_weight = C, float(base_weight)
+        if base is None:
+            return ops.loss_combine(row_loss, weight)
+        return ops.loss_combine(base.detach().reshape(1).float(), base_weight, row_loss, weight)
+
+    @staticmethod
+    def backward(ctx, g):
+        (dl,) = ctx.saved_tensors
+        out = ops.row_scale(dl, g.reshape(1).float().contiguous(), dl.shape[0])
+        return (out if out.shape[1] == ctx.C else out[:, :ctx.C]), None, None, None, None, (g * ctx.base_weight if ctx.needs_input_grad[5] else None), None
+
+
 class OutlookCoreFn(torch.autograd.Function):
     """unfold -> softmax -> attn@v -> fold (models/volo.py:83-98) on v [B,H,W,C], logits [B*h*w, ld]."""
 

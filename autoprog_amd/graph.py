@@ -228,6 +228,9 @@ def _copy_images(dst, src):
 def _clone_target(t, images=None):
     from .data import MixedLabelTarget, PreparedBatch
     from .loss.cross_entropy import SparseTokenLabelTarget
+    from .loss.distillation import DistillTarget
+    if isinstance(t, DistillTarget):
+        raise NotImplementedError("a DistillTarget cannot be captured yet: run the distillation step eagerly (use_graphs=False)")
     if isinstance(t, SparseTokenLabelTarget):
         return SparseTokenLabelTarget(t.idx.clone(), t.val.clone(), t.smoothing)
     if isinstance(t, MixedLabelTarget):

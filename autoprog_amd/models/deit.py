@@ -115,6 +115,13 @@ class VisionTransformer(nn.Module):
             blk.set_sample_config(is_identity_layer=i in skip)
         return skip
 
+    def set_drop_path_rate(self, rate):
+        """per-block DropPath rates of the CURRENT elastic config, as VOLO.set_drop_path_rate assigns them: rate * (index among the active
+        blocks) / (active blocks - 1) -- what prog.driver.AutoProgDriver calls at every configuration change"""
+        active = [b for b in self.blocks if not b.is_identity_layer]
+        for i, blk in enumerate(active):
+            blk.drop_prob = float(rate) * i / max(len(active) - 1, 1) if rate else 0.0
+
     def interpolate_pos_encoding(self, n_patches, n_extra):
         """elastic resolution for AutoProg-DeiT (BASELINE configs[3]: r in {128..224}; build-defined): the
         class / distillation embeddings are kept, the patch-grid part is resized exactly like VOLO.interpolate_pos_encoding

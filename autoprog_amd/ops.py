@@ -848,6 +848,36 @@ def soft_ce_sparse_fwd_bwd(logits, C, idx, val, p_sb, p_sn, rows_per_batch, smoo
     return row_loss, dlogits
 
 
+def _padded_rows(t, C, name):
+    """a bf16 CUDA matrix [M, >= C] with unit column stride -> its leading dimension (a padded view is taken as it is; a row stride
+    that is no multiple of 8 or below C, or a misaligned base, is the library's AP_ERR_SHAPE)"""
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise AutoProgHipError("%s must be a CUDA tensor (the HIP path has no CPU fallback)" % name)
+    if t.dtype != BF16 or t.dim() != 2 or t.shape[1] < C or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise AutoProgHipError("%s must be bf16 [M, >= %d] with unit column stride" % (name, C))
+    ld = t.stride(0)
+    if t.shape[0] <= 1 and (ld < t.shape[1] or ld % 8):         # (the row stride of a single row means nothing)
+        ld = t.shape[1]
+    return ld
+
+
+def distill_fwd_bwd(student, C, teacher, mode, inv_temp, grad_scale):
+    """distillation loss of student rows against teacher rows (include/autoprog_hip.h ap_distill_fwd_bwd): student / teacher bf16 [M, >= C]
+    with C valid columns (padded views: unit column stride, ld = the row stride, ld % 8 == 0).  mode 0 (soft): row_loss = T^2 KL(p_t || p_s)
+    at T = 1 / inv_temp, dstudent = grad_scale * T * (p_s - p_t); mode 1 (hard): CE against the teacher's argmax (equal logits: the smallest
+    class), dstudent = grad_scale * (softmax(x_s) - onehot).  -> (row_loss fp32 [M], dstudent bf16 [M, ld_s], columns C .. ld_s-1 zero)"""
+    C = int(C)
+    ld_s, ld_t = _padded_rows(student, C, "student"), _padded_rows(teacher, C, "teacher")
+    M = student.shape[0]
+    if teacher.shape[0] != M or teacher.device != student.device:
+        raise AutoProgHipError("distill_fwd_bwd: student and teacher must have the same rows on one device")
+    row_loss = torch.empty(M, dtype=torch.float32, device=student.device)
+    dstudent = torch.empty((M, ld_s), dtype=BF16, device=student.device)
+    check(lib.ap_distill_fwd_bwd(student.data_ptr(), ld_s, teacher.data_ptr(), ld_t, C, int(mode), float(inv_temp), row_loss.data_ptr(),
+                                 dstudent.data_ptr(), float(grad_scale), M, _stream()), "ap_distill_fwd_bwd")
+    return row_loss, dstudent
+
+
 def row_scale(x, scale, rows_per_scale):
     _req(x, BF16, "x"); _req(scale, torch.float32, "scale")
     C = x.shape[-1]

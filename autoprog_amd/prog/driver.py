@@ -68,7 +68,11 @@ class AutoProgDriver:
         SparseTokenLabelTarget of the teacher's top-k scores on this batch at the step's resolution (after batch_prep, when there is one:
         the teacher sees the erased, normalised pixels); any other target passes as it is.  Under use_graphs the labeler runs eagerly in
         front of every replay and the graph's copy of the target is refreshed as for any sparse target.  Token labels are not cut with
-        the images: a batch_prep with Mixup / CutMix enabled is refused here.  None (default): nothing changes."""
+        the images: a batch_prep with Mixup / CutMix enabled is refused here.  None (default): nothing changes.
+        A prog.teacher.TeacherLogits passes the same way: integer labels become the loss.DistillTarget (the labels, or the MixedLabelTarget
+        of a prepared batch, and the teacher's class logits) that loss.DistillationLoss takes on a distilled DeiT.  Eager steps only: under
+        use_graphs the capture of a DistillTarget is refused (NotImplementedError from graph.GraphedStep).  The refusal of a mixing
+        batch_prep holds for it too (distillation on a Mixup / CutMix batch works when the loss is called directly)."""
         if teacher is not None:
             if batch_prep is not None and getattr(batch_prep, "mix_enabled", False):
                 raise ValueError("a teacher's token labels cannot follow Mixup / CutMix: build the batch_prep with mixup_alpha = cutmix_alpha = 0")

@@ -51,3 +51,45 @@ class TeacherLabeler:
         out = SparseTokenLabelTarget.from_logits(labels, x_cls, x_aux, self.k, self.temperature, self.smoothing, out=self._targets.get(key))
         self._targets[key] = out
         return out
+
+
+class TeacherLogits:
+    """The teacher of DeiT's distillation objective (loss.DistillationLoss), on the device, every step: the teacher sees the batch the
+    student sees and its class logits travel to the loss beside the labels.
+
+        teacher = TeacherLogits(create_model("deit_small_patch16_224").cuda(), num_classes=student.num_classes)
+        driver = AutoProgDriver(student, DistillationLoss(SoftTargetCrossEntropy(), "hard"), ..., teacher=teacher)
+    """
+
+    def __init__(self, teacher, num_classes=None):
+        """teacher: any nn.Module whose eval() forward returns [B, C] logits on the device; it is put in eval() and only ever run under
+        no_grad.  num_classes: the student's class count, when given it must be the teacher's."""
+        tc = getattr(teacher, "num_classes", None)
+        if num_classes is not None and tc is not None and int(num_classes) != int(tc):
+            raise ValueError("TeacherLogits: the teacher has %d classes, the student %d" % (int(tc), int(num_classes)))
+        self.num_classes = int(tc) if tc is not None else (int(num_classes) if num_classes is not None else None)
+        self.teacher = teacher.eval()
+
+    @torch.no_grad()
+    def __call__(self, images, labels, r):
+        """images: fp32 [B, 3, H, W] or a data.PreparedBatch, mixed or not (the teacher then sees the mixed, erased, normalised pixels the
+        student sees, and the base target is the batch's own: images.target(labels)); labels: int [B]; r: the student's stage resolution --
+        a VOLO teacher resizes the batch to it as the student's stem does, any other teacher sees the images as given (a DeiT interpolates
+        its position embedding).  -> loss.DistillTarget(base, the teacher's logits [B, C])"""
+        from ..data import PreparedBatch
+        from ..loss.distillation import DistillTarget
+        t = self.teacher
+        if t.training:
+            t.eval()
+        pe = getattr(t, "patch_embed", None)
+        if pe is not None and hasattr(pe, "resize_to") and hasattr(pe, "resize_in_eval"):
+            pe.resize_to, pe.resize_in_eval = int(r), True
+        logits = t(images)
+        if not (torch.is_tensor(logits) and logits.dim() == 2):
+            raise ValueError("TeacherLogits: the teacher's eval() forward must return [B, C] logits")
+        if self.num_classes is not None and logits.shape[1] != self.num_classes:
+            raise ValueError("TeacherLogits: the teacher returned %d classes, %d were announced" % (logits.shape[1], self.num_classes))
+        if torch.is_tensor(labels) and not labels.is_cuda and logits.is_cuda:
+            labels = labels.to(logits.device)
+        base = images.target(labels) if isinstance(images, PreparedBatch) else labels
+        return DistillTarget(base, logits)

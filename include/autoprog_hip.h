@@ -358,6 +358,26 @@ int ap_classify_stats(const ap_bf16* logits, int ld, int n_classes, const int64_
  * global memory once.  No atomics, no workspace, no allocation, no host synchronisation. */
 int ap_softmax_topk_rows(const ap_bf16* logits, int ld, int C, int K, float inv_temp, int* idx, float* val, int64_t o_sb, int64_t o_sn,
                          int rows_per_batch, int64_t M, ap_stream_t stream);
+/* Distillation loss of a student row against a teacher row, loss and gradient from one read of both (additive in ABI version 7;
+ * csrc/distill.hip): DeiT's DistillationLoss.  student bf16 [M, ld_s], teacher bf16 [M, ld_t], columns 0 .. C-1 of both valid (C .. ld-1
+ * are never interpreted: they may hold NaN or inf).  p_s = softmax(inv_temp * x_s), p_t = softmax(inv_temp * x_t), both fp32 with the
+ * maximum subtracted, T = 1 / inv_temp:
+ *   mode 0 (soft)   row_loss[r] = T^2 * sum_c p_t[c] (log p_t[c] - log p_s[c])        dstudent[r, c] = grad_scale * T * (p_s[c] - p_t[c])
+ *   mode 1 (hard)   row_loss[r] = logsumexp(x_s) - x_s[c*]                             dstudent[r, c] = grad_scale * (softmax(x_s)[c] - [c == c*])
+ *                   c* = the class of the largest teacher logit, EQUAL logits resolve to the smallest class (the tie rule of
+ *                   ap_softmax_topk_rows; -0 equals +0); inv_temp is ignored.
+ * A teacher row that equals the student row gives exactly zero loss in soft mode, and a gradient of at most 2^-24 * grad_scale * T * p_s[c]
+ * (the rounding residue of one product).  dstudent has leading dimension ld_s; its
+ * columns C .. ld_s-1 are written as zero bits.  No gradient for the teacher.
+ * ld_s % 8 == 0, ld_t % 8 == 0, student / teacher / dstudent 16-byte aligned, 1 <= C <= min(ld_s, ld_t), mode 0 or 1, 0 < inv_temp < inf in
+ * soft mode (AP_ERR_SHAPE otherwise); a leading dimension above 65 536: AP_ERR_UNSUPPORTED.  M = 0 succeeds without a launch.
+ * The kernel is selected by round_up(C, 8) alone, so a padded operand gives the bits of the compact one: up to 1024 columns both rows sit in
+ * a wave's registers; wider rows are staged in LDS -- both operands are read from global memory exactly once up to 40 704 columns; beyond
+ * (soft mode) the student row is staged and read once and the teacher row is read in each of the three walks, the later two from L2.
+ * A NaN among the valid columns gives unspecified values and no out-of-range access.  Fixed reduction order: two runs are bit-identical.
+ * No atomics, no workspace, no allocation, no host synchronisation. */
+int ap_distill_fwd_bwd(const ap_bf16* student, int ld_s, const ap_bf16* teacher, int ld_t, int C, int mode, float inv_temp,
+                       float* row_loss, ap_bf16* dstudent, float grad_scale, int64_t M, ap_stream_t stream);
 int ap_soft_ce_fwd_bwd(const ap_bf16* logits, int ldx, const float* target, int64_t t_sb,
                        int64_t t_sc, int64_t t_sn, int rows_per_batch, float* row_loss,
                        ap_bf16* dlogits, float grad_scale, int64_t M, int C,
