@@ -675,7 +675,7 @@ int ap_resample_grid(const float* in, int hi, int wi, const float* wy, const flo
 }
 int ap_sum_reps_acc(const ap_bf16* x, float* out, int64_t n, int reps, ap_stream_t stream) {
     if (!x || !out) return AP_ERR_NULL;
-    if ((n & 7) || reps <= 0) return AP_ERR_SHAPE;
+    if ((n & 7) || reps <= 0 || reps > AP_SUM_REPS_MAX) return AP_ERR_SHAPE;        // (gridDim.y = ceil(reps / 16) <= 65 535)
     if (n == 0) return AP_OK;
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_sum_reps_acc, dim3(grid_for(n / 8), (reps + SR_CHUNK - 1) / SR_CHUNK), dim3(256), 0, (hipStream_t)stream, x, out, n / 8, reps);
@@ -714,7 +714,7 @@ int ap_avgpool2_bwd_acc(const ap_bf16* dpooled, ap_bf16* dx, int B, int H, int W
 }
 int ap_colsum_acc(const ap_bf16* A, int lda, float* out, int M, int N, ap_stream_t stream) {
     if (!A || !out) return AP_ERR_NULL;
-    if ((lda & 7) || M <= 0 || N <= 0 || lda < N) return AP_ERR_SHAPE;
+    if ((lda & 7) || M <= 0 || N <= 0 || lda < N || M > AP_MAX_ROWS) return AP_ERR_SHAPE;
     const int gx = (N + 255) / 256;
     int gy = (M + 255) / 256;                         // >= 256 rows per block
     const int cap = (2048 + gx - 1) / gx;

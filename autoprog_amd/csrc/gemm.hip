@@ -999,7 +999,7 @@ static int ws_try(const bf16_t* A, int lda, const bf16_t* B, int ldb, bf16_t* C,
 int ap_gemm_nt(const ap_bf16* A, int lda, const ap_bf16* B, int ldb, ap_bf16* C, int ldc, int M, int N, int K,
                const ap_gemm_epilogue* epi, ap_stream_t stream) {
     if (!A || !B || !C) return AP_ERR_NULL;
-    if (M <= 0 || N <= 0 || K <= 0) return AP_ERR_SHAPE;
+    if (M <= 0 || N <= 0 || K <= 0 || M > AP_MAX_ROWS) return AP_ERR_SHAPE;          // (tile counts (M + tile - 1) / tile are formed in int)
     if ((K & 7) || (lda & 7) || (ldb & 7) || lda < K || ldb < K || ldc < N) return AP_ERR_SHAPE;
     EpiArgs ep = {nullptr, 0, nullptr, nullptr, nullptr, 1, nullptr, 0, 0, nullptr, {0, 0, 0, 0, 0, 0u, 0u}, nullptr, nullptr, nullptr};
     { const char* e = getenv("AP_GEMM_DBG"); if (e) ep.dbg = atoi(e); }
@@ -1122,7 +1122,7 @@ int ap_gemm_nt(const ap_bf16* A, int lda, const ap_bf16* B, int ldb, ap_bf16* C,
 int ap_gemm_nt_fp8(const unsigned char* A, int lda, const unsigned char* B, int ldb, ap_bf16* C, int ldc, int M, int N, int K,
                    const float* dq_a, const float* dq_b, const ap_gemm_epilogue* epi, ap_stream_t stream) {
     if (!A || !B || !C || !dq_a || !dq_b) return AP_ERR_NULL;
-    if (M <= 0 || N <= 0 || K <= 0) return AP_ERR_SHAPE;
+    if (M <= 0 || N <= 0 || K <= 0 || M > AP_MAX_ROWS) return AP_ERR_SHAPE;          // (tile counts (M + tile - 1) / tile are formed in int)
     if ((K & 15) || (lda & 15) || (ldb & 15) || lda < K || ldb < K || ldc < N) return AP_ERR_SHAPE;       // 16-byte chunks of e4m3
     EpiArgs ep = {nullptr, 0, nullptr, nullptr, nullptr, 1, nullptr, 0, 0, nullptr, {0, 0, 0, 0, 0, 0u, 0u}, dq_a, dq_b, nullptr};
     if (epi) {
@@ -1167,7 +1167,7 @@ int ap_gemm_nt_patch_bn(const ap_bf16* A, const ap_bn_input* a_bn, const ap_bf16
                         const float* bias, const ap_patch_map* map, int side, ap_stream_t stream) {
     if (!A || !B || !C || !map) return AP_ERR_NULL;
     if (a_bn && (side != 1 || !a_bn->mean || !a_bn->rstd || !a_bn->gamma || !a_bn->beta)) return AP_ERR_NULL;
-    if (M <= 0 || N <= 0 || K <= 0 || (K & 7) || (ldb & 7) || ldb < K) return AP_ERR_SHAPE;
+    if (M <= 0 || N <= 0 || K <= 0 || M > AP_MAX_ROWS || (K & 7) || (ldb & 7) || ldb < K) return AP_ERR_SHAPE;
     EpiArgs ep = {nullptr, 0, nullptr, nullptr, nullptr, 1, nullptr, 0, 0, nullptr, {0, 0, 0, 0, 0, 0u, 0u}, nullptr, nullptr, nullptr};
     if (!patch_map_device(map, ep.pm)) return AP_ERR_SHAPE;
     if ((int64_t)M >= (int64_t)(0xFFFFFFFFu / (unsigned)map->group)) return AP_ERR_SHAPE;       // exactness bound of the magic division
@@ -1189,7 +1189,7 @@ int ap_gemm_nt_patch_bn(const ap_bf16* A, const ap_bn_input* a_bn, const ap_bf16
 int ap_gemm_tn_acc(const ap_bf16* A, int lda, const ap_bf16* B, int ldb, float* C, int ldc, int M, int N1, int N2,
                    float* colsum_A, ap_stream_t stream) {
     if (!A || !B || !C) return AP_ERR_NULL;
-    if (M <= 0 || N1 <= 0 || N2 <= 0) return AP_ERR_SHAPE;
+    if (M <= 0 || N1 <= 0 || N2 <= 0 || M > AP_MAX_ROWS) return AP_ERR_SHAPE;
     if ((lda & 7) || (ldb & 7) || lda < N1 || ldb < N2 || ldc < N2) return AP_ERR_SHAPE;
     const int t1 = (N1 + 127) / 128, t2 = (N2 + 127) / 128;
     int full_steps = 0;
@@ -1221,7 +1221,7 @@ static int tn_validate(const ap_tn_problem* problems, int count) {
     for (int i = 0; i < count; ++i) {
         const ap_tn_problem& q = problems[i];
         if (!q.A || !q.B || !q.C) return AP_ERR_NULL;
-        if (q.M <= 0 || q.N1 <= 0 || q.N2 <= 0) return AP_ERR_SHAPE;
+        if (q.M <= 0 || q.N1 <= 0 || q.N2 <= 0 || q.M > AP_MAX_ROWS) return AP_ERR_SHAPE;
         if ((q.lda & 7) || q.lda < q.N1 || q.ldc < q.N2) return AP_ERR_SHAPE;
         if (!q.b_patch && ((q.ldb & 7) || q.ldb < q.N2)) return AP_ERR_SHAPE;         // patch-addressed B has no leading dimension
     }
@@ -1242,7 +1242,7 @@ static int tn_plan(const ap_tn_problem* problems, int count, TnGroup& grp, int& 
     for (int i = 0; i < count; ++i) {
         const ap_tn_problem& q = problems[i];
         if (!q.A || !q.B || !q.C) return AP_ERR_NULL;
-        if (q.M <= 0 || q.N1 <= 0 || q.N2 <= 0) return AP_ERR_SHAPE;
+        if (q.M <= 0 || q.N1 <= 0 || q.N2 <= 0 || q.M > AP_MAX_ROWS) return AP_ERR_SHAPE;
         if ((q.lda & 7) || q.lda < q.N1 || q.ldc < q.N2) return AP_ERR_SHAPE;
         if (!q.b_patch && ((q.ldb & 7) || q.ldb < q.N2)) return AP_ERR_SHAPE;         // patch-addressed B has no leading dimension
         const int steps = (q.M + TM - 1) / TM;
@@ -1541,7 +1541,7 @@ static int tf_plan(const ap_tn8_problem* problems, int count, TfGroup& grp, int&
     for (int i = 0; i < count; ++i) {
         const ap_tn8_problem& q = problems[i];
         if (!q.A || !q.B || !q.C || !q.dq_a || !q.dq_b) return AP_ERR_NULL;
-        if (q.M <= 0 || q.N1 <= 0 || q.N2 <= 0) return AP_ERR_SHAPE;
+        if (q.M <= 0 || q.N1 <= 0 || q.N2 <= 0 || q.M > AP_MAX_ROWS) return AP_ERR_SHAPE;
         if ((q.lda & 15) || (q.ldb & 15) || q.lda < q.N1 || q.ldb < q.N2 || q.ldc < q.N2) return AP_ERR_SHAPE;
         if ((reinterpret_cast<uintptr_t>(q.A) & 15) || (reinterpret_cast<uintptr_t>(q.B) & 15)) return AP_ERR_SHAPE;
         if (q.N1 % 128 || q.N2 % 128 || (q.a_fmt != AP_FP8_E5M2 && q.a_fmt != AP_FP8_E4M3)) return AP_ERR_UNSUPPORTED;

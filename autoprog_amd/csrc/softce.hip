@@ -597,7 +597,7 @@ extern "C" int ap_soft_ce_fwd_bwd_dev(const ap_bf16* logits, int ldx, const floa
                                       float grad_scale, int64_t M, int C, float mix_lam, int mix_batches, const float* mix_lam_dev, ap_stream_t stream) {
     if (!logits || !target || !row_loss || !dlogits) return AP_ERR_NULL;
     if (mix_batches != 0 && (mix_batches < 0 || (int64_t)mix_batches * rows_per_batch != M)) return AP_ERR_SHAPE;
-    if (C <= 0 || ldx < C || (ldx & 7) || rows_per_batch <= 0 || M % rows_per_batch) return AP_ERR_SHAPE;
+    if (C <= 0 || ldx < C || (ldx & 7) || rows_per_batch <= 0 || M < 0 || M % rows_per_batch) return AP_ERR_SHAPE;
     if (ldx > 64 * 2 * CE_MAXV && t_sn == 1 && rows_per_batch > 1 && C <= CE_WIDE_CM_MAXC && ldx <= 128 * 20)
         return ce_wide_cm_launch(logits, ldx, target, t_sb, t_sc, t_sn, rows_per_batch, row_loss, dlogits, grad_scale, M, C, mix_lam, mix_batches, mix_lam_dev, stream);
     if (ldx > 64 * 2 * CE_MAXV)
@@ -606,6 +606,7 @@ extern "C" int ap_soft_ce_fwd_bwd_dev(const ap_bf16* logits, int ldx, const floa
     if (M == 0) return AP_OK;
     const int tiles = (rows_per_batch + CE_TN - 1) / CE_TN;
     const int64_t blocks = (M / rows_per_batch) * tiles;
+    if (blocks > 0x7fffffffLL) return AP_ERR_SHAPE;
     const size_t lds = (size_t)CE_TN * (C | 1) * sizeof(float);
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_soft_ce, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, logits, ldx, target, t_sb, t_sc,
@@ -630,6 +631,7 @@ extern "C" int ap_soft_ce_sparse_fwd_bwd_dev(const ap_bf16* logits, int ldx, con
         return ce_wide_launch<false>(logits, ldx, nullptr, 0, 0, 0, idx, val, K, p_sb, p_sn, smoothing, rows_per_batch, row_loss, dlogits, grad_scale, M, C,
                                      mix_lam, mix_batches, mix_lam_dev, stream);
     if (M == 0) return AP_OK;
+    if ((M + 4 * CE_SR - 1) / (4 * CE_SR) > 0x7fffffffLL) return AP_ERR_SHAPE;
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_soft_ce_sparse, dim3((unsigned)((M + 4 * CE_SR - 1) / (4 * CE_SR))), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const bf16_t*>(logits), ldx,
                        idx, val, K, p_sb, p_sn, rows_per_batch, smoothing, row_loss, reinterpret_cast<bf16_t*>(dlogits), grad_scale, M, C, mix_lam, mix_batches, mix_lam_dev);

@@ -37,6 +37,13 @@ enum {
     AP_ERR_NULL = -4          /* a required pointer is NULL                         */
 };
 
+/* Operand sizes ("Operand size limits").  Row, image and element counts passed as int64_t are good for any operand that fits device
+ * memory: every address is formed in 64 bits, and the kernels whose grid grows with the row count return AP_ERR_SHAPE beyond 2^31 - 1
+ * workgroups (the losses, top-K, the distillation loss, ap_classify_stats: 2^31 - 1 rows or more).  Row counts passed as int (M of the
+ * GEMMs, of ap_gemm_tn_acc* / ap_gemm_tn8_acc_grouped and of ap_colsum_acc) must not exceed AP_MAX_ROWS: the tile counts (M + tile - 1) / tile
+ * are formed in int.  AP_ERR_SHAPE beyond. */
+#define AP_MAX_ROWS 0x7fffff00       /* 2^31 - 256 */
+
 int ap_abi_version(void);
 const char* ap_error_string(int code);
 
@@ -412,7 +419,9 @@ int ap_row_scale(const ap_bf16* x, const float* scale, ap_bf16* y, int64_t M, in
                  int rows_per_scale, ap_stream_t stream);
 /* y = a + b (b broadcast over the leading `reps` copies when b_elems < n) */
 int ap_add_bcast(const ap_bf16* a, const ap_bf16* b, ap_bf16* y, int64_t n, int64_t b_elems, ap_stream_t stream);
-/* out[i] += sum over reps of x[r*n + i]  (fp32 accumulate; gradient of a broadcast add) */
+/* out[i] += sum over reps of x[r*n + i]  (fp32 accumulate; gradient of a broadcast add).  reps <= AP_SUM_REPS_MAX (16 repetitions per
+ * workgroup along the grid's y axis, which holds 65 535): AP_ERR_SHAPE beyond */
+#define AP_SUM_REPS_MAX (16 * 65535)
 int ap_sum_reps_acc(const ap_bf16* x, float* out, int64_t n, int reps, ap_stream_t stream);
 /* out[oy, ox, c] (+)= sum_iy wy[oy*hi + iy] * sum_ix wx[ox*wi + ix] * in[(iy*wi + ix)*C + c]   (fp32 NHWC grids, dense tap matrices wy [ho, hi],
  * wx [wo, wi]): VOLO.interpolate_pos_encoding (models/volo.py:580-596 -- F.interpolate(pos_embed, scale_factor, mode="bicubic") on every
