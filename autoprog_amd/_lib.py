@@ -172,6 +172,9 @@ _SIGNATURES["ap_adamw_ema_step_guarded"] = (_I, _SIGNATURES["ap_adamw_ema_step"]
 _SIGNATURES["ap_softmax_topk_rows"] = (_I, [_P, _I, _I, _I, _F, _P, _P, _L, _L, _I, _L, _P])
 # distillation loss (csrc/distill.hip): ap_distill_fwd_bwd(student, ld_s, teacher, ld_t, C, mode, inv_temp, row_loss, dstudent, grad_scale, M, stream)
 _SIGNATURES["ap_distill_fwd_bwd"] = (_I, [_P, _I, _P, _I, _I, _I, _F, _P, _P, _F, _L, _P])
+# class rows of TokenLabelGTCrossEntropy on the sparse target (csrc/softce.hip): ap_soft_ce_sparse_gt_fwd_bwd(logits, ldx, idx, val, K, p_sb, p_s0,
+# p_s1, smoothing, row_loss, dlogits, grad_scale, B, C, mix_lam, mix_batches, mix_lam_dev, stream)
+_SIGNATURES["ap_soft_ce_sparse_gt_fwd_bwd"] = (_I, [_P, _I, _P, _P, _I, _L, _L, _L, _F, _P, _P, _F, _L, _I, _F, _I, _P, _P])
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 EXPECTED_ABI = 7                     # ap_abi_version() of the library these ctypes Structures mirror (include/autoprog_hip.h)

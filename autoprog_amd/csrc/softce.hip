@@ -123,34 +123,89 @@ k_soft_ce(const bf16_t* __restrict__ logits, int ldx, const float* __restrict__ 
 // concatenated / flipped / scaled copies of the label maps on the host side.
 #define CE_MAXK 16
 #define CE_SR 4            // rows per wave, all of their loads issued before the first is reduced
+
+// GT = true: the class row of TokenLabelGTCrossEntropy (loss/cross_entropy.py:62-89), one row per image (rows_per_batch = 1).  Its target is
+//     t_b = ratio_b * dense(slot 1) + (1 - ratio_b) * dense(slot 0),   ratio_b = 0.9 - 0.4 * [argmax dense(slot 0) == argmax dense(slot 1)]
+// and, mixed, lam * t_b + (1 - lam) * t_{B-1-b} with the partner's OWN ratio: every weight row sums to 1, so the smoothing term stays s / C
+// and the row is up to 4 K weighted pairs, K <= CE_GT_MAXK.  Lane 8 g + k (< 32) holds pair k of group g:
+//     g = 0  own slot 1      lam * ratio_b                  g = 2  partner slot 1   (1 - lam) * ratio_{B-1-b}
+//     g = 1  own slot 0      lam * (1 - ratio_b)            g = 3  partner slot 0   (1 - lam) * (1 - ratio_{B-1-b})
+// (unmixed: groups 0 and 1, weights ratio_b and 1 - ratio_b).  The argmax of a slot, decided here per group of 8 lanes: a class's score is
+// the fp32 sum of its pairs' val in ascending k (indices outside [0, C) add nothing); the argmax is the SMALLEST class among those of the
+// largest score, and class 0 when no score is positive (every class then holds s / C).  Scores are assumed non-negative.
+// idx1 / val1 point at slot 1 of image 0, d0 is the offset from slot 1 to slot 0, p_sb the image stride.  Every lane loads (clamped to a
+// pair of the row's own slot 1); a pair outside [0, C) leaves (-1, 0).  All 64 lanes must be active (cross-lane reads).
+#define CE_GT_MAXK 8
+__device__ __forceinline__ void ce_gt_pairs(const int* __restrict__ idx1, const float* __restrict__ val1, int K, int64_t p_sb, int64_t d0, int64_t b,
+                                            int mix_batches, float mix_lam, float smoothing, int C, int lane, int& my_i, float& my_v) {
+    const bool mixed = mix_batches > 0;
+    const int g = lane >> 3, k = lane & 7;
+    const bool want = lane < 32 && k < K && (g < 2 || mixed);
+    const int64_t img = (mixed && (g & 2)) ? (int64_t)(mix_batches - 1) - b : b;
+    const int64_t po = want ? img * p_sb + ((g & 1) ? d0 : 0) + k : b * p_sb;
+    int ci = idx1[po];
+    float cv = val1[po];
+    const bool ok = want && ci >= 0 && ci < C;
+    ci = ok ? ci : -1;
+    cv = ok ? cv : 0.f;
+    // the score of this lane's class inside its group: the K x K compare, pairs in ascending k
+    float sc = 0.f;
+#pragma unroll
+    for (int j = 0; j < CE_GT_MAXK; ++j) {
+        const int oi = __shfl(ci, (lane & ~7) | j, 64);
+        const float ov = __shfl(cv, (lane & ~7) | j, 64);
+        sc += oi == ci ? ov : 0.f;
+    }
+    sc = ok ? sc : -1.0f;
+    float best = sc;
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) best = fmaxf(best, __shfl_xor(best, o, 64));
+    int am = (ok && best > 0.f && sc == best) ? ci : 0x7fffffff;
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) am = min(am, __shfl_xor(am, o, 64));
+    am = am == 0x7fffffff ? 0 : am;
+    const float ratio = am == __shfl_xor(am, 8, 64) ? 0.5f : 0.9f;          // 0.9 - 0.4 * [the two slots agree]
+    float wgt = (g & 1) ? 1.0f - ratio : ratio;
+    if (mixed) wgt *= (g & 2) ? 1.0f - mix_lam : mix_lam;
+    my_i = ci;
+    my_v = cv * wgt * (1.0f - smoothing);
+}
+
+// GT: one row per wave (the B class rows are latency, not traffic), p_sn carries d0 (rows_per_batch = 1 leaves it free), idx / val point at slot 1
+template <bool GT>
 __global__ void __launch_bounds__(256)
 k_soft_ce_sparse(const bf16_t* __restrict__ logits, int ldx, const int* __restrict__ idx, const float* __restrict__ val, int K,
                  int64_t p_sb, int64_t p_sn, int rows_per_batch, float smoothing, float* __restrict__ row_loss,
                  bf16_t* __restrict__ dlogits, float gscale, int64_t M, int C, float mix_lam, int mix_batches, const float* __restrict__ lam_dev = nullptr) {
     if (lam_dev) mix_lam = lam_dev[0];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t row0 = ((int64_t)blockIdx.x * 4 + wave) * CE_SR;
+    constexpr int SR = GT ? 1 : CE_SR;
+    const int64_t row0 = ((int64_t)blockIdx.x * 4 + wave) * SR;
     if (row0 >= M) return;
-    const int KK = mix_batches > 0 ? 2 * K : K;              // pairs per row
-    unsigned lraw[CE_SR][CE_MAXV];
-    int my_i[CE_SR];
-    float my_v[CE_SR];
+    const int KK = GT ? (mix_batches > 0 ? 32 : 16) : (mix_batches > 0 ? 2 * K : K);       // lanes that may hold a pair of the row
+    unsigned lraw[SR][CE_MAXV];
+    int my_i[SR];
+    float my_v[SR];
 #pragma unroll
-    for (int r = 0; r < CE_SR; ++r) {
+    for (int r = 0; r < SR; ++r) {
         const int64_t row = min(row0 + r, M - 1);
         const bf16_t* xr = logits + row * ldx;
 #pragma unroll
         for (int i = 0; i < CE_MAXV; ++i) lraw[r][i] = *reinterpret_cast<const unsigned*>(xr + min(2 * (lane + 64 * i), ldx - 2));
-        const int64_t b = row / rows_per_batch, n = row - b * rows_per_batch;
-        const bool other = lane >= K;                                // (mix) the partner image's pairs
-        const int64_t po = ((mix_batches > 0 && other) ? (int64_t)(mix_batches - 1) - b : b) * p_sb + n * p_sn + (other ? lane - K : lane);
-        const float wgt = mix_batches > 0 ? (other ? 1.0f - mix_lam : mix_lam) : 1.0f;
-        my_i[r] = lane < KK ? idx[po] : -1;                          // lane k holds pair k of the row
-        my_v[r] = lane < KK ? val[po] * wgt * (1.0f - smoothing) : 0.f;
+        if constexpr (GT) {
+            ce_gt_pairs(idx, val, K, p_sb, p_sn, row, mix_batches, mix_lam, smoothing, C, lane, my_i[r], my_v[r]);
+        } else {
+            const int64_t b = row / rows_per_batch, n = row - b * rows_per_batch;
+            const bool other = lane >= K;                                // (mix) the partner image's pairs
+            const int64_t po = ((mix_batches > 0 && other) ? (int64_t)(mix_batches - 1) - b : b) * p_sb + n * p_sn + (other ? lane - K : lane);
+            const float wgt = mix_batches > 0 ? (other ? 1.0f - mix_lam : mix_lam) : 1.0f;
+            my_i[r] = lane < KK ? idx[po] : -1;                          // lane k holds pair k of the row
+            my_v[r] = lane < KK ? val[po] * wgt * (1.0f - smoothing) : 0.f;
+        }
     }
     const float base = smoothing / (float)C;
 #pragma unroll
-    for (int r = 0; r < CE_SR; ++r) {
+    for (int r = 0; r < SR; ++r) {
         const int64_t row = row0 + r;
         if (row >= M) break;
         float xv[CE_MAXV][2], tv[CE_MAXV][2];
@@ -296,12 +351,15 @@ __device__ __forceinline__ void ce_wide_walk_target(const float* __restrict__ tb
     }
 }
 
-template <int WPR, bool DENSE>
+//   GT (SPARSE only): the class row of TokenLabelGTCrossEntropy -- the pairs and their weights come from ce_gt_pairs (up to 32 lanes), p_sn
+//     carries the offset from slot 1 to slot 0 and rows_per_batch is 1; everything behind the prologue is the SPARSE row body.
+template <int WPR, bool DENSE, bool GT = false>
 __global__ void __launch_bounds__(256)
 k_soft_ce_wide(const bf16_t* __restrict__ logits, int ldx, const float* __restrict__ target, int64_t t_sb, int64_t t_sc, int64_t t_sn,
                const int* __restrict__ idx, const float* __restrict__ val, int K, int64_t p_sb, int64_t p_sn, float smoothing,
                int rows_per_batch, float* __restrict__ row_loss, bf16_t* __restrict__ dlogits, float gscale, int64_t M, int C,
                float mix_lam, int mix_batches, const float* __restrict__ lam_dev) {
+    static_assert(!(GT && DENSE), "the GT class rows exist on the sparse target only");
     if (lam_dev) mix_lam = lam_dev[0];
     extern __shared__ __attribute__((aligned(16))) u32x4 ce_wide_rows[];       // [4 / WPR][ldx / 8]
     __shared__ float red_mx[4], red_a[4], red_b[4], red_c[4];
@@ -318,7 +376,9 @@ k_soft_ce_wide(const bf16_t* __restrict__ logits, int ldx, const float* __restri
     // SPARSE: lane k holds pair k of the row (lanes K .. 2K-1: the partner image's, weighted 1 - lam); a pair outside [0, C) is dropped here
     int my_i = -1;
     float my_v = 0.f;
-    if (!DENSE) {
+    if constexpr (GT) {
+        ce_gt_pairs(idx, val, K, p_sb, p_sn, row, mix_batches, mix_lam, smoothing, C, lane, my_i, my_v);
+    } else if (!DENSE) {
         const int KK = mixed ? 2 * K : K;
         const bool other = lane >= K;
         const int64_t po = ((mixed && other) ? (int64_t)(mix_batches - 1) - b : b) * p_sb + n * p_sn + (other ? lane - K : lane);
@@ -534,7 +594,7 @@ extern "C" int ap_loss_combine(const float* a, int64_t na, float wa, const float
 }
 
 // rows wider than the register kernels take: k_soft_ce_wide, a team of one wave per row up to CE_WIDE_TEAM1_MAXLD columns and of four beyond
-template <bool DENSE>
+template <bool DENSE, bool GT = false>
 static int ce_wide_launch(const ap_bf16* logits, int ldx, const float* target, int64_t t_sb, int64_t t_sc, int64_t t_sn, const int* idx, const float* val,
                           int K, int64_t p_sb, int64_t p_sn, float smoothing, int rows_per_batch, float* row_loss, ap_bf16* dlogits, float grad_scale,
                           int64_t M, int C, float mix_lam, int mix_batches, const float* mix_lam_dev, ap_stream_t stream) {
@@ -548,15 +608,15 @@ static int ce_wide_launch(const ap_bf16* logits, int ldx, const float* target, i
     const size_t lds = (size_t)rpb * ldx * sizeof(bf16_t);
     static bool attr = false;
     if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k_soft_ce_wide<4, DENSE>, hipFuncAttributeMaxDynamicSharedMemorySize, CE_WIDE_MAXLD * (int)sizeof(bf16_t));
+        (void)hipFuncSetAttribute((const void*)k_soft_ce_wide<4, DENSE, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, CE_WIDE_MAXLD * (int)sizeof(bf16_t));
         attr = true;
     }
     (void)hipGetLastError();
     if (team1)
-        hipLaunchKernelGGL((k_soft_ce_wide<1, DENSE>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, logits, ldx, target, t_sb, t_sc, t_sn, idx, val, K,
+        hipLaunchKernelGGL((k_soft_ce_wide<1, DENSE, GT>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, logits, ldx, target, t_sb, t_sc, t_sn, idx, val, K,
                            p_sb, p_sn, smoothing, rows_per_batch, row_loss, dlogits, grad_scale, M, C, mix_lam, mix_batches, mix_lam_dev);
     else
-        hipLaunchKernelGGL((k_soft_ce_wide<4, DENSE>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, logits, ldx, target, t_sb, t_sc, t_sn, idx, val, K,
+        hipLaunchKernelGGL((k_soft_ce_wide<4, DENSE, GT>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, logits, ldx, target, t_sb, t_sc, t_sn, idx, val, K,
                            p_sb, p_sn, smoothing, rows_per_batch, row_loss, dlogits, grad_scale, M, C, mix_lam, mix_batches, mix_lam_dev);
     return ap_check_launch();
 }
@@ -633,8 +693,28 @@ extern "C" int ap_soft_ce_sparse_fwd_bwd_dev(const ap_bf16* logits, int ldx, con
     if (M == 0) return AP_OK;
     if ((M + 4 * CE_SR - 1) / (4 * CE_SR) > 0x7fffffffLL) return AP_ERR_SHAPE;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_soft_ce_sparse, dim3((unsigned)((M + 4 * CE_SR - 1) / (4 * CE_SR))), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const bf16_t*>(logits), ldx,
+    hipLaunchKernelGGL(k_soft_ce_sparse<false>, dim3((unsigned)((M + 4 * CE_SR - 1) / (4 * CE_SR))), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const bf16_t*>(logits), ldx,
                        idx, val, K, p_sb, p_sn, rows_per_batch, smoothing, row_loss, reinterpret_cast<bf16_t*>(dlogits), grad_scale, M, C, mix_lam, mix_batches, mix_lam_dev);
+    return ap_check_launch();
+}
+
+// the class rows of TokenLabelGTCrossEntropy: B rows, one per image (include/autoprog_hip.h)
+extern "C" int ap_soft_ce_sparse_gt_fwd_bwd(const ap_bf16* logits, int ldx, const int* idx, const float* val, int K, int64_t p_sb, int64_t p_s0, int64_t p_s1,
+                                            float smoothing, float* row_loss, ap_bf16* dlogits, float grad_scale, int64_t B, int C, float mix_lam,
+                                            int mix_batches, const float* mix_lam_dev, ap_stream_t stream) {
+    if (!logits || !idx || !val || !row_loss || !dlogits) return AP_ERR_NULL;
+    if (C <= 0 || ldx < C || (ldx & 7) || B < 0 || K <= 0 || K > CE_GT_MAXK || smoothing < 0.f || smoothing >= 1.f) return AP_ERR_SHAPE;
+    if (mix_batches != 0 && (mix_batches < 0 || (int64_t)mix_batches != B)) return AP_ERR_SHAPE;
+    // the kernels address slot 1 as the base and slot 0 relative to it (their p_sn; one row per image)
+    if (ldx > 64 * 2 * CE_MAXV)
+        return ce_wide_launch<false, true>(logits, ldx, nullptr, 0, 0, 0, idx + p_s1, val + p_s1, K, p_sb, p_s0 - p_s1, smoothing, 1, row_loss, dlogits, grad_scale,
+                                           B, C, mix_lam, mix_batches, mix_lam_dev, stream);
+    if (B == 0) return AP_OK;
+    if ((B + 3) / 4 > 0x7fffffffLL) return AP_ERR_SHAPE;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_soft_ce_sparse<true>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const bf16_t*>(logits), ldx,
+                       idx + p_s1, val + p_s1, K, p_sb, p_s0 - p_s1, 1, smoothing, row_loss, reinterpret_cast<bf16_t*>(dlogits), grad_scale, B, C, mix_lam, mix_batches,
+                       mix_lam_dev);
     return ap_check_launch();
 }
 

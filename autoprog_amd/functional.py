@@ -1041,6 +1041,43 @@ class SparseTokenLabelCEFn(torch.autograd.Function):
         return dc, da.reshape(B, N, C), None, None, None, None, None, None
 
 
+class SparseTokenLabelGTCEFn(torch.autograd.Function):
+    """TokenLabelGTCrossEntropy (loss/cross_entropy.py:62-89) on the sparse target [B, 2+N, K], K <= 8: the aux rows on the sparse kernel as
+    in SparseTokenLabelCEFn, the B class rows on ops.soft_ce_sparse_gt_fwd_bwd -- the argmaxes of slot 0 and slot 1, the ratio, the blend
+    with the ground truth and the mix-token blend with image B-1-b are formed by the kernel from the two images' pairs -- and
+    ops.loss_combine: three launches, nothing densified, no host decision beyond the one SparseTokenLabelCEFn makes."""
+
+    @staticmethod
+    def forward(ctx, x_cls, x_aux, idx, val, smoothing, lam, cls_weight, dense_weight):
+        B, N, C = x_aux.shape
+        K = idx.shape[-1]
+        ld = ops.round_up(C, 8)
+
+        def padded(x2d):
+            if ld == C and x2d.is_contiguous():
+                return x2d
+            xp = torch.zeros((x2d.shape[0], ld), dtype=BF16, device=x2d.device)
+            xp[:, :C] = x2d
+            return xp
+        idx, val = idx.contiguous(), val.contiguous()
+        rl_aux, d_aux = ops.soft_ce_sparse_fwd_bwd(padded(x_aux.reshape(B * N, C)), C, idx[:, 2:], val[:, 2:], (2 + N) * K, K, N, smoothing,
+                                                   dense_weight / (B * N))
+        # the class row: slot 0 (ground truth) at offset 0 and slot 1 (image level) at offset K of every image, in place
+        if hasattr(lam, "lam_ptr"):           # graph.StepScalars
+            rl_cls, d_cls = ops.soft_ce_sparse_gt_fwd_bwd(padded(x_cls.reshape(B, C)), C, idx, val, (2 + N) * K, 0, K, smoothing, cls_weight / B,
+                                                          mix_lam=1.0, mix_batches=B, mix_lam_ptr=lam.lam_ptr)
+        else:
+            rl_cls, d_cls = ops.soft_ce_sparse_gt_fwd_bwd(padded(x_cls.reshape(B, C)), C, idx, val, (2 + N) * K, 0, K, smoothing, cls_weight / B,
+                                                          mix_lam=lam, mix_batches=B if lam < 1 else 0)
+        ctx.save_for_backward(d_cls, d_aux)
+        ctx.dims = (B, N, C)
+        return ops.loss_combine(rl_cls, cls_weight / B, rl_aux, dense_weight / (B * N))
+
+    @staticmethod
+    def backward(ctx, g):
+        return SparseTokenLabelCEFn.backward(ctx, g)          # (the same saved gradients, the same eight inputs)
+
+
 class MixedLabelCEFn(torch.autograd.Function):
     """SoftTargetCrossEntropy on a Mixup / CutMix batch whose target is still (labels, lam) -- data.MixedLabelTarget -- instead of the
     dense [B, C] tensor timm's mixup_target builds every step (main_prog.py:978-979 -> loss/cross_entropy.py:21-36): the sparse

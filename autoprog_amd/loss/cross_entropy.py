@@ -55,6 +55,7 @@ class TokenLabelSoftTargetCrossEntropy(nn.Module):
 
 
 SPARSE_CE_MAX_PAIRS = 16        # CE_MAXK of csrc/softce.hip; the class count is not limited here (rows of up to 65 536 padded columns)
+SPARSE_GT_MAX_K = 8             # CE_GT_MAXK: pairs per slot on the class rows of TokenLabelGTCrossEntropy
 
 
 class _TokenLabelBase(nn.Module):
@@ -84,6 +85,13 @@ class _TokenLabelBase(nn.Module):
                 lam = dev_box if dev_box is not None else float(1 - ((bbx2 - bbx1) * (bby2 - bby1) / N))
                 return AF.SparseTokenLabelCEFn.apply(output.to(torch.bfloat16), aux_output.to(torch.bfloat16), target.idx, target.val,
                                                      target.smoothing, lam, float(self.cls_weight), float(self.dense_weight))
+            # the ground-truth variant's class row carries 4 K pairs (slot 1 and slot 0 of the image and of its mix-token partner) and the
+            # kernel takes 32: functional.SparseTokenLabelGTCEFn.  A subclass with an _adjust_cls of its own is densified as before.
+            if (type(self)._adjust_cls is TokenLabelGTCrossEntropy._adjust_cls and target.idx.is_cuda and target.idx.shape[1] == 2 + N
+                    and K <= SPARSE_GT_MAX_K):
+                lam = dev_box if dev_box is not None else float(1 - ((bbx2 - bbx1) * (bby2 - bby1) / N))
+                return AF.SparseTokenLabelGTCEFn.apply(output.to(torch.bfloat16), aux_output.to(torch.bfloat16), target.idx, target.val,
+                                                       target.smoothing, lam, float(self.cls_weight), float(self.dense_weight))
             target = target.dense(C)
         target = target.float()
         if target.dim() == 3 and type(self)._adjust_cls is _TokenLabelBase._adjust_cls and target.is_cuda:
@@ -91,7 +99,12 @@ class _TokenLabelBase(nn.Module):
             lam = dev_box if dev_box is not None else float(1 - ((bbx2 - bbx1) * (bby2 - bby1) / N))
             return AF.TokenLabelCEFn.apply(output.to(torch.bfloat16), aux_output.to(torch.bfloat16), target, lam,
                                            float(self.cls_weight), float(self.dense_weight))
-        if dev_box is not None:
+        # the ground-truth variant on a dense [B, C, 2 + N] target in a graph-mode step takes the route below op for op -- the adjusted class
+        # target from torch ops, the dense kernels -- with lam read from device memory, so a replay gives the eager step's bits wherever lam
+        # and 1 - lam are exact in fp32 (a token grid of 2^k tokens); 2-D targets and other subclasses have no graph-mode route
+        dev_gt = (dev_box is not None and target.dim() == 3 and target.is_cuda
+                  and type(self)._adjust_cls is TokenLabelGTCrossEntropy._adjust_cls)
+        if dev_box is not None and not dev_gt:
             raise NotImplementedError("a graph-mode forward (device-resident mix box) needs the fused token-label loss paths")
         aux2d = aux_output.reshape(B * N, C).to(torch.bfloat16)
         if target.dim() == 2:
@@ -102,9 +115,14 @@ class _TokenLabelBase(nn.Module):
             target_cls = self._adjust_cls(target[:, :, 1], target)
             taux = target[:, :, 2:]                                   # [B,C,N] class-major view, consumed in place
             loss_aux = _ce_rows(aux2d, taux, target.stride(0), target.stride(1), target.stride(2), N)
-        lam = 1 - ((bbx2 - bbx1) * (bby2 - bby1) / N)
-        if lam < 1:
+        if dev_gt:
+            # no host decision: lam = 1 blends nothing (1 * t + 0 * t' = t exactly)
+            lam = dev_box.dev.view(torch.float32)[4]            # graph.StepScalars: word 4 is lam
             target_cls = lam * target_cls + (1 - lam) * target_cls.flip(0)
+        else:
+            lam = 1 - ((bbx2 - bbx1) * (bby2 - bby1) / N)
+            if lam < 1:
+                target_cls = lam * target_cls + (1 - lam) * target_cls.flip(0)
         loss_cls = _dense_ce(output.to(torch.bfloat16), target_cls)
         return self.cls_weight * loss_cls + self.dense_weight * loss_aux
 

@@ -848,6 +848,28 @@ def soft_ce_sparse_fwd_bwd(logits, C, idx, val, p_sb, p_sn, rows_per_batch, smoo
     return row_loss, dlogits
 
 
+def soft_ce_sparse_gt_fwd_bwd(logits, C, idx, val, p_sb, p_s0, p_s1, smoothing, grad_scale, mix_lam=1.0, mix_batches=0, mix_lam_ptr=None):
+    """the class rows of TokenLabelGTCrossEntropy on the sparse target (include/autoprog_hip.h ap_soft_ce_sparse_gt_fwd_bwd): logits bf16
+    [B, ldx], one row per image; image b holds K = idx.shape[-1] <= 8 pairs of the ground-truth slot at b * p_sb + p_s0 and of the
+    image-level slot at b * p_sb + p_s1 (elements of idx int32 / val fp32).  The two argmaxes, ratio = 0.9 - 0.4 * [they agree] and the
+    blend ratio * slot 1 + (1 - ratio) * slot 0 are formed on the device, for the row's image and -- mix_batches = B -- for its partner
+    B-1-b.  Returns (row_loss fp32 [B], dlogits bf16)."""
+    _req(logits, BF16, "logits")
+    if not (idx.is_cuda and idx.dtype == torch.int32 and val.is_cuda and val.dtype == torch.float32):
+        raise AutoProgHipError("sparse targets: idx must be CUDA int32 and val CUDA fp32")
+    B, ldx = logits.shape
+    K, p_sb, p_s0, p_s1 = int(idx.shape[-1]), int(p_sb), int(p_s0), int(p_s1)
+    if B > 0 and (min(p_sb, p_s0, p_s1) < 0 or (B - 1) * p_sb + max(p_s0, p_s1) + K > min(idx.numel(), val.numel())):
+        raise AutoProgHipError("soft_ce_sparse_gt_fwd_bwd: the slot offsets reach past the %d elements of the pair arrays" % min(idx.numel(), val.numel()))
+    row_loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty_like(logits)
+    check(lib.ap_soft_ce_sparse_gt_fwd_bwd(logits.data_ptr(), ldx, idx.data_ptr(), val.data_ptr(), K, p_sb, p_s0, p_s1, float(smoothing),
+                                           row_loss.data_ptr(), dlogits.data_ptr(), float(grad_scale), B, C, float(mix_lam), int(mix_batches),
+                                           int(mix_lam_ptr) if mix_lam_ptr else None, _stream()),
+          "ap_soft_ce_sparse_gt_fwd_bwd")
+    return row_loss, dlogits
+
+
 def _padded_rows(t, C, name):
     """a bf16 CUDA matrix [M, >= C] with unit column stride -> its leading dimension (a padded view is taken as it is; a row stride
     that is no multiple of 8 or below C, or a misaligned base, is the library's AP_ERR_SHAPE)"""

@@ -409,6 +409,29 @@ int ap_soft_ce_fwd_bwd_dev(const ap_bf16* logits, int ldx, const float* target, 
 int ap_soft_ce_sparse_fwd_bwd_dev(const ap_bf16* logits, int ldx, const int* idx, const float* val, int K, int64_t p_sb, int64_t p_sn,
                                   int rows_per_batch, float smoothing, float* row_loss, ap_bf16* dlogits, float grad_scale, int64_t M, int C,
                                   float mix_lam, int mix_batches, const float* mix_lam_dev, ap_stream_t stream);
+/* The class rows of TokenLabelGTCrossEntropy (loss/cross_entropy.py:62-89) on the sparse target, at every class width of the sparse loss
+ * (additive in ABI version 7).  logits bf16 [B, ldx], one row per image.  Image b holds K pairs of slot s at
+ * idx / val + b * p_sb + p_s + k, p_s = p_s0 for the ground-truth slot and p_s1 for the image-level slot, 1 <= K <= 8.  With
+ *   dense_s[c] = (1 - smoothing) * sum_k [idx_k == c] * val_k + smoothing / C     (repeated indices accumulate, indices outside [0, C) add nothing)
+ *   a_s        = argmax_c dense_s[c]
+ *   ratio_b    = 0.9 - 0.4 * [a_0 == a_1]
+ *   t_b        = ratio_b * dense_1 + (1 - ratio_b) * dense_0
+ * the target of row b is t_b, or with mix_batches = B the mix-token class target mix_lam * t_b + (1 - mix_lam) * t_{B-1-b}, where the partner
+ * image's ratio is the partner's own; loss and gradient as the sparse loss above.
+ * The argmax rule: a class's score is the fp32 sum of its pairs' val, added in ascending k; the argmax is the smallest class index among
+ * those with the largest score, and class 0 if no score is positive (a slot of -1 fillers: every class then holds smoothing / C).  Scores
+ * are assumed non-negative.
+ * Every weight row sums to 1, so the smoothing term stays smoothing / C and the row is at most 4 K weighted pairs:
+ *   own slot 1      mix_lam * ratio_b                      partner slot 1   (1 - mix_lam) * ratio_{B-1-b}
+ *   own slot 0      mix_lam * (1 - ratio_b)                partner slot 0   (1 - mix_lam) * (1 - ratio_{B-1-b})
+ * (mix_batches = 0: the own slots with ratio_b and 1 - ratio_b; mix_lam is ignored).  mix_lam_dev non-NULL overrides mix_lam (pass
+ * mix_batches = B: lam = 1 gives the unmixed bits exactly).  Columns C .. ldx-1 of the logits are never interpreted and their gradient is
+ * stored as zero bits.  K outside 1 .. 8, mix_batches not in {0, B}, ldx % 8 != 0, ldx < C, smoothing outside [0, 1), rows wider than 1024
+ * columns that are not 16-byte aligned: AP_ERR_SHAPE; ldx > 65 536: AP_ERR_UNSUPPORTED.  B = 0 succeeds without a launch.  Fixed reduction
+ * order: two runs are bit-identical.  No atomics, no workspace, no allocation, no host synchronisation. */
+int ap_soft_ce_sparse_gt_fwd_bwd(const ap_bf16* logits, int ldx, const int* idx, const float* val, int K, int64_t p_sb, int64_t p_s0, int64_t p_s1,
+                                 float smoothing, float* row_loss, ap_bf16* dlogits, float grad_scale, int64_t B, int C, float mix_lam,
+                                 int mix_batches, const float* mix_lam_dev, ap_stream_t stream);
 /* out[0] = wa * sum(a[0:na]) + wb * sum(b[0:nb]): cls_weight * mean(row losses) + dense_weight * mean(row losses)
  * of the token-label loss (loss/cross_entropy.py:154-156) in one launch */
 int ap_loss_combine(const float* a, int64_t na, float wa, const float* b, int64_t nb, float wb, float* out, ap_stream_t stream);
