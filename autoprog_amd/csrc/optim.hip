@@ -23,11 +23,20 @@ struct AdamArgs {
 // or not apex skipped the step, main_prog.py:1030-1033).  With plain AdamArgs `skip` is a constant and the kernel is the one it was.
 struct AdamGuardArgs : AdamArgs { const ap_guard_state* guard; };
 
+// Arguments of ap_adamw_ema_step_ema16: either set above plus one bf16 slab per EMA copy (nullptr: that copy is not emitted).  An emitted
+// copy is the rounding of the fp32 lerp that is stored beside it (pack_bf2, as p16), from the registers that hold it: 2 bytes per
+// parameter and copy more, no second pass.  A skipped guarded step moves the EMA copies and so writes their bf16 copies as well.  The
+// two instantiations without these pointers compile to the code they were: the store below is discarded for them.
+template <class Base> struct Ema16Args : Base { bf16_t* ema16[4]; };
+template <class T> struct has_ema16 { static constexpr bool value = false; };
+template <class Base> struct has_ema16<Ema16Args<Base>> { static constexpr bool value = true; };
+
 template <class Args>
 __global__ void __launch_bounds__(256)
 k_adamw_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
             const unsigned char* __restrict__ wd_mask, int64_t n, Args a, bf16_t* __restrict__ p16) {
-    constexpr bool GUARD = !__is_same(Args, AdamArgs);
+    constexpr bool GUARD = __is_base_of(AdamGuardArgs, Args);
+    constexpr bool E16 = has_ema16<Args>::value;
     const int64_t nv = n >> 2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     if (a.step_dev) { a.lr = a.step_dev[0]; a.bc1 = a.step_dev[1]; a.bc2_sqrt = a.step_dev[2]; }
@@ -76,6 +85,9 @@ k_adamw_ema(float* __restrict__ p, const float* __restrict__ g, float* __restric
                 ee.x = d * ee.x + (1.0f - d) * pp.x; ee.y = d * ee.y + (1.0f - d) * pp.y;
                 ee.z = d * ee.z + (1.0f - d) * pp.z; ee.w = d * ee.w + (1.0f - d) * pp.w;
                 reinterpret_cast<float4*>(a.ema[e])[i] = ee;
+                if constexpr (E16) {
+                    if (a.ema16[e]) { u32x2 o; o[0] = pack_bf2(ee.x, ee.y); o[1] = pack_bf2(ee.z, ee.w); reinterpret_cast<u32x2*>(a.ema16[e])[i] = o; }
+                }
             }
         }
     }
@@ -125,11 +137,13 @@ extern "C" int ap_sumsq_f32(const float* x, int64_t n, float* out, void* workspa
     return ap_check_launch();
 }
 
-// the argument checks and the launch both entry points share; `guard` selects the guarded instantiation
+// the argument checks and the launch all entry points share; `guard` selects the guarded instantiation, `ema16` (an array of 4, entries
+// past n_ema already checked to be null) the ones that emit bf16 copies of EMA slabs
 static int adamw_ema_launch(float* p, const float* g, float* m, float* v, const unsigned char* wd_mask, int64_t n,
                             float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
                             const float* gnorm_sq, float max_norm, float clip_value, const float* step_scalars_dev,
-                            float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, const ap_guard_state* guard, ap_stream_t stream) {
+                            float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, const ap_guard_state* guard, ap_stream_t stream,
+                            ap_bf16* const* ema16 = nullptr) {
     if (!p || !g || !m || !v || !wd_mask) return AP_ERR_NULL;
     if (n <= 0 || (n & 3) || n_ema < 0 || n_ema > 4 || step < 1) return AP_ERR_SHAPE;
     if (gnorm_sq && !(max_norm > 0.f)) return AP_ERR_SHAPE;
@@ -146,6 +160,20 @@ static int adamw_ema_launch(float* p, const float* g, float* m, float* v, const 
     int64_t grid = (n / 4 + 255) / 256;
     if (grid > 256 * 16) grid = 256 * 16;
     (void)hipGetLastError();
+    // (four null entries: nothing to emit, the launch is the one without the pointers)
+    if (ema16 && (ema16[0] || ema16[1] || ema16[2] || ema16[3])) {
+        Ema16Args<AdamGuardArgs> b;
+        static_cast<AdamGuardArgs&>(b) = a;
+        for (int e = 0; e < 4; ++e) b.ema16[e] = reinterpret_cast<bf16_t*>(ema16[e]);
+        if (guard) hipLaunchKernelGGL(k_adamw_ema<Ema16Args<AdamGuardArgs>>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, wd_mask, n, b, p_bf16);
+        else {
+            Ema16Args<AdamArgs> c;
+            static_cast<AdamArgs&>(c) = a;
+            for (int e = 0; e < 4; ++e) c.ema16[e] = b.ema16[e];
+            hipLaunchKernelGGL(k_adamw_ema<Ema16Args<AdamArgs>>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, wd_mask, n, c, p_bf16);
+        }
+        return ap_check_launch();
+    }
     if (guard) hipLaunchKernelGGL(k_adamw_ema<AdamGuardArgs>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, wd_mask, n, a, p_bf16);
     else hipLaunchKernelGGL(k_adamw_ema<AdamArgs>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, wd_mask, n, static_cast<const AdamArgs&>(a), p_bf16);
     return ap_check_launch();
@@ -169,6 +197,25 @@ extern "C" int ap_adamw_ema_step_guarded(float* p, const float* g, float* m, flo
     if (!guard) return AP_ERR_NULL;
     return adamw_ema_launch(p, g, m, v, wd_mask, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, gnorm_sq, max_norm, clip_value,
                             step_scalars_dev, ema, ema_decay, n_ema, p_bf16, guard, stream);
+}
+
+// the step that also emits bf16 copies of EMA slabs (a forward pass reads bf16 weights: an EMA copy becomes a network to compute with,
+// the reference's ModelEmaV2 modules of main_prog.py:1030-1033, without a cast pass).  ema_bf16: HOST array of 4 device pointers, entry e
+// the bf16 slab of EMA copy e (same offsets, 8-byte aligned) or null for "not this copy"; entries at e >= n_ema must be null.
+// guard_or_null selects the guarded step.  Everything is checked before anything is launched.
+extern "C" int ap_adamw_ema_step_ema16(float* p, const float* g, float* m, float* v, const unsigned char* wd_mask, int64_t n,
+                                       float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                                       const float* gnorm_sq, float max_norm, float clip_value, const float* step_scalars_dev,
+                                       float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, ap_bf16* const* ema_bf16,
+                                       const ap_guard_state* guard_or_null, ap_stream_t stream) {
+    if (!ema_bf16) return AP_ERR_NULL;
+    if (n_ema < 0 || n_ema > 4) return AP_ERR_SHAPE;
+    for (int e = 0; e < 4; ++e) {
+        if (!ema_bf16[e]) continue;
+        if (e >= n_ema || ((uintptr_t)ema_bf16[e] & 7)) return AP_ERR_SHAPE;
+    }
+    return adamw_ema_launch(p, g, m, v, wd_mask, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, gnorm_sq, max_norm, clip_value,
+                            step_scalars_dev, ema, ema_decay, n_ema, p_bf16, guard_or_null, stream, ema_bf16);
 }
 
 // ---- gradient health (ap_grad_health): per parameter tensor the sum of squares of the finite elements (fp64) and the number of

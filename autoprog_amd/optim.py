@@ -103,6 +103,11 @@ class FlatAdamWEma:
         # model.load_state_dict() copies INTO the slab views (pointers unchanged): re-derive the bf16 copies afterwards
         self._load_hook = model.register_load_state_dict_post_hook(lambda module, incompatible: self.resync())
         self._guard = None                                       # the non-finite guard's device buffers (_guard_workspace)
+        # EMA copies as networks (ema_model): the bf16 slab of copy i while its shadow module lives (else None), the shadow modules,
+        # and the launch-constant pointer array ap_adamw_ema_step_ema16 reads (a null entry: that copy is not emitted)
+        self.ema16 = [None] * len(self.ema)
+        self._shadows = {}
+        self._ema16_ptrs = (ctypes.c_void_p * 4)()
 
     # ------------------------------------------------------------------ properties kept for callers of the round-1 API
     @property
@@ -142,8 +147,103 @@ class FlatAdamWEma:
                 if self._guard is not None:
                     self._guard["state"].zero_()                 # applied / skipped / consecutive restart with the optimizer
         self._stamp_versions()
+        self._refresh_ema16()
         from . import functional
         functional._WeightBank.generation += 1
+
+    # ------------------------------------------------------------------ EMA copies as networks
+    def _ema_index(self, i, what):
+        if not self.ema:
+            raise ValueError("FlatAdamWEma.%s: the optimizer keeps no EMA copies (ema_decays is empty)" % what)
+        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < len(self.ema):
+            raise IndexError("FlatAdamWEma.%s: EMA copy %r, the optimizer keeps copies 0 .. %d" % (what, i, len(self.ema) - 1))
+        return i
+
+    def live_ema_models(self):
+        """[(i, shadow module)] of the EMA copies that ema_model() turned into networks and release_ema_model() has not released"""
+        return sorted(self._shadows.items())
+
+    def _refresh_ema16(self):
+        """after an EMA slab was written from outside the update kernel (resync, grow, load_state_dict, either end of ema_weights):
+        the live bf16 copies again from their fp32 slabs"""
+        if not self._shadows:
+            return
+        with torch.no_grad():
+            for i, shadow in self._shadows.items():
+                self.ema16[i].copy_(self.ema[i])
+                for q in shadow.parameters():
+                    flat = q.__dict__.get("_ap_flat16")
+                    if flat is not None:
+                        flat[3] = q._version
+
+    def ema_model(self, i):
+        """EMA copy i as a network to compute with: a forward-only nn.Module of the model's architecture in eval(), every parameter a view
+        of `ema[i]` at the parameter's slab offset (requires_grad False, no storage of its own), every floating-point buffer THE tensor of
+        `ema_buffers[i]`, every parameter of two or more dimensions with its bf16 [N, K] copy in a bf16 slab `ema16[i]` that the update
+        kernel writes in the pass that moves `ema[i]` (ap_adamw_ema_step_ema16: 2 bytes per parameter more, no cast, nothing per use).
+        The module follows the EMA copy from step to step at the cost of nothing but its own forward pass -- an EMA teacher:
+        prog.teacher.TeacherLabeler(opt.ema_model(3), ...), prog.teacher.TeacherLogits(opt.ema_model(3)).  The reference's ModelEmaV2
+        objects are such modules (main_prog.py:1030-1033).
+        The first call for a copy allocates and fills `ema16[i]` and switches step() to the entry point that emits it (with and without
+        skip_nonfinite); it must not happen while a stream is being captured.  A graph captured afterwards holds the pointer like the
+        EMA pointers; a graph captured BEFORE does not emit the copy -- capture after.  Later calls return the same module.
+        release_ema_model(i) undoes it.  The module has no transposed weight copies: it never runs a backward.  It carries none of the
+        model's hooks, gradient views or sinks; set_sample_config / eval() act on it alone (prog.driver.AutoProgDriver keeps the live
+        shadow modules at the student's elastic configuration).
+        Inside `with opt.ema_weights(i)` the slabs have traded places: a shadow of copy i then computes with the STUDENT's weights."""
+        i = self._ema_index(i, "ema_model")
+        if i in self._shadows:
+            return self._shadows[i]
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FlatAdamWEma.ema_model: the first call for a copy allocates its bf16 slab and must come before a step is captured")
+        import copy
+        slab = self.ema[i]
+        e16 = torch.empty(self.n_pad, dtype=torch.bfloat16, device=slab.device)
+        e16.copy_(slab)
+        memo = {}
+        for p, (name, off, shape) in zip(self.reducer.params, self._views):
+            n = p.numel()
+            q = torch.nn.Parameter(torch.empty(0, dtype=slab.dtype, device=slab.device), requires_grad=False)
+            q.data = slab[off:off + n].view(shape)           # (as the model's parameters sit in `p`: the version counter stays the parameter's own)
+            q._ap_flat16 = [q.data_ptr(), e16[off:off + n].view(shape[0], -1) if len(shape) >= 2 else None, None, q._version]
+            memo[id(p)] = q
+        for b, eb in zip(self._buffers, self.ema_buffers[i]):
+            memo[id(b)] = eb
+        for p in self.model.parameters():                    # (a frozen parameter has no slab and no average: the shadow shares it)
+            memo.setdefault(id(p), p)
+        rng = getattr(self.model, "drop_path_rng", None)     # per-model scratch state: a fresh one, not a copy of device tensors
+        if rng is not None:
+            memo[id(rng)] = type(rng)()
+        scalars = getattr(self.model, "step_scalars", None)  # (a captured step's device scalars belong to the student's graph)
+        if scalars is not None:
+            memo[id(scalars)] = None
+        shadow = copy.deepcopy(self.model, memo)
+        for mod in shadow.modules():
+            for key, val in list(mod.__dict__.items()):
+                if "_hooks" in key and isinstance(val, dict):
+                    mod.__dict__[key] = type(val)()
+        shadow.requires_grad_(False)
+        shadow.eval()
+        self.ema16[i] = e16
+        self._ema16_ptrs[i] = e16.data_ptr()
+        self._shadows[i] = shadow
+        return shadow
+
+    def release_ema_model(self, i):
+        """forget the shadow module of EMA copy i and its bf16 slab; with none left step() launches what it launched before any existed.
+        (A module still held elsewhere keeps its views of `ema[i]` but its bf16 copies are no longer written: do not use it.  A graph
+        captured while the shadow lived holds the slab's address: release its graphs first -- GraphedStep.release(), or the driver's
+        stage transition -- as for any buffer a captured step writes.)"""
+        i = self._ema_index(i, "release_ema_model")
+        if i not in self._shadows:
+            raise KeyError("FlatAdamWEma.release_ema_model: EMA copy %d has no shadow module (ema_model(%d) was never called, or it was released)" % (i, i))
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FlatAdamWEma.release_ema_model: not while a step is being captured")
+        shadow = self._shadows.pop(i)
+        for q in shadow.parameters():
+            q.__dict__.pop("_ap_flat16", None)               # (a surviving reference falls back to the keyed casts of the weight bank)
+        self.ema16[i] = None
+        self._ema16_ptrs[i] = None
 
     def _refresh_transposes(self):
         if self._tr_desc is not None:
@@ -253,7 +353,10 @@ class FlatAdamWEma:
         args = (self.p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.wd_mask.data_ptr(),
                 self.n_pad, lr, self.betas[0], self.betas[1], self.eps, wd, self.step_count, gscale,
                 gnorm_ptr, max_norm, clip_value, scalars.adam_ptr if scalars is not None else None, self._ema_ptrs, self._ema_decay, len(self.ema), self.p16.data_ptr())
-        if skip_nonfinite:
+        if self._shadows:                                    # some EMA copy is a network: the same update, and its bf16 copy in the same pass
+            check(lib.ap_adamw_ema_step_ema16(*args, self._ema16_ptrs, gd["state"].data_ptr() if skip_nonfinite else None, ops._stream()),
+                  "ap_adamw_ema_step_ema16")
+        elif skip_nonfinite:
             check(lib.ap_adamw_ema_step_guarded(*args, gd["state"].data_ptr(), ops._stream()), "ap_adamw_ema_step_guarded")
         else:
             check(lib.ap_adamw_ema_step(*args, ops._stream()), "ap_adamw_ema_step")
@@ -394,3 +497,7 @@ class FlatAdamWEma:
             if self._guard is not None:                          # the restored t goes into the device record; the skip counters restart
                 self._guard["state"].zero_()
                 self._guard["state"][1] = int(self.step_count)
+        if self._shadows:                                        # the EMA slabs were written from outside the kernel
+            self._refresh_ema16()
+            from . import functional
+            functional._WeightBank.generation += 1

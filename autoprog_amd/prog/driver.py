@@ -71,10 +71,15 @@ class AutoProgDriver:
         the images: a batch_prep with Mixup / CutMix enabled is refused here.  None (default): nothing changes.
         A prog.teacher.TeacherLogits passes the same way: integer labels become the loss.DistillTarget (the labels, or the MixedLabelTarget
         of a prepared batch, and the teacher's class logits) that loss.DistillationLoss takes on a distilled DeiT.  Eager steps only: under
-        use_graphs the capture of a DistillTarget is refused (NotImplementedError from graph.GraphedStep).  The refusal of a mixing
-        batch_prep holds for it too (distillation on a Mixup / CutMix batch works when the loss is called directly)."""
+        use_graphs the capture of a DistillTarget is refused (NotImplementedError from graph.GraphedStep).  A mixing batch_prep is
+        accepted beside it: the DistillTarget's base is then the batch's MixedLabelTarget and the teacher sees the mixed pixels -- DeiT's
+        recipe, distillation with Mixup / CutMix.
+        An EMA copy of the student teaches like any other network: TeacherLabeler(optimizer.ema_model(i), ...) /
+        TeacherLogits(optimizer.ema_model(i)).  Every live shadow module of the optimizer (FlatAdamWEma.live_ema_models) is kept at the
+        student's elastic configuration -- depth and resolution of the stage or of a search's candidate -- and grows with it."""
         if teacher is not None:
-            if batch_prep is not None and getattr(batch_prep, "mix_enabled", False):
+            from .teacher import TeacherLogits
+            if batch_prep is not None and getattr(batch_prep, "mix_enabled", False) and not isinstance(teacher, TeacherLogits):
                 raise ValueError("a teacher's token labels cannot follow Mixup / CutMix: build the batch_prep with mixup_alpha = cutmix_alpha = 0")
             tc, mc = getattr(teacher, "num_classes", None), getattr(model, "num_classes", None)
             if tc is not None and mc is not None and int(tc) != int(mc):
@@ -130,6 +135,9 @@ class AutoProgDriver:
     def _activate(self, l, r, dp):
         mask = self.model.set_sample_config(self._config(l, r))
         self.model.set_drop_path_rate(dp)
+        live = getattr(self.opt, "live_ema_models", None)        # EMA copies run as networks (an EMA teacher): the student's depth and resolution
+        for _, shadow in (live() if live is not None else ()):
+            shadow.set_sample_config(self._config(l, r))
         return mask
 
     def _transition(self, l, r, dp):

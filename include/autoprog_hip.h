@@ -605,6 +605,18 @@ int ap_adamw_ema_step_guarded(float* p, const float* g, float* m, float* v, cons
                               const float* gnorm_sq, float max_norm, float clip_value, const float* step_scalars_dev,
                               float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, const ap_guard_state* guard,
                               ap_stream_t stream);
+/* ap_adamw_ema_step / _guarded that also writes bf16 copies of EMA slabs (additive in ABI version 7).  The reference keeps its EMA copies
+ * as ModelEmaV2 MODULES it can run (main_prog.py:1030-1033); a forward pass here reads bf16 weights, so an EMA slab becomes a network to
+ * compute with -- a teacher -- once its bf16 copy exists.  ema_bf16 is a HOST array of 4 device pointers: entry e is the bf16 slab of
+ * EMA copy e (n elements, same offsets, 8-byte aligned), written with the rounding p_bf16 gets from the lerp result in registers, or
+ * NULL for "do not emit this copy" (four NULL entries: the launch of ap_adamw_ema_step / _guarded itself).  guard_or_null: NULL is ap_adamw_ema_step, otherwise ap_adamw_ema_step_guarded (a skipped step
+ * moves the EMA copies and writes their bf16 copies).  Refused before anything is launched: ema_bf16 == NULL (AP_ERR_NULL); an entry
+ * that is not 8-byte aligned, or a non-null entry at an index >= n_ema (AP_ERR_SHAPE). */
+int ap_adamw_ema_step_ema16(float* p, const float* g, float* m, float* v, const unsigned char* wd_mask, int64_t n,
+                            float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                            const float* gnorm_sq, float max_norm, float clip_value, const float* step_scalars_dev,
+                            float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, ap_bf16* const* ema_bf16,
+                            const ap_guard_state* guard_or_null, ap_stream_t stream);
 /* transpose `count` bf16 matrices of one slab in one launch: desc_dev = device array of
  * {int64 src_off, int64 dst_off, int rows, int cols, int ld_dst, int first_tile} (32x32 tiles, first_tile
  * = running tile prefix); dst[dst_off + c*ld_dst + r] = src[src_off + r*cols + c], pad columns zeroed */
