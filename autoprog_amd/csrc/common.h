@@ -95,3 +95,48 @@ static inline int ap_check_launch() {
     return e == hipSuccess ? AP_OK : AP_ERR_LAUNCH;
 }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// ---- what a launcher has to know about the CURRENT device, asked once per device (a process may drive several) and never per process
+#define AP_MAXDEV 64
+static inline int ap_device() {
+    int dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < AP_MAXDEV) return dev;
+    (void)hipGetLastError();
+    return -1;
+}
+// A workgroup may take more than 64 KB of dynamic LDS only after the runtime allowed it, per kernel and per device.  Call this in front of
+// every such launch with the bytes the launch may pass: AP_OK, or AP_ERR_UNSUPPORTED when the runtime refuses (the sticky error is cleared;
+// a caller with another path falls back on that code).  The record is a plain int: two host threads that launch for the first time at
+// once both set the same attribute, which is harmless.
+template <auto KERNEL>
+static int ap_allow_lds(int bytes) {
+    static int allowed[AP_MAXDEV] = {};
+    const int dev = ap_device();
+    if (dev < 0) return AP_ERR_LAUNCH;
+    if (bytes > allowed[dev]) {
+        if (hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return AP_ERR_UNSUPPORTED;
+        }
+        allowed[dev] = bytes;
+    }
+    return AP_OK;
+}
+// the two together, for a launcher that picks one of several instantiations (KERNEL in parentheses where its template arguments hold a
+// comma); returns from the calling function when the runtime refuses
+#define AP_LAUNCH_LDS(KERNEL, grid, block, lds, stream, ...)                                       \
+    do {                                                                                           \
+        if (const int rc_ = ap_allow_lds<KERNEL>((int)(lds)); rc_ != AP_OK) return rc_;            \
+        hipLaunchKernelGGL(KERNEL, grid, block, lds, stream, __VA_ARGS__);                         \
+    } while (0)
+// compute units of the current device, 256 where it does not say
+static inline int ap_cu_count() {
+    static int cus[AP_MAXDEV] = {};
+    const int dev = ap_device();
+    if (dev < 0) return 256;
+    if (!cus[dev]) {
+        hipDeviceProp_t pr;
+        cus[dev] = (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
+    }
+    return cus[dev];
+}

@@ -695,38 +695,22 @@ int ap_conv3x3_c64_bn(const ap_bf16* x, const ap_bn_input* bn_in, const ap_bf16*
     const int64_t nt64 = (int64_t)B * tiles_x * tiles_y;
     if (nt64 > 0x7fffffff) return AP_ERR_SHAPE;
     const int ntiles = (int)nt64;
-    static int attr_done = 0;
     (void)hipGetLastError();
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c64<false>), hipFuncAttributeMaxDynamicSharedMemorySize, CV_LDS_BYTES) != hipSuccess) return AP_ERR_LAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c64<true>), hipFuncAttributeMaxDynamicSharedMemorySize, CV_LDS_BYTES) != hipSuccess) return AP_ERR_LAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c64<false, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, CV_LDS_BYTES) != hipSuccess) return AP_ERR_LAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c64<true, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, CV_LDS_BYTES) != hipSuccess) return AP_ERR_LAUNCH;
-        attr_done = 1;
-    }
     const int grid = cv_grid(ntiles);
     static int waves = 0;
     if (waves == 0) { const char* e = getenv("AP_CONV_WAVES"); waves = (e && atoi(e) == 4) ? 4 : 8; }
     if (waves == 8) {
-        static int attr8 = 0;
-        if (!attr8) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c64<false, 0, false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, CV_LDS_BYTES) != hipSuccess) return AP_ERR_LAUNCH;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c64<true, 0, false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, CV_LDS_BYTES) != hipSuccess) return AP_ERR_LAUNCH;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c64<false, 0, true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, CV_LDS_BYTES) != hipSuccess) return AP_ERR_LAUNCH;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c64<true, 0, true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, CV_LDS_BYTES) != hipSuccess) return AP_ERR_LAUNCH;
-            attr8 = 1;
-        }
         const BnIn bn = bn_in ? BnIn{bn_in->mean, bn_in->rstd, bn_in->gamma, bn_in->beta} : BnIn{nullptr, nullptr, nullptr, nullptr};
-        if (bn_in && stats) hipLaunchKernelGGL((k_conv3x3_c64<true, 0, true, 8>), dim3(grid), dim3(512), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats, bn);
-        else if (bn_in) hipLaunchKernelGGL((k_conv3x3_c64<false, 0, true, 8>), dim3(grid), dim3(512), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats, bn);
-        else if (stats) hipLaunchKernelGGL((k_conv3x3_c64<true, 0, false, 8>), dim3(grid), dim3(512), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats, bn);
-        else hipLaunchKernelGGL((k_conv3x3_c64<false, 0, false, 8>), dim3(grid), dim3(512), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats, bn);
+        if (bn_in && stats) AP_LAUNCH_LDS((k_conv3x3_c64<true, 0, true, 8>), dim3(grid), dim3(512), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats, bn);
+        else if (bn_in) AP_LAUNCH_LDS((k_conv3x3_c64<false, 0, true, 8>), dim3(grid), dim3(512), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats, bn);
+        else if (stats) AP_LAUNCH_LDS((k_conv3x3_c64<true, 0, false, 8>), dim3(grid), dim3(512), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats, bn);
+        else AP_LAUNCH_LDS((k_conv3x3_c64<false, 0, false, 8>), dim3(grid), dim3(512), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats, bn);
         return ap_check_launch();
     }
     if (bn_in) {
         const BnIn bn = {bn_in->mean, bn_in->rstd, bn_in->gamma, bn_in->beta};
-        if (stats) hipLaunchKernelGGL((k_conv3x3_c64<true, 0, true>), dim3(grid), dim3(256), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats, bn);
-        else hipLaunchKernelGGL((k_conv3x3_c64<false, 0, true>), dim3(grid), dim3(256), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats, bn);
+        if (stats) AP_LAUNCH_LDS((k_conv3x3_c64<true, 0, true>), dim3(grid), dim3(256), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats, bn);
+        else AP_LAUNCH_LDS((k_conv3x3_c64<false, 0, true>), dim3(grid), dim3(256), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats, bn);
         return ap_check_launch();
     }
 #if AP_EXPERIMENTS             // ablation instantiations (DESIGN.md "Convolution kernels, by ablation"): make EXTRA=-DAP_EXPERIMENTS=1, AP_CONV_ABL=bits
@@ -736,8 +720,8 @@ int ap_conv3x3_c64_bn(const ap_bf16* x, const ap_bn_input* bn_in, const ap_bf16*
         hipLaunchKernelGGL((k_conv3x3_c64<false, A>), dim3(grid), dim3(256), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats); return ap_check_launch();
     switch (abl) { CV_ABL_LAUNCH(1) CV_ABL_LAUNCH(2) CV_ABL_LAUNCH(3) CV_ABL_LAUNCH(4) CV_ABL_LAUNCH(7) CV_ABL_LAUNCH(8) CV_ABL_LAUNCH(11) default: break; }
 #endif
-    if (stats) hipLaunchKernelGGL((k_conv3x3_c64<true>), dim3(grid), dim3(256), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats);
-    else hipLaunchKernelGGL((k_conv3x3_c64<false>), dim3(grid), dim3(256), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats);
+    if (stats) AP_LAUNCH_LDS((k_conv3x3_c64<true>), dim3(grid), dim3(256), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats);
+    else AP_LAUNCH_LDS((k_conv3x3_c64<false>), dim3(grid), dim3(256), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats);
     return ap_check_launch();
 }
 
@@ -750,14 +734,9 @@ int ap_conv3x3_c64_bwd_stats(const ap_bf16* dz, const ap_bf16* w_packed_bwd, ap_
     const int64_t nt64 = (int64_t)B * tiles_x * tiles_y;
     if (nt64 > 0x7fffffff || (int64_t)H * W * CV_C > 0x7fffffff) return AP_ERR_SHAPE;
     const int ntiles = (int)nt64;
-    static int attr_done = 0;
     (void)hipGetLastError();
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c64<false, 0, false, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, CV_LDS_BYTES + 1024) != hipSuccess) return AP_ERR_LAUNCH;
-        attr_done = 1;
-    }
     const BnIn bn = {bn_below->mean, bn_below->rstd, bn_below->gamma, bn_below->beta};
-    hipLaunchKernelGGL((k_conv3x3_c64<false, 0, false, 8, true>), dim3(cv_grid(ntiles)), dim3(512), CV_LDS_BYTES + 1024, (hipStream_t)stream, dz, w_packed_bwd,
+    AP_LAUNCH_LDS((k_conv3x3_c64<false, 0, false, 8, true>), dim3(cv_grid(ntiles)), dim3(512), CV_LDS_BYTES + 1024, (hipStream_t)stream, dz, w_packed_bwd,
                        da, H, W, tiles_x, tiles_y, ntiles, stats, bn, z_below);
     return ap_check_launch();
 }
@@ -789,16 +768,9 @@ int ap_conv3x3_c64_wgrad_bn(const ap_bf16* x, const ap_bn_input* bn_in, const ap
     if (nt64 > 0x7fffffff) return AP_ERR_SHAPE;
     if (ws_bytes < ap_conv3x3_c64_wgrad_workspace(B, H, W)) return AP_ERR_SHAPE;
     int ntiles = (int)nt64, grid = cw_grid(ntiles);
-    static int attr_done = 0;
     (void)hipGetLastError();
     constexpr int PTR = CW_PTR;
     constexpr int P_LDS = (PTR * CW_T + (PTR + 2) * CW_PW) * CV_C * 2;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c64_wgrad), hipFuncAttributeMaxDynamicSharedMemorySize, CW_LDS_BYTES) != hipSuccess) return AP_ERR_LAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c64_wgrad_p<PTR>), hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS) != hipSuccess) return AP_ERR_LAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c64_wgrad_p<PTR, true>), hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS) != hipSuccess) return AP_ERR_LAUNCH;
-        attr_done = 1;
-    }
     static int use_p = -1;
     if (use_p < 0) { const char* e = getenv("AP_CONV_WGRAD_P"); use_p = e ? atoi(e) : 1; }
     if (use_p || bn_in) {       // the prefetching kernel: at most 256 workgroups on CW_PTR x 16 = 16 x 16 tiles (the only one with the BatchNorm input transform)
@@ -812,20 +784,14 @@ int ap_conv3x3_c64_wgrad_bn(const ap_bf16* x, const ap_bn_input* bn_in, const ap
         if (waves == 0) { const char* e = getenv("AP_CONV_WAVES"); waves = (e && atoi(e) == 4) ? 4 : 8; }
         const BnIn bn = bn_in ? BnIn{bn_in->mean, bn_in->rstd, bn_in->gamma, bn_in->beta} : BnIn{nullptr, nullptr, nullptr, nullptr};
         if (waves == 8) {
-            static int attr8 = 0;
-            if (!attr8) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c64_wgrad_p<PTR, false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS) != hipSuccess) return AP_ERR_LAUNCH;
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c64_wgrad_p<PTR, true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS) != hipSuccess) return AP_ERR_LAUNCH;
-                attr8 = 1;
-            }
-            if (bn_in) hipLaunchKernelGGL((k_conv3x3_c64_wgrad_p<PTR, true, 8>), dim3(grid), dim3(512), P_LDS, (hipStream_t)stream, x, dy, static_cast<float*>(workspace), H, W, tiles_x, tyy, ntiles, bn);
-            else hipLaunchKernelGGL((k_conv3x3_c64_wgrad_p<PTR, false, 8>), dim3(grid), dim3(512), P_LDS, (hipStream_t)stream, x, dy, static_cast<float*>(workspace), H, W, tiles_x, tyy, ntiles, bn);
+            if (bn_in) AP_LAUNCH_LDS((k_conv3x3_c64_wgrad_p<PTR, true, 8>), dim3(grid), dim3(512), P_LDS, (hipStream_t)stream, x, dy, static_cast<float*>(workspace), H, W, tiles_x, tyy, ntiles, bn);
+            else AP_LAUNCH_LDS((k_conv3x3_c64_wgrad_p<PTR, false, 8>), dim3(grid), dim3(512), P_LDS, (hipStream_t)stream, x, dy, static_cast<float*>(workspace), H, W, tiles_x, tyy, ntiles, bn);
         } else if (bn_in) {
-            hipLaunchKernelGGL((k_conv3x3_c64_wgrad_p<PTR, true>), dim3(grid), dim3(256), P_LDS, (hipStream_t)stream, x, dy, static_cast<float*>(workspace), H, W, tiles_x, tyy, ntiles, bn);
+            AP_LAUNCH_LDS((k_conv3x3_c64_wgrad_p<PTR, true>), dim3(grid), dim3(256), P_LDS, (hipStream_t)stream, x, dy, static_cast<float*>(workspace), H, W, tiles_x, tyy, ntiles, bn);
         } else
-        hipLaunchKernelGGL((k_conv3x3_c64_wgrad_p<PTR>), dim3(grid), dim3(256), P_LDS, (hipStream_t)stream, x, dy, static_cast<float*>(workspace), H, W, tiles_x, tyy, ntiles);
+        AP_LAUNCH_LDS((k_conv3x3_c64_wgrad_p<PTR>), dim3(grid), dim3(256), P_LDS, (hipStream_t)stream, x, dy, static_cast<float*>(workspace), H, W, tiles_x, tyy, ntiles);
     } else
-    hipLaunchKernelGGL(k_conv3x3_c64_wgrad, dim3(grid), dim3(256), CW_LDS_BYTES, (hipStream_t)stream, x, dy, static_cast<float*>(workspace), H, W, tiles_x, tiles_y, ntiles);
+    AP_LAUNCH_LDS(k_conv3x3_c64_wgrad, dim3(grid), dim3(256), CW_LDS_BYTES, (hipStream_t)stream, x, dy, static_cast<float*>(workspace), H, W, tiles_x, tiles_y, ntiles);
     int rc = ap_check_launch();
     if (rc != AP_OK) return rc;
     hipLaunchKernelGGL(k_conv3x3_wgrad_reduce, dim3(CV_WELEMS / 256), dim3(1024), 0, (hipStream_t)stream, static_cast<const float*>(workspace), grid, dw_oihw);
@@ -850,16 +816,11 @@ int ap_conv3x3_c128_wgrad(const ap_bf16* x, const ap_bf16* dy, float* dw_oihw, i
     if (np > 0x7fffffff) return AP_ERR_SHAPE;
     const int ntiles = (int)np, grid = cw_grid(ntiles < 256 ? ntiles : 256);
     if ((size_t)grid * CV_WELEMS * sizeof(float) > ws_bytes) return AP_ERR_SHAPE;
-    static int attr_done = 0;
     (void)hipGetLastError();
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c64_wgrad_p<PTR, false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS) != hipSuccess) return AP_ERR_LAUNCH;
-        attr_done = 1;
-    }
     const BnIn bn = BnIn{nullptr, nullptr, nullptr, nullptr};
     for (int a = 0; a < 2; ++a)
         for (int b = 0; b < 2; ++b) {
-            hipLaunchKernelGGL((k_conv3x3_c64_wgrad_p<PTR, false, 8>), dim3(grid), dim3(512), P_LDS, (hipStream_t)stream, x + 64 * b, dy + 64 * a,
+            AP_LAUNCH_LDS((k_conv3x3_c64_wgrad_p<PTR, false, 8>), dim3(grid), dim3(512), P_LDS, (hipStream_t)stream, x + 64 * b, dy + 64 * a,
                                static_cast<float*>(workspace), H, W, tiles_x, tyy, ntiles, bn, 128, 128);
             hipLaunchKernelGGL(k_conv3x3_wgrad_reduce, dim3(CV_WELEMS / 256), dim3(1024), 0, (hipStream_t)stream, static_cast<const float*>(workspace), grid,
                                dw_oihw + ((int64_t)(64 * a) * 128 + 64 * b) * 9, 128);

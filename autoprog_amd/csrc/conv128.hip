@@ -220,15 +220,9 @@ k_conv3x3_c128(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp, bf16
 extern "C" {
 
 static int c8_grid(int ntiles) {
-    static int cap = 0;
-    if (cap == 0) {
-        const char* e = getenv("AP_CONV128_GRID");
-        cap = e ? atoi(e) : 0;
-        if (cap < 1) {
-            int dev = 0; hipDeviceProp_t pr;
-            cap = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-        }
-    }
+    static int forced = -1;
+    if (forced < 0) { const char* e = getenv("AP_CONV128_GRID"); forced = e ? atoi(e) : 0; }
+    const int cap = forced >= 1 ? forced : ap_cu_count();
     return ntiles < cap ? ntiles : cap;
 }
 
@@ -252,16 +246,10 @@ int ap_conv3x3_c128(const ap_bf16* x, const ap_bf16* w_packed, ap_bf16* y, int B
     const int64_t nt64 = (int64_t)B * tiles_x * tiles_y;
     if (nt64 > 0x7fffffff || (int64_t)W * C8_C > 0x7fffffff) return AP_ERR_SHAPE;
     const int ntiles = (int)nt64;
-    static int attr_done = 0;
     (void)hipGetLastError();
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c128<false>), hipFuncAttributeMaxDynamicSharedMemorySize, C8_LDS_BYTES) != hipSuccess) return AP_ERR_LAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c128<true>), hipFuncAttributeMaxDynamicSharedMemorySize, C8_LDS_BYTES + C8_LDS_STATS) != hipSuccess) return AP_ERR_LAUNCH;
-        attr_done = 1;
-    }
     const int grid = c8_grid(ntiles);
-    if (stats) hipLaunchKernelGGL((k_conv3x3_c128<true>), dim3(grid), dim3(512), C8_LDS_BYTES + C8_LDS_STATS, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats);
-    else hipLaunchKernelGGL((k_conv3x3_c128<false>), dim3(grid), dim3(512), C8_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats);
+    if (stats) AP_LAUNCH_LDS((k_conv3x3_c128<true>), dim3(grid), dim3(512), C8_LDS_BYTES + C8_LDS_STATS, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats);
+    else AP_LAUNCH_LDS((k_conv3x3_c128<false>), dim3(grid), dim3(512), C8_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats);
     return ap_check_launch();
 }
 

@@ -346,15 +346,9 @@ int ap_conv7_s2d_ld(const ap_bf16* xs, const ap_bf16* w_packed, ap_bf16* y, int 
     const int nt = s7_tiles(B, H, W, S_TR, S_TW, &tx, &ty);
     if (nt < 0) return AP_ERR_SHAPE;
     const int grid = s7_grid(nt, "AP_CONV7_GRID", 512);
-    static int attr_done = 0;
     (void)hipGetLastError();
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv7_s2d<false>), hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS_BYTES) != hipSuccess) return AP_ERR_LAUNCH;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv7_s2d<true>), hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS_BYTES) != hipSuccess) return AP_ERR_LAUNCH;
-        attr_done = 1;
-    }
-    if (stats) hipLaunchKernelGGL((k_conv7_s2d<true>), dim3(grid), dim3(256), S_LDS_BYTES, (hipStream_t)stream, xs, w_packed, y, H, W, tx, ty, nt, stats, ldy);
-    else hipLaunchKernelGGL((k_conv7_s2d<false>), dim3(grid), dim3(256), S_LDS_BYTES, (hipStream_t)stream, xs, w_packed, y, H, W, tx, ty, nt, stats, ldy);
+    if (stats) AP_LAUNCH_LDS((k_conv7_s2d<true>), dim3(grid), dim3(256), S_LDS_BYTES, (hipStream_t)stream, xs, w_packed, y, H, W, tx, ty, nt, stats, ldy);
+    else AP_LAUNCH_LDS((k_conv7_s2d<false>), dim3(grid), dim3(256), S_LDS_BYTES, (hipStream_t)stream, xs, w_packed, y, H, W, tx, ty, nt, stats, ldy);
     return ap_check_launch();
 }
 

@@ -19,48 +19,34 @@
 // replaced by a select before any use; columns Cp .. ld-1 are never read.  dstudent's columns C .. ld_s-1 are stored as zero bits.
 //   Cp <= 1024           k_distill: both rows in one wave's registers (two 16-byte chunks per lane and operand), DS_SR rows per wave, all of
 //                        their loads issued before the first reduction.
-//   1024 < Cp            k_distill_wide: the rows are staged in LDS ONCE as 16-byte chunks (the loads of the next batch issued before the
-//                        previous one is written and reduced), the maxima (or the hard label) on the way; the sums and the gradient walk LDS.
-//                        Thread tt of a team owns chunks tt, tt + T, ..; two barriers per workgroup, reached by every wave (rows beyond M
-//                        are clamped and only their stores are masked).  A team is one wave up to 4096 columns (four rows per workgroup),
-//                        four waves beyond (one row per workgroup).
+//   1024 < Cp            k_distill_wide: the rows are staged in LDS ONCE, the maxima (or the hard label) on the way; the sums and the gradient
+//                        walk LDS.  The teams and the rules are those of row_wide.h; its staging walk is written out here for two rows
+//                        walked together (through the shared template this kernel measured 3 - 7 % slower).  Two barriers per workgroup.
 //     soft, 4 Cp <= DS_LDS_MAX (Cp <= 40 704)   both rows in LDS, 4 B per column: both operands are read from global memory exactly once
 //                                               (21 848 columns: 87 KB, one workgroup per CU).
 //     soft, wider                               the STUDENT row is staged (2 B per column, 128 KB at 65 536) and read from global memory once;
 //                                               the TEACHER row is read from global memory in each of the three walks (maximum, sums,
 //                                               gradient) -- the second and third from L2, a row is at most 128 KB.
 //     hard                                      only the student row is staged at any width; the teacher row is read once, for its label.
-#include "common.h"
+#include "row_wide.h"
 
 #define DS_SR 2                          // narrow kernel: rows per wave
 #define DS_NARROW_MAXC 1024
-#define DS_TEAM1_MAXC 4096
-#define DS_MAXLD 65536
 #define DS_LDS_MAX (159 * 1024)          // dynamic LDS of a workgroup (160 KB less the reduction words and slack)
-#define DS_MAXDEV 64
 #define DS_NEG (-3.0e38f)
 #define DS_LOG2E 1.44269504088896341f
 
-// two bf16 of a word -> their two 16-bit order codes (unsigned order == value order, -0 == +0): tk_encode2 of csrc/topk.hip
-__device__ __forceinline__ unsigned ds_encode2(unsigned w) {
-    const unsigned m = w & 0x7fff7fffu;
-    const unsigned nz = (m + 0x7fff7fffu) & 0x80008000u;
-    w &= nz | 0x7fff7fffu;
-    const unsigned s = (w >> 15) & 0x00010001u;
-    return w ^ (s * 0x7fffu + 0x80008000u);
-}
 // max of t and the keys of the chunk whose first column is c0; columns >= C give key 0 (below every valid key)
 __device__ __forceinline__ unsigned ds_chunk_key(const u32x4& v, int c0, int C, unsigned t) {
     const unsigned cc = 0xffffu - (unsigned)c0;
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
-        const unsigned o = ds_encode2(v[w]);
+        const unsigned o = rw_encode2(v[w]);
         t = max(t, c0 + 2 * w < C ? ((o << 16) | ((cc - 2 * w) & 0xffffu)) : 0u);
         t = max(t, c0 + 2 * w + 1 < C ? ((o & 0xffff0000u) | ((cc - 2 * w - 1) & 0xffffu)) : 0u);
     }
     return t;
 }
-__device__ __forceinline__ int ds_key_class(unsigned key, int C) { return min((int)(0xffffu - (key & 0xffffu)), C - 1); }
 // the 8 values of a chunk, columns >= C replaced (only the last chunk of a row takes the branch)
 __device__ __forceinline__ void ds_vals8(const u32x4& v, int c0, int C, float* f) {
     unpack8(v, f);
@@ -69,39 +55,6 @@ __device__ __forceinline__ void ds_vals8(const u32x4& v, int c0, int C, float* f
         for (int j = 0; j < 8; ++j) f[j] = c0 + j < C ? f[j] : DS_NEG;
     }
 }
-// Wave reductions on the DPP path: lanes of a quad, the halves of a row of 16 and the row mirrored, then lane 15 of rows 0 / 2 into rows
-// 1 / 3 and lane 31 into rows 2 / 3 -- lane 63 ends with the whole wave, read back as a wave-uniform value.  Rows that a step does not
-// write keep `old`: 0 for the sums and the keys, the value itself for the float maximum.
-#define DS_DPP(old, x, ctrl, rows) __builtin_amdgcn_update_dpp((int)(old), (int)(x), ctrl, rows, 0xf, false)
-__device__ __forceinline__ unsigned ds_wave_maxu(unsigned v) {
-    v = max(v, (unsigned)DS_DPP(0, v, 0xb1, 0xf));
-    v = max(v, (unsigned)DS_DPP(0, v, 0x4e, 0xf));
-    v = max(v, (unsigned)DS_DPP(0, v, 0x141, 0xf));
-    v = max(v, (unsigned)DS_DPP(0, v, 0x140, 0xf));
-    v = max(v, (unsigned)DS_DPP(0, v, 0x142, 0xa));
-    v = max(v, (unsigned)DS_DPP(0, v, 0x143, 0xc));
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-#define DS_DPP_F(old, x, ctrl, rows) __builtin_bit_cast(float, DS_DPP(__builtin_bit_cast(int, old), __builtin_bit_cast(int, x), ctrl, rows))
-__device__ __forceinline__ float ds_wave_sum(float v) {
-    v += DS_DPP_F(0.f, v, 0xb1, 0xf);
-    v += DS_DPP_F(0.f, v, 0x4e, 0xf);
-    v += DS_DPP_F(0.f, v, 0x141, 0xf);
-    v += DS_DPP_F(0.f, v, 0x140, 0xf);
-    v += DS_DPP_F(0.f, v, 0x142, 0xa);
-    v += DS_DPP_F(0.f, v, 0x143, 0xc);
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-__device__ __forceinline__ float ds_wave_max(float v) {
-    v = fmaxf(v, DS_DPP_F(v, v, 0xb1, 0xf));
-    v = fmaxf(v, DS_DPP_F(v, v, 0x4e, 0xf));
-    v = fmaxf(v, DS_DPP_F(v, v, 0x141, 0xf));
-    v = fmaxf(v, DS_DPP_F(v, v, 0x140, 0xf));
-    v = fmaxf(v, DS_DPP_F(v, v, 0x142, 0xa));
-    v = fmaxf(v, DS_DPP_F(v, v, 0x143, 0xc));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-
 __device__ __forceinline__ float ds_soft_loss(float Ss, float St, float W, float inv_temp, float temp) {
     return temp * temp * (W * inv_temp / St + (__logf(Ss) - __logf(St)));
 }
@@ -145,11 +98,11 @@ k_distill(const bf16_t* __restrict__ student, int ld_s, const bf16_t* __restrict
         }
 #pragma unroll
         for (int e = 0; e < 16; ++e) { mxs = fmaxf(mxs, a[e]); if (MODE == 0) mxt = fmaxf(mxt, b[e]); }
-        mxs = ds_wave_max(mxs);
+        mxs = rw_wave_max(mxs);
         float Ss = 0.f, St = 0.f, W = 0.f, ks, kt = 0.f, loss;
         int cstar = -1;
         if (MODE == 0) {
-            mxt = ds_wave_max(mxt);
+            mxt = rw_wave_max(mxt);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const float ds = a[e] - mxs, dt = b[e] - mxt;
@@ -158,11 +111,11 @@ k_distill(const bf16_t* __restrict__ student, int ld_s, const bf16_t* __restrict
                 Ss += a[e]; St += b[e];
                 W += b[e] * (dt - ds);
             }
-            Ss = ds_wave_sum(Ss); St = ds_wave_sum(St); W = ds_wave_sum(W);
+            Ss = rw_wave_sum(Ss); St = rw_wave_sum(St); W = rw_wave_sum(W);
             loss = ds_soft_loss(Ss, St, W, inv_temp, temp);
             ks = gscale * temp / Ss; kt = gscale * temp / St;
         } else {
-            cstar = ds_key_class(ds_wave_maxu(key), C);
+            cstar = rw_key_class(rw_wave_maxu(key), C);
             float xstar = 0.f;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
@@ -171,7 +124,7 @@ k_distill(const bf16_t* __restrict__ student, int ld_s, const bf16_t* __restrict
                 a[e] = __builtin_amdgcn_exp2f((a[e] - mxs) * DS_LOG2E);
                 Ss += a[e];
             }
-            Ss = ds_wave_sum(Ss); xstar = ds_wave_sum(xstar);
+            Ss = rw_wave_sum(Ss); xstar = rw_wave_sum(xstar);
             loss = (mxs - xstar) + __logf(Ss);
             ks = gscale / Ss;
         }
@@ -206,18 +159,17 @@ k_distill_wide(const bf16_t* __restrict__ student, int ld_s, const bf16_t* __res
     __shared__ float red_ms[4], red_mt[4], red_a[4], red_b[4], red_c[4];
     __shared__ unsigned red_k[4];
     constexpr int T = 64 * WPR, RPB = 4 / WPR, U = 4;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int team = wave / WPR, tw = wave % WPR, tt = tw * 64 + lane;
-    const int64_t row_raw = (int64_t)blockIdx.x * RPB + team;
-    const bool live = row_raw < M;
-    const int64_t row = min(row_raw, M - 1);
+    const RwTeam g = rw_team<WPR>(M);
+    const int wave = g.wave, lane = g.lane, team = g.team, tt = g.tt;
+    const bool live = g.live;
+    const int64_t row = g.row;
     const int nch = (C + 7) >> 3, nchs = ld_s >> 3;
     const float scale = MODE == 1 ? DS_LOG2E : inv_temp * DS_LOG2E;
     u32x4* ls = ds_rows + (size_t)team * nch;
     u32x4* lt = MODE == 0 ? ds_rows + (size_t)(RPB + team) * nch : nullptr;      // the teacher's rows exist in LDS in MODE 0 only
     const u32x4* sg = reinterpret_cast<const u32x4*>(student + row * ld_s);
     const u32x4* tg = reinterpret_cast<const u32x4*>(teacher + row * ld_t);
-    // ---- walk 1: global -> LDS, the maxima (or the hard label's key) on the way
+    // ---- walk 1: global -> LDS, the maxima (or the hard label's key) on the way: rw_stage of row_wide.h written out for two rows (see there)
     float mxs = DS_NEG, mxt = DS_NEG;
     unsigned key = 0;
     {
@@ -255,14 +207,14 @@ k_distill_wide(const bf16_t* __restrict__ student, int ld_s, const bf16_t* __res
             }
         }
     }
-    mxs = ds_wave_max(mxs);
-    if (MODE == 1) key = ds_wave_maxu(key); else mxt = ds_wave_max(mxt);
+    mxs = rw_wave_max(mxs);
+    if (MODE == 1) key = rw_wave_maxu(key); else mxt = rw_wave_max(mxt);
     if (lane == 0) { red_ms[wave] = mxs; red_mt[wave] = mxt; red_k[wave] = key; }
     __syncthreads();
     mxs = red_ms[team * WPR]; mxt = red_mt[team * WPR]; key = red_k[team * WPR];
 #pragma unroll
     for (int w = 1; w < WPR; ++w) { mxs = fmaxf(mxs, red_ms[team * WPR + w]); mxt = fmaxf(mxt, red_mt[team * WPR + w]); key = max(key, red_k[team * WPR + w]); }
-    const int cstar = MODE == 1 ? ds_key_class(key, C) : -1;
+    const int cstar = MODE == 1 ? rw_key_class(key, C) : -1;
     // ---- walk 2: the sums
     float Ss = 0.f, St = 0.f, W = 0.f;
 #pragma unroll 2
@@ -284,8 +236,8 @@ k_distill_wide(const bf16_t* __restrict__ student, int ld_s, const bf16_t* __res
             }
         }
     }
-    Ss = ds_wave_sum(Ss);
-    if (MODE != 1) { St = ds_wave_sum(St); W = ds_wave_sum(W); }
+    Ss = rw_wave_sum(Ss);
+    if (MODE != 1) { St = rw_wave_sum(St); W = rw_wave_sum(W); }
     if (lane == 0) { red_a[wave] = Ss; red_b[wave] = St; red_c[wave] = W; }
     __syncthreads();
     Ss = red_a[team * WPR]; St = red_b[team * WPR]; W = red_c[team * WPR];
@@ -322,33 +274,13 @@ k_distill_wide(const bf16_t* __restrict__ student, int ld_s, const bf16_t* __res
         if (live) st16_nt(dr + 8 * q, zero);
 }
 
-// a workgroup of the wide kernels takes up to DS_LDS_MAX bytes of dynamic LDS: allowed once per kernel and DEVICE, and the answer is checked
-// (third item: keyed by hipGetDevice(), AP_ERR_UNSUPPORTED when the runtime refuses).  The flags are plain bools: two host threads
-// that launch for the first time at once both set the same attribute to the same value, which is harmless.
-template <class K>
-static int ds_allow_lds(K kernel, bool (&done)[DS_MAXDEV]) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= DS_MAXDEV) { (void)hipGetLastError(); return AP_ERR_LAUNCH; }
-    if (!done[dev]) {
-        if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DS_LDS_MAX) != hipSuccess) {
-            (void)hipGetLastError();
-            return AP_ERR_UNSUPPORTED;
-        }
-        done[dev] = true;
-    }
-    return AP_OK;
-}
-
+// a workgroup of the wide kernels takes up to DS_LDS_MAX bytes of dynamic LDS
 template <int WPR, int MODE>
 static int ds_launch_wide(const bf16_t* s, int ld_s, const bf16_t* t, int ld_t, int C, float inv_temp, float temp, float* row_loss, bf16_t* ds,
-                          float gscale, int64_t M, size_t lds, hipStream_t stream) {
-    static bool allowed[DS_MAXDEV] = {};
-    const int rc = ds_allow_lds(k_distill_wide<WPR, MODE>, allowed);
-    if (rc != AP_OK) return rc;
-    const int64_t blocks = (M + (4 / WPR) - 1) / (4 / WPR);
-    if (blocks > 0x7fffffffLL) return AP_ERR_SHAPE;
+                          float gscale, int64_t M, size_t lds, unsigned blocks, hipStream_t stream) {
+    if (const int rc = ap_allow_lds<k_distill_wide<WPR, MODE>>(DS_LDS_MAX); rc != AP_OK) return rc;
     (void)hipGetLastError();
-    hipLaunchKernelGGL((k_distill_wide<WPR, MODE>), dim3((unsigned)blocks), dim3(256), lds, stream, s, ld_s, t, ld_t, C, inv_temp, temp, row_loss, ds, gscale, M);
+    hipLaunchKernelGGL((k_distill_wide<WPR, MODE>), dim3(blocks), dim3(256), lds, stream, s, ld_s, t, ld_t, C, inv_temp, temp, row_loss, ds, gscale, M);
     return ap_check_launch();
 }
 
@@ -356,7 +288,7 @@ extern "C" int ap_distill_fwd_bwd(const ap_bf16* student, int ld_s, const ap_bf1
                                   float* row_loss, ap_bf16* dstudent, float grad_scale, int64_t M, ap_stream_t stream) {
     if (M < 0 || C < 1 || ld_s < C || ld_t < C || (ld_s & 7) || (ld_t & 7) || (mode != 0 && mode != 1)) return AP_ERR_SHAPE;
     if (mode == 0 && (!(inv_temp > 0.f) || !(inv_temp < 3.0e38f))) return AP_ERR_SHAPE;
-    if (ld_s > DS_MAXLD || ld_t > DS_MAXLD) return AP_ERR_UNSUPPORTED;
+    if (ld_s > RW_MAXLD || ld_t > RW_MAXLD) return AP_ERR_UNSUPPORTED;
     if (M == 0) return AP_OK;
     if (!student || !teacher || !row_loss || !dstudent) return AP_ERR_NULL;
     if (((uintptr_t)student | (uintptr_t)teacher | (uintptr_t)dstudent) & 15) return AP_ERR_SHAPE;     // rows are moved in 16-byte chunks
@@ -375,12 +307,13 @@ extern "C" int ap_distill_fwd_bwd(const ap_bf16* student, int ld_s, const ap_bf1
         else hipLaunchKernelGGL(k_distill<1>, dim3((unsigned)blocks), dim3(256), 0, st, s, ld_s, t, ld_t, C, inv_temp, temp, row_loss, ds, grad_scale, M);
         return ap_check_launch();
     }
-    const size_t row_bytes = (size_t)Cp * sizeof(bf16_t);
-    if (Cp <= DS_TEAM1_MAXC) {
-        if (mode == 0) return ds_launch_wide<1, 0>(s, ld_s, t, ld_t, C, inv_temp, temp, row_loss, ds, grad_scale, M, 8 * row_bytes, st);
-        return ds_launch_wide<1, 1>(s, ld_s, t, ld_t, C, inv_temp, temp, row_loss, ds, grad_scale, M, 4 * row_bytes, st);
-    }
-    if (mode == 1) return ds_launch_wide<4, 1>(s, ld_s, t, ld_t, C, inv_temp, temp, row_loss, ds, grad_scale, M, row_bytes, st);
-    if (2 * row_bytes <= DS_LDS_MAX) return ds_launch_wide<4, 0>(s, ld_s, t, ld_t, C, inv_temp, temp, row_loss, ds, grad_scale, M, 2 * row_bytes, st);
-    return ds_launch_wide<4, 2>(s, ld_s, t, ld_t, C, inv_temp, temp, row_loss, ds, grad_scale, M, row_bytes, st);
+    return rw_launch(Cp, M, [&](auto wpr, unsigned blocks) {
+        constexpr int WPR = decltype(wpr)::value;
+        const size_t rows = (size_t)(4 / WPR) * Cp * sizeof(bf16_t);              // the student rows of a workgroup
+        if (mode == 1) return ds_launch_wide<WPR, 1>(s, ld_s, t, ld_t, C, inv_temp, temp, row_loss, ds, grad_scale, M, rows, blocks, st);
+        if constexpr (WPR == 4) {                                                // (four rows of a one-wave team and their teachers are 64 KB at the most)
+            if (2 * rows > DS_LDS_MAX) return ds_launch_wide<4, 2>(s, ld_s, t, ld_t, C, inv_temp, temp, row_loss, ds, grad_scale, M, rows, blocks, st);
+        }
+        return ds_launch_wide<WPR, 0>(s, ld_s, t, ld_t, C, inv_temp, temp, row_loss, ds, grad_scale, M, 2 * rows, blocks, st);
+    });
 }

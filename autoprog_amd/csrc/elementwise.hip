@@ -624,12 +624,8 @@ int ap_quantize_bf8(const ap_bf16* g, unsigned char* y, int64_t n, const float* 
 
 int ap_debug_poison_lds(unsigned pattern, unsigned* scratch2, ap_stream_t stream) {
     if (!scratch2) return AP_ERR_NULL;
-    int dev = 0, ncu = 256;
-    (void)hipGetDevice(&dev);
-    hipDeviceProp_t pr;
-    if (hipGetDeviceProperties(&pr, dev) == hipSuccess) ncu = pr.multiProcessorCount;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)k_poison_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
+    const int ncu = ap_cu_count();
+    if (const int rc = ap_allow_lds<k_poison_lds>(160 * 1024); rc != AP_OK) return rc;
     (void)hipGetLastError();
     if (hipMemsetAsync(scratch2, 0, 8, (hipStream_t)stream) != hipSuccess) return AP_ERR_LAUNCH;
     hipLaunchKernelGGL(k_poison_lds, dim3(ncu), dim3(1024), 160 * 1024, (hipStream_t)stream, pattern, scratch2, ncu);

@@ -829,83 +829,79 @@ const unsigned* g8_gelu_table_ptr(hipStream_t st) {
 // launch of the persistent 8-phase kernel (gemm8p.h): one instantiation per epilogue flavour of the training step, a generic one
 // for anything else
 template <int NT1, int EF>
-static void g8_go(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)k_gemm_nt_8p<NT1, EF>, hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS_BYTES); attr = true; (void)hipGetLastError(); }
+static int g8_go(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
+    if (const int rc = ap_allow_lds<k_gemm_nt_8p<NT1, EF>>(G8_LDS_BYTES); rc != AP_OK) return rc;
     hipLaunchKernelGGL((k_gemm_nt_8p<NT1, EF>), dim3(grid), dim3(512), G8_LDS_BYTES, st, ga, ep);
+    return ap_check_launch();
 }
 // the 224-row instantiations (256 x 192 tiles only): the flavours of the N = 384 products of a transformer block -- plain, row scale,
 // bias (+ row scale) + residual; -> false for any other flavour (the caller then launches 256-row tiles)
 template <int EF>
-static void g8_go224(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)k_gemm_nt_8p<1, EF, false, 224>, hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS_BYTES); attr = true; (void)hipGetLastError(); }
+static int g8_go224(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
+    if (const int rc = ap_allow_lds<k_gemm_nt_8p<1, EF, false, 224>>(G8_LDS_BYTES); rc != AP_OK) return rc;
     hipLaunchKernelGGL((k_gemm_nt_8p<1, EF, false, 224>), dim3(grid), dim3(512), G8_LDS_BYTES, st, ga, ep);
+    return ap_check_launch();
 }
 static bool g8_has224(const EpiArgs& ep) {
     const int f = g8_flavour(ep);
     return f == 0 || f == G8_RS || f == (G8_BIAS | G8_RES) || f == (G8_BIAS | G8_RS | G8_RES);
 }
-static void g8_pick224(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
+static int g8_pick224(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
     switch (g8_flavour(ep)) {
-        case 0: g8_go224<0>(ga, ep, grid, st); break;
-        case G8_RS: g8_go224<G8_RS>(ga, ep, grid, st); break;
-        case G8_BIAS | G8_RES: g8_go224<G8_BIAS | G8_RES>(ga, ep, grid, st); break;
-        default: g8_go224<G8_BIAS | G8_RS | G8_RES>(ga, ep, grid, st); break;
+        case 0: return g8_go224<0>(ga, ep, grid, st);
+        case G8_RS: return g8_go224<G8_RS>(ga, ep, grid, st);
+        case G8_BIAS | G8_RES: return g8_go224<G8_BIAS | G8_RES>(ga, ep, grid, st);
+        default: return g8_go224<G8_BIAS | G8_RS | G8_RES>(ga, ep, grid, st);
     }
 }
 template <int NT1>
-static void g8_pick(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
+static int g8_pick(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
     switch (g8_flavour(ep)) {
-        case 0: g8_go<NT1, 0>(ga, ep, grid, st); break;
-        case G8_BIAS: g8_go<NT1, G8_BIAS>(ga, ep, grid, st); break;
-        case G8_RS: g8_go<NT1, G8_RS>(ga, ep, grid, st); break;
-        case G8_BIAS | G8_GELU: g8_go<NT1, G8_BIAS | G8_GELU>(ga, ep, grid, st); break;
-        case G8_BIAS | G8_GELU | G8_RS: g8_go<NT1, G8_BIAS | G8_GELU | G8_RS>(ga, ep, grid, st); break;
-        case G8_BIAS | G8_GELU | G8_GTAB: g8_go<NT1, G8_BIAS | G8_GELU | G8_GTAB>(ga, ep, grid, st); break;
-        case G8_BIAS | G8_GELU | G8_RS | G8_GTAB: g8_go<NT1, G8_BIAS | G8_GELU | G8_RS | G8_GTAB>(ga, ep, grid, st); break;
-        case G8_BIAS | G8_GELU | G8_GTAB | G8_NOSIDE: g8_go<NT1, G8_BIAS | G8_GELU | G8_GTAB | G8_NOSIDE>(ga, ep, grid, st); break;
-        case G8_BIAS | G8_GELU | G8_RS | G8_GTAB | G8_NOSIDE: g8_go<NT1, G8_BIAS | G8_GELU | G8_RS | G8_GTAB | G8_NOSIDE>(ga, ep, grid, st); break;
-        case G8_DGELU: g8_go<NT1, G8_DGELU>(ga, ep, grid, st); break;
-        case G8_DGELU | G8_RS: g8_go<NT1, G8_DGELU | G8_RS>(ga, ep, grid, st); break;
-        case G8_MUL: g8_go<NT1, G8_MUL>(ga, ep, grid, st); break;
-        case G8_MUL | G8_RS: g8_go<NT1, G8_MUL | G8_RS>(ga, ep, grid, st); break;
-        case G8_MUL8: g8_go<NT1, G8_MUL8>(ga, ep, grid, st); break;
-        case G8_MUL8 | G8_RS: g8_go<NT1, G8_MUL8 | G8_RS>(ga, ep, grid, st); break;
-        case G8_MUL8 | G8_Q8: g8_go<NT1, G8_MUL8 | G8_Q8>(ga, ep, grid, st); break;
-        case G8_MUL8 | G8_RS | G8_Q8: g8_go<NT1, G8_MUL8 | G8_RS | G8_Q8>(ga, ep, grid, st); break;
-        case G8_BIAS | G8_RES: g8_go<NT1, G8_BIAS | G8_RES>(ga, ep, grid, st); break;
-        case G8_BIAS | G8_RS | G8_RES: g8_go<NT1, G8_BIAS | G8_RS | G8_RES>(ga, ep, grid, st); break;
-        default: g8_go<NT1, -1>(ga, ep, grid, st); break;
+        case 0: return g8_go<NT1, 0>(ga, ep, grid, st);
+        case G8_BIAS: return g8_go<NT1, G8_BIAS>(ga, ep, grid, st);
+        case G8_RS: return g8_go<NT1, G8_RS>(ga, ep, grid, st);
+        case G8_BIAS | G8_GELU: return g8_go<NT1, G8_BIAS | G8_GELU>(ga, ep, grid, st);
+        case G8_BIAS | G8_GELU | G8_RS: return g8_go<NT1, G8_BIAS | G8_GELU | G8_RS>(ga, ep, grid, st);
+        case G8_BIAS | G8_GELU | G8_GTAB: return g8_go<NT1, G8_BIAS | G8_GELU | G8_GTAB>(ga, ep, grid, st);
+        case G8_BIAS | G8_GELU | G8_RS | G8_GTAB: return g8_go<NT1, G8_BIAS | G8_GELU | G8_RS | G8_GTAB>(ga, ep, grid, st);
+        case G8_BIAS | G8_GELU | G8_GTAB | G8_NOSIDE: return g8_go<NT1, G8_BIAS | G8_GELU | G8_GTAB | G8_NOSIDE>(ga, ep, grid, st);
+        case G8_BIAS | G8_GELU | G8_RS | G8_GTAB | G8_NOSIDE: return g8_go<NT1, G8_BIAS | G8_GELU | G8_RS | G8_GTAB | G8_NOSIDE>(ga, ep, grid, st);
+        case G8_DGELU: return g8_go<NT1, G8_DGELU>(ga, ep, grid, st);
+        case G8_DGELU | G8_RS: return g8_go<NT1, G8_DGELU | G8_RS>(ga, ep, grid, st);
+        case G8_MUL: return g8_go<NT1, G8_MUL>(ga, ep, grid, st);
+        case G8_MUL | G8_RS: return g8_go<NT1, G8_MUL | G8_RS>(ga, ep, grid, st);
+        case G8_MUL8: return g8_go<NT1, G8_MUL8>(ga, ep, grid, st);
+        case G8_MUL8 | G8_RS: return g8_go<NT1, G8_MUL8 | G8_RS>(ga, ep, grid, st);
+        case G8_MUL8 | G8_Q8: return g8_go<NT1, G8_MUL8 | G8_Q8>(ga, ep, grid, st);
+        case G8_MUL8 | G8_RS | G8_Q8: return g8_go<NT1, G8_MUL8 | G8_RS | G8_Q8>(ga, ep, grid, st);
+        case G8_BIAS | G8_RES: return g8_go<NT1, G8_BIAS | G8_RES>(ga, ep, grid, st);
+        case G8_BIAS | G8_RS | G8_RES: return g8_go<NT1, G8_BIAS | G8_RS | G8_RES>(ga, ep, grid, st);
+        default: return g8_go<NT1, -1>(ga, ep, grid, st);
     }
 }
 // the fp8 instantiations (ap_gemm_nt_fp8: the forward Linear layers of the configs[4] step): the flavours a transformer block's forward uses
 template <int NT1, int EF>
-static void g8_go_fp8(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)k_gemm_nt_8p<NT1, EF, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS_BYTES); attr = true; (void)hipGetLastError(); }
+static int g8_go_fp8(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
+    if (const int rc = ap_allow_lds<k_gemm_nt_8p<NT1, EF, true>>(G8_LDS_BYTES); rc != AP_OK) return rc;
     hipLaunchKernelGGL((k_gemm_nt_8p<NT1, EF, true>), dim3(grid), dim3(512), G8_LDS_BYTES, st, ga, ep);
+    return ap_check_launch();
 }
 template <int NT1>
-static void g8_pick_fp8(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
+static int g8_pick_fp8(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
     switch (g8_flavour(ep)) {
-        case 0: g8_go_fp8<NT1, 0>(ga, ep, grid, st); break;
-        case G8_BIAS: g8_go_fp8<NT1, G8_BIAS>(ga, ep, grid, st); break;
-        case G8_BIAS | G8_GELU: g8_go_fp8<NT1, G8_BIAS | G8_GELU>(ga, ep, grid, st); break;
-        case G8_BIAS | G8_GELU | G8_RS: g8_go_fp8<NT1, G8_BIAS | G8_GELU | G8_RS>(ga, ep, grid, st); break;
-        case G8_BIAS | G8_GELU | G8_GTAB: g8_go_fp8<NT1, G8_BIAS | G8_GELU | G8_GTAB>(ga, ep, grid, st); break;
-        case G8_BIAS | G8_GELU | G8_RS | G8_GTAB: g8_go_fp8<NT1, G8_BIAS | G8_GELU | G8_RS | G8_GTAB>(ga, ep, grid, st); break;
-        case G8_BIAS | G8_RES: g8_go_fp8<NT1, G8_BIAS | G8_RES>(ga, ep, grid, st); break;
-        case G8_BIAS | G8_RS | G8_RES: g8_go_fp8<NT1, G8_BIAS | G8_RS | G8_RES>(ga, ep, grid, st); break;
-        default: g8_go_fp8<NT1, -1>(ga, ep, grid, st); break;
+        case 0: return g8_go_fp8<NT1, 0>(ga, ep, grid, st);
+        case G8_BIAS: return g8_go_fp8<NT1, G8_BIAS>(ga, ep, grid, st);
+        case G8_BIAS | G8_GELU: return g8_go_fp8<NT1, G8_BIAS | G8_GELU>(ga, ep, grid, st);
+        case G8_BIAS | G8_GELU | G8_RS: return g8_go_fp8<NT1, G8_BIAS | G8_GELU | G8_RS>(ga, ep, grid, st);
+        case G8_BIAS | G8_GELU | G8_GTAB: return g8_go_fp8<NT1, G8_BIAS | G8_GELU | G8_GTAB>(ga, ep, grid, st);
+        case G8_BIAS | G8_GELU | G8_RS | G8_GTAB: return g8_go_fp8<NT1, G8_BIAS | G8_GELU | G8_RS | G8_GTAB>(ga, ep, grid, st);
+        case G8_BIAS | G8_RES: return g8_go_fp8<NT1, G8_BIAS | G8_RES>(ga, ep, grid, st);
+        case G8_BIAS | G8_RS | G8_RES: return g8_go_fp8<NT1, G8_BIAS | G8_RS | G8_RES>(ga, ep, grid, st);
+        default: return g8_go_fp8<NT1, -1>(ga, ep, grid, st);
     }
 }
 static int g8_launch(int bn, const bf16_t* A, int lda, const bf16_t* B, int ldb, bf16_t* C, int ldc, int M, int N, int K, const EpiArgs& ep, hipStream_t st, bool fp8 = false) {
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0; (void)hipGetDevice(&dev); hipDeviceProp_t pr;
-        n_cu = (hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256;
-    }
+    const int n_cu = ap_cu_count();
     G8Args ga;
     ga.A = A; ga.lda = lda; ga.B = B; ga.ldb = ldb; ga.C = C; ga.ldc = ldc; ga.M = M; ga.N = N; ga.K = K;
     ga.tiles_n = (N + bn - 1) / bn; ga.ntiles = ((M + 255) / 256) * ga.tiles_n;
@@ -920,15 +916,13 @@ static int g8_launch(int bn, const bf16_t* A, int lda, const bf16_t* B, int ldb,
         if (ga.ntiles < cap && t224 <= cap && t224 > ga.ntiles) {
             ga.ntiles = t224;
             const int want4 = (t224 + 7) & ~7;
-            g8_pick224(ga, ep, want4 < cap ? want4 : cap, st);
-            return ap_check_launch();
+            return g8_pick224(ga, ep, want4 < cap ? want4 : cap, st);
         }
     }
     const int want = (ga.ntiles + 7) & ~7;        // a multiple of 8: the kernel deals tiles per XCD label
     const int grid = want < cap ? want : cap;
-    if (fp8) { if (bn == 192) g8_pick_fp8<1>(ga, ep, grid, st); else g8_pick_fp8<2>(ga, ep, grid, st); }
-    else if (bn == 192) g8_pick<1>(ga, ep, grid, st); else g8_pick<2>(ga, ep, grid, st);
-    return ap_check_launch();
+    if (fp8) return bn == 192 ? g8_pick_fp8<1>(ga, ep, grid, st) : g8_pick_fp8<2>(ga, ep, grid, st);
+    return bn == 192 ? g8_pick<1>(ga, ep, grid, st) : g8_pick<2>(ga, ep, grid, st);
 }
 
 // Where the persistent 8-phase kernel is picked (measured INSIDE the training step, tools/instep_8p.sh; profiles/r03_gemm_instep_*):
@@ -948,8 +942,7 @@ static int use_8p(int M, int N, int K, int ldc, const EpiArgs& ep) {          //
         // N = 1152 (4.5 -> 5 column tiles of 256): 25088 rows 2 x 1.3 against 3 rounds -> 256; the AutoProg stages' 8192 / 18432 rows
         // (128 / 192 px) one round against one, two against two -> 192 (12.2 against 13.8 us, 21.3 against 25.5); 12800 rows (160 px) one
         // round of 250 tiles against two of 300 -> 256 (16.3 against 21.5): tools/sweep_nt.py, AP_GEMM_NT_TILE = 20 / 21.
-        static int ncu = 0;
-        if (ncu == 0) { hipDeviceProp_t pr; int dev = 0; ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }
+        const int ncu = ap_cu_count();
         const int64_t mt = (M + 255) / 256;
         const int64_t r192 = (mt * (N / 192) + ncu - 1) / ncu, r256 = (mt * ((N + 255) / 256) + ncu - 1) / ncu;
         bn = (r192 * 10 < r256 * 13) ? 192 : 256;
@@ -963,12 +956,8 @@ extern "C" {
 
 // -> 1: not a launch of the weight-stationary kernel (the caller goes on); otherwise the launch's status.  AP_GEMM_WS=0: never
 static int ws_try(const bf16_t* A, int lda, const bf16_t* B, int ldb, bf16_t* C, int ldc, int M, int N, int K, EpiArgs& ep, hipStream_t st) {
-    static int on = -1, ncu = 0;
-    if (on < 0) {
-        const char* e = getenv("AP_GEMM_WS"); on = (e && e[0] == '0') ? 0 : 1;
-        int dev = 0; hipDeviceProp_t pr;
-        ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-    }
+    static int on = -1;
+    if (on < 0) { const char* e = getenv("AP_GEMM_WS"); on = (e && e[0] == '0') ? 0 : 1; }
     if (!on || K != WS_K || N % WS_BN || M % WS_BM || M < 16384 || (ldc & 15) || (lda & 7) || (ldb & 7)) return 1;
     if (ep.dgelu_of || ep.mul_by || ep.row_scale || ep.residual || ep.q8) return 1;
     int epi = -1;
@@ -980,16 +969,12 @@ static int ws_try(const bf16_t* A, int lda, const bf16_t* B, int ldb, bf16_t* C,
     WsArgs a;
     a.A = A; a.lda = lda; a.W = B; a.ldb = ldb; a.C = C; a.ldc = ldc; a.M = M; a.N = N;
     a.n_slices = N / WS_BN; a.n_items = M / WS_BM;
+    const int ncu = ap_cu_count();
     if (a.n_slices > ncu / 8) return 1;
     a.per_xcd = (ncu / 8) / a.n_slices;                           // tile streams per XCD: 10 for three slices on 32 CUs (two CUs per XCD stay idle)
     const int grid = ncu & ~7;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k_gemm_nt_ws<0>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS_BYTES(0));
-        (void)hipFuncSetAttribute((const void*)k_gemm_nt_ws<1>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS_BYTES(1));
-        (void)hipFuncSetAttribute((const void*)k_gemm_nt_ws<2>, hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS_BYTES(2));
-        attr = true; (void)hipGetLastError();
-    }
+    const int rc = epi == 0 ? ap_allow_lds<k_gemm_nt_ws<0>>(WS_LDS_BYTES(0)) : epi == 2 ? ap_allow_lds<k_gemm_nt_ws<2>>(WS_LDS_BYTES(2)) : ap_allow_lds<k_gemm_nt_ws<1>>(WS_LDS_BYTES(1));
+    if (rc != AP_OK) return rc;
     if (epi == 0) hipLaunchKernelGGL(k_gemm_nt_ws<0>, dim3(grid), dim3(512), WS_LDS_BYTES(0), st, a, ep);
     else if (epi == 2) hipLaunchKernelGGL(k_gemm_nt_ws<2>, dim3(grid), dim3(512), WS_LDS_BYTES(2), st, a, ep);
     else hipLaunchKernelGGL(k_gemm_nt_ws<1>, dim3(grid), dim3(512), WS_LDS_BYTES(1), st, a, ep);
@@ -1026,9 +1011,8 @@ int ap_gemm_nt(const ap_bf16* A, int lda, const ap_bf16* B, int ldb, ap_bf16* C,
     if (skinny < 0) { const char* e = getenv("AP_GEMM_NT_NO_SKINNY"); skinny = (e && e[0] == '1') ? 0 : 1; }
     if (skinny && M <= 256 && (K & 7) == 0) {          // (K = 1000: the head's input gradient ran on three 128 x 128 workgroups, 31 us, until round 4)
         const size_t lds = (size_t)8 * 64 * SK_STRIDE * sizeof(float);
-        static bool sk_attr = false;
-        if (!sk_attr) { (void)hipFuncSetAttribute((const void*)k_gemm_nt_skinny, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); sk_attr = true; (void)hipGetLastError(); }
         if (ep.noside) return AP_ERR_UNSUPPORTED;       // (the caller falls back to gelu = 3 with a side buffer)
+        if (const int rc = ap_allow_lds<k_gemm_nt_skinny>((int)lds); rc != AP_OK) return rc;
         hipLaunchKernelGGL(k_gemm_nt_skinny, dim3((N + 31) / 32, (M + 63) / 64), dim3(512), lds, (hipStream_t)stream, A, lda, B, ldb, C, ldc, M, N, K, ep);
         return ap_check_launch();
     }
@@ -1232,12 +1216,9 @@ static int tn_plan(const ap_tn_problem* problems, int count, TnGroup& grp, int& 
     if (count <= 0 || count > TN_MAX_GROUP) return AP_ERR_SHAPE;
     // Two 256-thread workgroups are resident per CU: the launch should fill that single wave of workgroups as fully as
     // possible but never spill into a second one (measured on the D1 blocks: 450 workgroups 125 us, 540 -> 175 us).
-    static int capacity = 0;
-    if (capacity == 0) {
-        const char* e = getenv("AP_GEMM_TN_GROUP_BLOCKS");
-        if (e) capacity = atoi(e);
-        else { int dev = 0; (void)hipGetDevice(&dev); hipDeviceProp_t pr; capacity = 2 * ((hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256); }
-    }
+    static int forced = -1;
+    if (forced < 0) { const char* e = getenv("AP_GEMM_TN_GROUP_BLOCKS"); forced = e ? atoi(e) : 0; }
+    const int capacity = forced > 0 ? forced : 2 * ap_cu_count();
     int max_steps = 1;
     for (int i = 0; i < count; ++i) {
         const ap_tn_problem& q = problems[i];
@@ -1432,13 +1413,7 @@ int ap_gemm_tn_acc_grouped_ln(const ap_tn_problem* problems, int count, const ap
     if (!workspace) {
         // the 192 x 192-tile LDS-DMA kernel takes the problems that fit it (with the LayerNorm riders); the rest of the group -- e.g. the
         // 486-wide attention-weight projection of an outlooker block -- goes on in launches of the 128 x 128-tile kernel, 8 problems each
-        static int n_cu = 0;
-        if (n_cu == 0) {
-            int dev = 0; (void)hipGetDevice(&dev); hipDeviceProp_t pr;
-            n_cu = (hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256;
-            (void)hipFuncSetAttribute((const void*)k_gemm_tn_8p, hipFuncAttributeMaxDynamicSharedMemorySize, T8_LDS_BYTES);
-            (void)hipGetLastError();
-        }
+        const int n_cu = ap_cu_count();
         ap_tn_problem fit[AP_TN_MAX_GROUP], rest[AP_TN_MAX_GROUP];
         int nfit = 0, nrest = 0;
         for (int i = 0; i < count; ++i) { if (tn8_fits(problems[i])) fit[nfit++] = problems[i]; else rest[nrest++] = problems[i]; }
@@ -1454,6 +1429,7 @@ int ap_gemm_tn_acc_grouped_ln(const ap_tn_problem* problems, int count, const ap
                 } else ln.it[i] = TnLnItem{nullptr, nullptr, nullptr, 0, 0};
             }
             ln.count = ln_count; ln.first = mb8;
+            if (const int rca = ap_allow_lds<k_gemm_tn_8p>(T8_LDS_BYTES); rca != AP_OK) return rca;
             (void)hipGetLastError();
             hipLaunchKernelGGL(k_gemm_tn_8p, dim3(mb8 + lblocks), dim3(512), T8_LDS_BYTES, (hipStream_t)stream, g8, map8, ln);
             const int rc8 = ap_check_launch();
@@ -1505,12 +1481,9 @@ static int tn_grouped_128(const ap_tn_problem* problems, int count, const ap_ln_
         if (problems[0].b_bn) hipLaunchKernelGGL(k_gemm_tn_patch<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grp.p[0], bbn);
         else hipLaunchKernelGGL(k_gemm_tn_patch<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grp.p[0], bbn);
     } else {
-        static int place = -1, cap = 0;
-        if (place < 0) {
-            const char* e = getenv("AP_GEMM_TN_PLACE"); place = e ? atoi(e) : 1;
-            int dev = 0; (void)hipGetDevice(&dev); hipDeviceProp_t pr;
-            cap = 2 * ((hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256) / 8;     // resident workgroups per XCD
-        }
+        static int place = -1;
+        if (place < 0) { const char* e = getenv("AP_GEMM_TN_PLACE"); place = e ? atoi(e) : 1; }
+        const int cap = 2 * ap_cu_count() / 8;                                                                  // resident workgroups per XCD
         TnMap map; int mblocks = 0;
         if (place && tn_place(grp, cap, map, mblocks)) {
             TnLn ln;
@@ -1547,11 +1520,7 @@ static int tf_plan(const ap_tn8_problem* problems, int count, TfGroup& grp, int&
         if (q.N1 % 128 || q.N2 % 128 || (q.a_fmt != AP_FP8_E5M2 && q.a_fmt != AP_FP8_E4M3)) return AP_ERR_UNSUPPORTED;
     }
     // resident capacity: two 256-thread workgroups per CU (32 KB of LDS each); the smallest K-steps per workgroup (>= 4) that fits it once
-    static int capacity = 0;
-    if (capacity == 0) {
-        int dev = 0; (void)hipGetDevice(&dev); hipDeviceProp_t pr;
-        capacity = 2 * ((hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256);
-    }
+    const int capacity = 2 * ap_cu_count();
     int max_k = 1;
     for (int i = 0; i < count; ++i) max_k = std::max(max_k, (problems[i].M + 127) / 128);
     auto blocks_at = [&](int sps) {
@@ -1668,19 +1637,14 @@ int ap_gemm_tn8_acc_grouped_ln(const ap_tn8_problem* problems, int count, const 
     }
     ln.count = ln_count;
     if (!workspace) {                                 // atomic mode: the 8-phase flavour when every problem fits it
-        static int n_cu = 0;
-        if (n_cu == 0) {
-            int dev = 0; (void)hipGetDevice(&dev); hipDeviceProp_t pr;
-            n_cu = (hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256;
-            (void)hipFuncSetAttribute((const void*)k_gemm_tn_8p_fp8<AP_FP8_E4M3>, hipFuncAttributeMaxDynamicSharedMemorySize, T8_LDS_BYTES);
-            (void)hipFuncSetAttribute((const void*)k_gemm_tn_8p_fp8<AP_FP8_E5M2>, hipFuncAttributeMaxDynamicSharedMemorySize, T8_LDS_BYTES);
-            (void)hipGetLastError();
-        }
+        const int n_cu = ap_cu_count();
         T8GroupF8 g8; T8Map map8; int mb8 = 0;
         if (tf8_plan(problems, count, n_cu, g8, map8, mb8)) {
             ln.first = mb8;
+            const bool e5 = problems[0].a_fmt == AP_FP8_E5M2;
+            if (const int rca = e5 ? ap_allow_lds<k_gemm_tn_8p_fp8<AP_FP8_E5M2>>(T8_LDS_BYTES) : ap_allow_lds<k_gemm_tn_8p_fp8<AP_FP8_E4M3>>(T8_LDS_BYTES); rca != AP_OK) return rca;
             (void)hipGetLastError();
-            if (problems[0].a_fmt == AP_FP8_E5M2)
+            if (e5)
                 hipLaunchKernelGGL(k_gemm_tn_8p_fp8<AP_FP8_E5M2>, dim3(mb8 + lblocks), dim3(512), T8_LDS_BYTES, (hipStream_t)stream, g8, map8, ln);
             else
                 hipLaunchKernelGGL(k_gemm_tn_8p_fp8<AP_FP8_E4M3>, dim3(mb8 + lblocks), dim3(512), T8_LDS_BYTES, (hipStream_t)stream, g8, map8, ln);

@@ -861,22 +861,11 @@ int ap_mhsa_fwd(const ap_bf16* qkv, ap_bf16* out, float* lse, int B, int N, int 
     const dim3 grid(B * heads);
     const size_t lds = (size_t)2 * nt * 16 * hd * sizeof(bf16_t);
     hipStream_t s = (hipStream_t)stream;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)k_mhsa_fwd<14, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        (void)hipFuncSetAttribute((const void*)k_mhsa_fwd<16, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        attr_done = true;
-    }
     (void)hipGetLastError();
     // head_dim 32 and 7 .. 13 query tiles: the persistent kernel with loader waves (AP_MHSA_FWD_P=0: one workgroup per (image, head))
-    static int use_p = -1, p_cu = 0;
-    if (use_p < 0) {
-        const char* e = getenv("AP_MHSA_FWD_P"); use_p = e ? atoi(e) : 1;
-        int dev = 0; hipDeviceProp_t pr;
-        p_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256;
-        p_cu &= ~7;                                                            // whole XCD groups (xcd_remap)
-        (void)hipGetLastError();
-    }
+    static int use_p = -1;
+    if (use_p < 0) { const char* e = getenv("AP_MHSA_FWD_P"); use_p = e ? atoi(e) : 1; }
+    const int p_cu = ap_cu_count() & ~7;                                       // whole XCD groups (xcd_remap)
     const int nq = (N + 15) / 16;
     if (hd == 32 && use_p && nq >= 7 && nq <= 16 - FP_LOADERS && p_cu >= 8) {
         const int items = B * heads;
@@ -886,6 +875,9 @@ int ap_mhsa_fwd(const ap_bf16* qkv, ap_bf16* out, float* lse, int B, int N, int 
         switch (nt) { case 8: FP_LAUNCH(8); break; case 10: FP_LAUNCH(10); break; case 12: FP_LAUNCH(12); break; default: FP_LAUNCH(14); break; }
 #undef FP_LAUNCH
         return ap_check_launch();
+    }
+    if (hd != 32 && nt >= 14) {                                                // the two instantiations whose head does not fit 64 KB
+        if (const int rc = nt == 14 ? ap_allow_lds<k_mhsa_fwd<14, 64>>(96 * 1024) : ap_allow_lds<k_mhsa_fwd<16, 64>>(96 * 1024); rc != AP_OK) return rc;
     }
     if (hd == 32) { MHSA_FWD_SWITCH(32) } else { MHSA_FWD_SWITCH(64) }
     return ap_check_launch();
@@ -910,26 +902,12 @@ int ap_mhsa_bwd(const ap_bf16* qkv, const ap_bf16* out, const ap_bf16* dout, con
     const dim3 grid(B * heads);
     const size_t lds = (size_t)4 * nt * 16 * hd * sizeof(bf16_t) + (size_t)2 * nt * 16 * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)k_mhsa_bwd<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)k_mhsa_bwd<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_done = true;
-    }
     (void)hipGetLastError();
     // default for head_dim 32 and 8 .. 13 token tiles (N = 113 .. 208): dS through LDS, loader waves (AP_MHSA_BWD_DS=0: the two-pass kernel)
-    static int use_ds = -1, ds_cu = 0;
-    if (use_ds < 0) {
-        const char* e = getenv("AP_MHSA_BWD_DS"); use_ds = e ? atoi(e) : 1;
-        int dev = 0; hipDeviceProp_t pr;
-        ds_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256;
-        if (ds_cu >= 8) ds_cu &= ~7;                                           // whole XCD groups (xcd_remap)
-        (void)hipFuncSetAttribute((const void*)k_mhsa_bwd_ds<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)k_mhsa_bwd_ds<5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)k_mhsa_bwd_ds<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)k_mhsa_bwd_ds<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipGetLastError();
-    }
+    static int use_ds = -1;
+    if (use_ds < 0) { const char* e = getenv("AP_MHSA_BWD_DS"); use_ds = e ? atoi(e) : 1; }
+    int ds_cu = ap_cu_count();
+    if (ds_cu >= 8) ds_cu &= ~7;                                               // whole XCD groups (xcd_remap)
     {
         const int ntile = (N + 15) / 16;
         const size_t lds_ds = lds + (size_t)2 * nt * 16 * sizeof(float) + (size_t)ntile * 16 * DS_STR * sizeof(bf16_t);
@@ -937,12 +915,14 @@ int ap_mhsa_bwd(const ap_bf16* qkv, const ap_bf16* out, const ap_bf16* dout, con
             lds_ds <= (size_t)160 * 1024) {
             const int items = B * heads;
             const dim3 gds(items < ds_cu ? items : ds_cu);
-#define DS_LAUNCH(NP) hipLaunchKernelGGL(k_mhsa_bwd_ds<NP>, gds, dim3(1024), lds_ds, s, qkv, out, dout, lse, dqkv, N, heads, scale, nt, items)
+#define DS_LAUNCH(NP) if (const int rc = ap_allow_lds<k_mhsa_bwd_ds<NP>>(160 * 1024); rc != AP_OK) return rc; \
+                      hipLaunchKernelGGL(k_mhsa_bwd_ds<NP>, gds, dim3(1024), lds_ds, s, qkv, out, dout, lse, dqkv, N, heads, scale, nt, items)
             switch (nt / 2) { case 4: DS_LAUNCH(4); break; case 5: DS_LAUNCH(5); break; case 6: DS_LAUNCH(6); break; default: DS_LAUNCH(7); break; }
 #undef DS_LAUNCH
             return ap_check_launch();
         }
     }
+    if (const int rc = hd == 32 ? ap_allow_lds<k_mhsa_bwd<32>>(160 * 1024) : ap_allow_lds<k_mhsa_bwd<64>>(160 * 1024); rc != AP_OK) return rc;
     if (hd == 32) hipLaunchKernelGGL(k_mhsa_bwd<32>, grid, dim3(512), lds, s, qkv, out, dout, lse, dqkv, N, heads, scale, nt);
     else hipLaunchKernelGGL(k_mhsa_bwd<64>, grid, dim3(512), lds, s, qkv, out, dout, lse, dqkv, N, heads, scale, nt);
     return ap_check_launch();

@@ -1034,13 +1034,9 @@ template <int C, bool BWD, bool LN = false, bool RES = false, bool INFER = false
 static int mf_launch(const MlpArgs& a, hipStream_t st) {
     static int version = 0;                  // AP_MLP_FUSED_V = 1: the one-wave-per-SIMD kernel; default 2: producer / consumer waves
     if (!version) { const char* e = getenv("AP_MLP_FUSED_V"); version = (e && e[0] == '1') ? 1 : 2; }
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k_mlp_fused<C, BWD>, hipFuncAttributeMaxDynamicSharedMemorySize, MF_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)k_mlp_fused2<C, BWD, LN, RES, INFER>, hipFuncAttributeMaxDynamicSharedMemorySize, M2_LDS_BYTES);
-        attr = true; (void)hipGetLastError();
-    }
     if (version == 1 && (LN || INFER)) return AP_ERR_UNSUPPORTED;
+    // (refused by the runtime: AP_ERR_UNSUPPORTED, on which the caller takes the two launches)
+    if (const int rc = version == 1 ? ap_allow_lds<k_mlp_fused<C, BWD>>(MF_LDS_BYTES) : ap_allow_lds<k_mlp_fused2<C, BWD, LN, RES, INFER>>(M2_LDS_BYTES); rc != AP_OK) return rc;
     if (version == 1) hipLaunchKernelGGL((k_mlp_fused<C, BWD>), dim3(a.M / MF_BM), dim3(256), MF_LDS_BYTES, st, a);
     else hipLaunchKernelGGL((k_mlp_fused2<C, BWD, LN, RES, INFER>), dim3(a.M / MF_BM), dim3(512), M2_LDS_BYTES, st, a);
     return ap_check_launch();

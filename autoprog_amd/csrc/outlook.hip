@@ -750,10 +750,8 @@ static int olk_launch(const OlkArgs& a0, int SR, size_t lds, hipStream_t s) {
     const int h = (a.H + 1) / 2, w = (a.W + 1) / 2;
     a.SR = SR; a.nstrips = (h + SR - 1) / SR; a.nitems = a.B * a.nstrips * a.heads;
     a.wp_shift = w <= 16 ? 4 : 5;
-    static int ncu = 0;
-    if (!ncu) { int dev = 0; hipDeviceProp_t pr; (void)hipGetDevice(&dev); ncu = (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }
-    static bool attr_done = false;
-    if (!attr_done) { (void)hipFuncSetAttribute((const void*)k_outlook_p<T, NSU, NPU, BWD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_done = true; (void)hipGetLastError(); }
+    const int ncu = ap_cu_count();
+    if (const int rc = ap_allow_lds<k_outlook_p<T, NSU, NPU, BWD>>(160 * 1024); rc != AP_OK) return rc;
     const int per_cu = std::max(1, std::min((int)(160 * 1024 / lds), 2048 / T));
     int grid = std::min(a.nitems, ncu * per_cu);
     grid = std::max(8, grid & ~7);                      // a multiple of 8: the XCD-contiguous item walk
@@ -786,12 +784,7 @@ static int gather_launch(bool tp, const bf16_t* in, const bf16_t* logits, int ld
         if (lds_m(SRm) <= 160 * 1024) {
             const int ns = (h + SRm - 1) / SRm;
             const dim3 gm((unsigned)(B * ns * heads));
-            static bool attr_done = false;
-            if (!attr_done) {
-                (void)hipFuncSetAttribute((const void*)k_outlook_gather_mfma<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                (void)hipFuncSetAttribute((const void*)k_outlook_gather_mfma<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr_done = true; (void)hipGetLastError();
-            }
+            if (const int rc = tp ? ap_allow_lds<k_outlook_gather_mfma<true>>(160 * 1024) : ap_allow_lds<k_outlook_gather_mfma<false>>(160 * 1024); rc != AP_OK) return rc;
             if (tp) hipLaunchKernelGGL(k_outlook_gather_mfma<true>, gm, dim3(OGT), lds_m(SRm), s, in, logits, ldl, out, H, W, heads, scale, SRm, ns);
             else hipLaunchKernelGGL(k_outlook_gather_mfma<false>, gm, dim3(OGT), lds_m(SRm), s, in, logits, ldl, out, H, W, heads, scale, SRm, ns);
             return ap_check_launch();

@@ -8,7 +8,7 @@
 // the token axis (16 consecutive fp32 = 64 B per class) and stored token-major in LDS with an
 // odd row stride.  Phase B: each wave owns 4 rows; lanes stride over classes (coalesced logits),
 // keep the row in registers, reduce max / sum-exp / sum t / sum t*x with wavefront shuffles.
-#include "common.h"
+#include "row_wide.h"
 
 #define CE_TN 16
 #define CE_MAXV 8          // classes per lane pairs: supports C <= 64*2*CE_MAXV = 1024
@@ -260,14 +260,13 @@ k_soft_ce_sparse(const bf16_t* __restrict__ logits, int ldx, const int* __restri
 
 // ---------------------------------------------------------------------------------------------------------------- rows wider than 1024
 // ldx > 64 * 2 * CE_MAXV: a row no longer fits one wave's registers (21 843 classes: 43.7 KB of bf16).  The row is staged in LDS ONCE
-// (16-byte chunks, the loads of the next batch issued before the previous one is written and reduced) and every later walk reads LDS:
-// logits once in, gradient once out, whatever the caches do.  Three walks: maximum (while staging), sums, gradient -- the exact
-// max-then-sum order of the narrow kernels, no running rescale.  A TEAM of WPR waves owns a row:
-//   WPR = 1 (ldx <= CE_WIDE_TEAM1_MAXLD): four rows per workgroup, 4 * ldx * 2 B of LDS (<= 32 KB);
-//   WPR = 4: one row per workgroup, ldx * 2 B of LDS -- three workgroups per CU at 21 848 columns, one at CE_WIDE_MAXLD = 65 536.
-// Plain grid, one workgroup per row group; two barriers per workgroup (every wave reaches both: rows beyond M are clamped and only
-// their stores are masked).  Padding columns C .. ldx-1 of the logits reach LDS and registers but are replaced by a select before
-// any use; their gradient is stored as zeros with the last chunks of the row.
+// by the walk of row_wide.h (its teams, its rules) and every later walk reads LDS: logits once in, gradient once out, whatever the caches
+// do.  Three walks: maximum (while staging), sums, gradient -- the exact max-then-sum order of the narrow kernels, no running rescale.
+//   WPR = 1 (ldx <= RW_TEAM1_MAXLD): four rows per workgroup, 4 * ldx * 2 B of LDS (<= 32 KB);
+//   WPR = 4: one row per workgroup, ldx * 2 B of LDS -- three workgroups per CU at 21 848 columns, one at RW_MAXLD = 65 536.
+// Plain grid, one workgroup per row group; two barriers per workgroup.  The wave reductions stay the xor butterflies of the narrow
+// kernels (group_max / group_sum: the DPP tree adds in another order).  Padding columns C .. ldx-1 of the logits reach LDS and
+// registers but are replaced by a select before any use; their gradient is stored as zeros with the last chunks of the row.
 //   SPARSE: a lane owns the 8 classes of a 16-byte chunk (16-byte stores).  The pairs sit one per lane (as in k_soft_ce_sparse);
 //     sum t = s + sum_k v_k and sum t x = (s / C) sum x + sum_k v_k x[i_k] need no scan, and in the gradient walk a wave's 64 chunks
 //     are one 512-class window: one ballot per window finds the pairs inside it, and each of those lands in ONE (lane, element).
@@ -275,41 +274,6 @@ k_soft_ce_sparse(const bf16_t* __restrict__ logits, int ldx, const int* __restri
 //     through (t_sb, t_sc, t_sn) -- any strides, coalesced when the target is row-major [M, C] (t_sc = 1: timm's Mixup target).  The
 //     target is walked twice (sums, gradient): 8 B per class of one row, the second walk comes from L2.  The class-major token-label
 //     tensor (t_sn = 1) is correct here and uncoalesced; it takes k_soft_ce_wide_cm below where its token tile fits LDS.
-#define CE_WIDE_MAXLD 65536
-#define CE_WIDE_TEAM1_MAXLD 4096
-
-template <int T>
-__device__ __forceinline__ float ce_wide_stage(const u32x4* __restrict__ xg, u32x4* xs, int nch, int C, int tt) {
-    constexpr int U = 4;
-    float mx = -3.0e38f;
-    u32x4 cur[U], nxt[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) cur[u] = xg[min(tt + T * u, nch - 1)];          // clamped, unconditional
-    for (int base = 0; base < nch; base += U * T) {
-        const bool more = base + U * T < nch;                                    // team-uniform: one branch around the whole batch
-        if (more) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) nxt[u] = xg[min(base + U * T + tt + T * u, nch - 1)];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int q = base + tt + T * u;
-            if (q < nch) {
-                xs[q] = cur[u];
-                float f[8];
-                unpack8(cur[u], f);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) mx = fmaxf(mx, 8 * q + j < C ? f[j] : -3.0e38f);
-            }
-        }
-        if (more) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) cur[u] = nxt[u];
-        }
-    }
-    return mx;
-}
-
 // the dense target of class pairs g = tt, tt + T, .. < ngr, four pairs per lane in flight, the next batch requested before f(g, t0, t1)
 // runs on the previous one.  mixed: t = lam1 * t[b] + lam2 * t[B-1-b] (one wave-uniform branch per batch)
 template <int T, class F>
@@ -364,11 +328,10 @@ k_soft_ce_wide(const bf16_t* __restrict__ logits, int ldx, const float* __restri
     extern __shared__ __attribute__((aligned(16))) u32x4 ce_wide_rows[];       // [4 / WPR][ldx / 8]
     __shared__ float red_mx[4], red_a[4], red_b[4], red_c[4];
     constexpr int T = 64 * WPR;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int team = wave / WPR, tw = wave % WPR, tt = tw * 64 + lane;
-    const int64_t row_raw = (int64_t)blockIdx.x * (4 / WPR) + team;
-    const bool live = row_raw < M;
-    const int64_t row = min(row_raw, M - 1);
+    const RwTeam g = rw_team<WPR>(M);
+    const int wave = g.wave, lane = g.lane, team = g.team, tw = g.tw, tt = g.tt;
+    const bool live = g.live;
+    const int64_t row = g.row;
     const int nch = ldx >> 3;
     u32x4* xs = ce_wide_rows + (size_t)team * nch;
     const int64_t b = row / rows_per_batch, n = row - b * rows_per_batch;
@@ -387,7 +350,15 @@ k_soft_ce_wide(const bf16_t* __restrict__ logits, int ldx, const float* __restri
         if (my_i < 0 || my_i >= C) { my_i = -1; my_v = 0.f; }
     }
     // ---- walk 1: global -> LDS, the maximum on the way
-    float mx = group_max<64>(ce_wide_stage<T>(reinterpret_cast<const u32x4*>(logits + row * ldx), xs, nch, C, tt));
+    float mx = -3.0e38f;
+    rw_stage<T>(reinterpret_cast<const u32x4*>(logits + row * ldx), nch, tt, [&](int q, const u32x4& v) {
+        xs[q] = v;
+        float f[8];
+        unpack8(v, f);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) mx = fmaxf(mx, 8 * q + j < C ? f[j] : -3.0e38f);
+    });
+    mx = group_max<64>(mx);
     if (lane == 0) red_mx[wave] = mx;
     __syncthreads();
     mx = red_mx[team * WPR];
@@ -400,11 +371,11 @@ k_soft_ce_wide(const bf16_t* __restrict__ logits, int ldx, const float* __restri
     const unsigned* xw = reinterpret_cast<const unsigned*>(xs);
     float se = 0.f, st = 0.f, stx = 0.f;
     if (DENSE) {
-        ce_wide_walk_target<T>(tb, tb2, mixed, lam1, lam2, t_sc, C, (C + 1) >> 1, tt, [&](int g, float t0, float t1) {
-            const unsigned w = xw[g];
+        ce_wide_walk_target<T>(tb, tb2, mixed, lam1, lam2, t_sc, C, (C + 1) >> 1, tt, [&](int p, float t0, float t1) {
+            const unsigned w = xw[p];
             const float x0 = bf_lo(w), x1 = bf_hi(w);
-            se += __expf(x0 - mx); st += t0; stx += t0 * x0;                      // 2 g < C always
-            if (2 * g + 1 < C) { se += __expf(x1 - mx); st += t1; stx += t1 * x1; }
+            se += __expf(x0 - mx); st += t0; stx += t0 * x0;                      // 2 p < C always
+            if (2 * p + 1 < C) { se += __expf(x1 - mx); st += t1; stx += t1 * x1; }
         });
     } else {
         float sx = 0.f;
@@ -437,9 +408,9 @@ k_soft_ce_wide(const bf16_t* __restrict__ logits, int ldx, const float* __restri
     // ---- walk 3: the gradient, columns C .. ldx-1 as zeros
     bf16_t* dr = dlogits + row * ldx;
     if (DENSE) {
-        ce_wide_walk_target<T>(tb, tb2, mixed, lam1, lam2, t_sc, C, ldx >> 1, tt, [&](int g, float t0, float t1) {
-            const unsigned w = xw[g];
-            const int c = 2 * g;
+        ce_wide_walk_target<T>(tb, tb2, mixed, lam1, lam2, t_sc, C, ldx >> 1, tt, [&](int p, float t0, float t1) {
+            const unsigned w = xw[p];
+            const int c = 2 * p;
             float d0 = 0.f, d1 = 0.f;
             if (c < C) d0 = gscale * (__expf(bf_lo(w) - lse) * st - t0);
             if (c + 1 < C) d1 = gscale * (__expf(bf_hi(w) - lse) * st - t1);
@@ -593,32 +564,25 @@ extern "C" int ap_loss_combine(const float* a, int64_t na, float wa, const float
     return ap_check_launch();
 }
 
-// rows wider than the register kernels take: k_soft_ce_wide, a team of one wave per row up to CE_WIDE_TEAM1_MAXLD columns and of four beyond
+// rows wider than the register kernels take: k_soft_ce_wide, a team of one wave per row up to RW_TEAM1_MAXLD columns and of four beyond
 template <bool DENSE, bool GT = false>
 static int ce_wide_launch(const ap_bf16* logits, int ldx, const float* target, int64_t t_sb, int64_t t_sc, int64_t t_sn, const int* idx, const float* val,
                           int K, int64_t p_sb, int64_t p_sn, float smoothing, int rows_per_batch, float* row_loss, ap_bf16* dlogits, float grad_scale,
                           int64_t M, int C, float mix_lam, int mix_batches, const float* mix_lam_dev, ap_stream_t stream) {
-    if (ldx > CE_WIDE_MAXLD) return AP_ERR_UNSUPPORTED;
+    if (ldx > RW_MAXLD) return AP_ERR_UNSUPPORTED;
     if (((uintptr_t)logits | (uintptr_t)dlogits) & 15) return AP_ERR_SHAPE;       // rows are moved in 16-byte chunks
     if (M == 0) return AP_OK;
-    const bool team1 = ldx <= CE_WIDE_TEAM1_MAXLD;
-    const int rpb = team1 ? 4 : 1;
-    const int64_t blocks = (M + rpb - 1) / rpb;
-    if (blocks > 0x7fffffffLL) return AP_ERR_SHAPE;
-    const size_t lds = (size_t)rpb * ldx * sizeof(bf16_t);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k_soft_ce_wide<4, DENSE, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, CE_WIDE_MAXLD * (int)sizeof(bf16_t));
-        attr = true;
-    }
-    (void)hipGetLastError();
-    if (team1)
-        hipLaunchKernelGGL((k_soft_ce_wide<1, DENSE, GT>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, logits, ldx, target, t_sb, t_sc, t_sn, idx, val, K,
+    return rw_launch(ldx, M, [&](auto wpr, unsigned blocks) {
+        constexpr int WPR = decltype(wpr)::value;
+        const size_t lds = (size_t)(4 / WPR) * ldx * sizeof(bf16_t);
+        if constexpr (WPR == 4) {                                                // (four rows of a one-wave team are 32 KB at the most)
+            if (const int rc = ap_allow_lds<k_soft_ce_wide<4, DENSE, GT>>(RW_MAXLD * (int)sizeof(bf16_t)); rc != AP_OK) return rc;
+        }
+        (void)hipGetLastError();
+        hipLaunchKernelGGL((k_soft_ce_wide<WPR, DENSE, GT>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, logits, ldx, target, t_sb, t_sc, t_sn, idx, val, K,
                            p_sb, p_sn, smoothing, rows_per_batch, row_loss, dlogits, grad_scale, M, C, mix_lam, mix_batches, mix_lam_dev);
-    else
-        hipLaunchKernelGGL((k_soft_ce_wide<4, DENSE, GT>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, logits, ldx, target, t_sb, t_sc, t_sn, idx, val, K,
-                           p_sb, p_sn, smoothing, rows_per_batch, row_loss, dlogits, grad_scale, M, C, mix_lam, mix_batches, mix_lam_dev);
-    return ap_check_launch();
+        return ap_check_launch();
+    });
 }
 
 // the class-major token-label tensor while its 16-token tile fits LDS: 12 or 20 class pairs per lane
@@ -630,13 +594,8 @@ static int ce_wide_cm_launch(const ap_bf16* logits, int ldx, const float* target
     const int64_t blocks = (M / rows_per_batch) * tiles;
     if (blocks > 0x7fffffffLL) return AP_ERR_SHAPE;
     const size_t lds = (size_t)CE_TN * (C | 1) * sizeof(float);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k_soft_ce_wide_cm<12>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)k_soft_ce_wide_cm<20>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-    }
     (void)hipGetLastError();
+    if (const int rc = ldx <= 128 * 12 ? ap_allow_lds<k_soft_ce_wide_cm<12>>(160 * 1024) : ap_allow_lds<k_soft_ce_wide_cm<20>>(160 * 1024); rc != AP_OK) return rc;
     if (ldx <= 128 * 12)
         hipLaunchKernelGGL(k_soft_ce_wide_cm<12>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, logits, ldx, target, t_sb, t_sc, t_sn, rows_per_batch,
                            row_loss, dlogits, grad_scale, M, C, tiles, mix_lam, mix_batches, mix_lam_dev);

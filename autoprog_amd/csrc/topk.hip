@@ -14,23 +14,13 @@
 // the stored class is clamped into [0, C) whatever the keys were.
 // Statistics in fp32, maximum subtracted ((x - max) is exact for bf16 operands), fixed reduction order (one DPP tree per wave, then the
 // waves of a team in index order): bit-reproducible.  No atomics, no workspace; plain grids (one workgroup per row group).
-#include "common.h"
+#include "row_wide.h"
 
 #define TK_MAXK 16
 #define TK_SR 2                    // narrow kernel: rows per wave, all of their loads issued before the first is reduced
 #define TK_NARROW_MAXLD 1024       // a row in one wave's registers: 2 chunks of 8 columns per lane
-#define TK_TEAM1_MAXLD 4096        // LDS rows: a wave per row up to here (4 rows per workgroup), four waves per row beyond
-#define TK_MAXLD 65536             // 2 B per column of LDS: 128 KB, one workgroup per CU
 #define TK_NEG_INF_CODE 0x007fu    // ~0xff80
 
-// two bf16 of a word -> their two codes
-__device__ __forceinline__ unsigned tk_encode2(unsigned w) {
-    const unsigned m = w & 0x7fff7fffu;
-    const unsigned nz = (m + 0x7fff7fffu) & 0x80008000u;          // bit 15 of a half: its magnitude is not zero (no carry between the halves)
-    w &= nz | 0x7fff7fffu;                                        // -0 -> +0: equal logits are equal codes
-    const unsigned s = (w >> 15) & 0x00010001u;
-    return w ^ (s * 0x7fffu + 0x80008000u);                       // negative: ^ 0xffff, positive: ^ 0x8000
-}
 // one chunk (columns c0 .. c0+7) with its columns >= C replaced by -inf (only the last chunks of a row take the branch)
 __device__ __forceinline__ u32x4 tk_mask8(u32x4 v, int c0, int C) {
     if (c0 + 8 > C) {
@@ -46,7 +36,7 @@ __device__ __forceinline__ u32x4 tk_mask8(u32x4 v, int c0, int C) {
 __device__ __forceinline__ u32x4 tk_encode8(const u32x4& v) {
     u32x4 o;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) o[w] = tk_encode2(v[w]);
+    for (int w = 0; w < 4; ++w) o[w] = rw_encode2(v[w]);
     return o;
 }
 // code << 16 (low half zero) -> the value
@@ -63,29 +53,6 @@ __device__ __forceinline__ unsigned tk_chunk_round(const u32x4& o, int q, unsign
     }
     return t;
 }
-// Wave reductions on the DPP path (no LDS crossbar round trip per step): lanes of a quad, the two halves of a row of 16 and the row mirrored,
-// then lane 15 of rows 0 / 2 into rows 1 / 3 and lane 31 into rows 2 / 3 -- lane 63 ends with the whole wave, read back as a wave-uniform value.
-// One fixed order for every row: the float sum is bit-reproducible.
-#define TK_DPP(x, ctrl, rows) __builtin_amdgcn_update_dpp(0, (int)(x), ctrl, rows, 0xf, false)
-__device__ __forceinline__ unsigned tk_wave_max(unsigned v) {
-    v = max(v, (unsigned)TK_DPP(v, 0xb1, 0xf));                  // quad_perm [1, 0, 3, 2]
-    v = max(v, (unsigned)TK_DPP(v, 0x4e, 0xf));                  // quad_perm [2, 3, 0, 1]
-    v = max(v, (unsigned)TK_DPP(v, 0x141, 0xf));                 // row_half_mirror
-    v = max(v, (unsigned)TK_DPP(v, 0x140, 0xf));                 // row_mirror: every lane of a row holds the row's maximum
-    v = max(v, (unsigned)TK_DPP(v, 0x142, 0xa));                 // row_bcast15 into rows 1 and 3 (others read 0: the identity)
-    v = max(v, (unsigned)TK_DPP(v, 0x143, 0xc));                 // row_bcast31 into rows 2 and 3
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ float tk_wave_sum(float v) {
-#define TK_DPP_F(x, ctrl, rows) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), ctrl, rows, 0xf, false))
-    v += TK_DPP_F(v, 0xb1, 0xf);
-    v += TK_DPP_F(v, 0x4e, 0xf);
-    v += TK_DPP_F(v, 0x141, 0xf);
-    v += TK_DPP_F(v, 0x140, 0xf);
-    v += TK_DPP_F(v, 0x142, 0xa);
-    v += TK_DPP_F(v, 0x143, 0xc);
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
 // lane k < K holds the winner of round k in `mine`; se = sum_c exp(inv_temp (x_c - max)), scale = inv_temp * log2(e)
 __device__ __forceinline__ void tk_store(unsigned mine, unsigned first, float scale, float se, int lane, int K, int C, int64_t row, int rows_per_batch,
                                          int* __restrict__ idx, float* __restrict__ val, int64_t o_sb, int64_t o_sn) {
@@ -95,7 +62,7 @@ __device__ __forceinline__ void tk_store(unsigned mine, unsigned first, float sc
         const int64_t o = b * o_sb + n * o_sn + lane;
         const float mx = tk_code_value(first & 0xffff0000u);
         const float e = __builtin_amdgcn_exp2f((tk_code_value(mine & 0xffff0000u) - mx) * scale);
-        idx[o] = min((int)(0xffffu - (mine & 0xffffu)), C - 1);
+        idx[o] = rw_key_class(mine, C);
         val[o] = e / se;
     }
 }
@@ -138,7 +105,7 @@ k_softmax_topk(const bf16_t* __restrict__ logits, int ld, int C, int K, float sc
             unsigned t = 0;
 #pragma unroll
             for (int e = 0; e < 16; ++e) t = max(t, key[e] - prev);
-            prev += tk_wave_max(t);
+            prev += rw_wave_maxu(t);
             if (j == 0) first = prev;
             mine = lane == j ? prev : mine;
         }
@@ -150,46 +117,14 @@ k_softmax_topk(const bf16_t* __restrict__ logits, int ld, int C, int K, float sc
             se += __builtin_amdgcn_exp2f((bf_lo(w) - mx) * scale);
             se += __builtin_amdgcn_exp2f((bf_hi(w) - mx) * scale);
         }
-        se = tk_wave_sum(se);
+        se = rw_wave_sum(se);
         tk_store(mine, first, scale, se, lane, K, C, row, rows_per_batch, idx, val, o_sb, o_sn);
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- 1024 < ld <= 65 536
-// The row is staged in LDS once, as codes, in 16-byte chunks (the loads of the next batch issued before the previous one is encoded and
-// written), round 0 on the way.  A TEAM of WPR waves owns a row; thread tt of the team owns chunks tt, tt + T, ..: it is the only
-// thread that ever writes or reads them, so the row itself needs no barrier -- the rounds and the sum meet in a few words of LDS
-// (one barrier each, double-buffered; every wave reaches every barrier: rows beyond M are clamped and only their stores are masked).
-template <int T>
-__device__ __forceinline__ unsigned tk_stage(const u32x4* __restrict__ xg, u32x4* xs, int nch, int C, int tt) {
-    constexpr int U = 4;
-    unsigned t = 0;
-    u32x4 cur[U], nxt[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) cur[u] = xg[min(tt + T * u, nch - 1)];          // clamped, unconditional
-    for (int base = 0; base < nch; base += U * T) {
-        const bool more = base + U * T < nch;                                    // team-uniform: one branch around the whole batch
-        if (more) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) nxt[u] = xg[min(base + U * T + tt + T * u, nch - 1)];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int q = base + tt + T * u;
-            if (q < nch) {
-                const u32x4 o = tk_encode8(tk_mask8(cur[u], 8 * q, C));
-                xs[q] = o;
-                t = tk_chunk_round(o, q, 0u, t);
-            }
-        }
-        if (more) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) cur[u] = nxt[u];
-        }
-    }
-    return t;
-}
-
+// The row is staged in LDS once, as codes, round 0 on the way (the staging walk, the team and their rules: row_wide.h).  The rounds and the
+// sum meet in a few words of LDS (one barrier each, double-buffered; none for a team of one wave).
 template <int WPR>
 __global__ void __launch_bounds__(256)
 k_softmax_topk_wide(const bf16_t* __restrict__ logits, int ld, int C, int K, float scale, int* __restrict__ idx, float* __restrict__ val,
@@ -198,23 +133,24 @@ k_softmax_topk_wide(const bf16_t* __restrict__ logits, int ld, int C, int K, flo
     __shared__ unsigned red_k[2][4];
     __shared__ float red_s[4];
     constexpr int T = 64 * WPR;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int team = wave / WPR, tw = wave % WPR, tt = tw * 64 + lane;
-    const int64_t row_raw = (int64_t)blockIdx.x * (4 / WPR) + team;
-    const bool live = row_raw < M;
-    const int64_t row = min(row_raw, M - 1);
+    const RwTeam g = rw_team<WPR>(M);
+    const int wave = g.wave, lane = g.lane, team = g.team, tw = g.tw, tt = g.tt;
     const int nch = ld >> 3;
     u32x4* xs = tk_rows + (size_t)team * nch;
     unsigned prev = 0, mine = 0, first = 0;
     for (int j = 0; j < K; ++j) {
         unsigned t = 0;
         if (j == 0) {
-            t = tk_stage<T>(reinterpret_cast<const u32x4*>(logits + row * ld), xs, nch, C, tt);
+            rw_stage<T>(reinterpret_cast<const u32x4*>(logits + g.row * ld), nch, tt, [&](int q, const u32x4& v) {
+                const u32x4 o = tk_encode8(tk_mask8(v, 8 * q, C));
+                xs[q] = o;
+                t = tk_chunk_round(o, q, 0u, t);
+            });
         } else {
 #pragma unroll 2
             for (int q = tt; q < nch; q += T) t = tk_chunk_round(xs[q], q, prev, t);
         }
-        t = tk_wave_max(t);
+        t = rw_wave_maxu(t);
         if (WPR > 1) {
             if (lane == 0) red_k[j & 1][wave] = t;
             __syncthreads();
@@ -237,7 +173,7 @@ k_softmax_topk_wide(const bf16_t* __restrict__ logits, int ld, int C, int K, flo
             se += __builtin_amdgcn_exp2f((tk_code_value(o[w] & 0xffff0000u) - mx) * scale);
         }
     }
-    se = tk_wave_sum(se);
+    se = rw_wave_sum(se);
     if (WPR > 1) {
         if (lane == 0) red_s[wave] = se;
         __syncthreads();
@@ -245,14 +181,14 @@ k_softmax_topk_wide(const bf16_t* __restrict__ logits, int ld, int C, int K, flo
 #pragma unroll
         for (int w = 1; w < WPR; ++w) se += red_s[team * WPR + w];
     }
-    if (live && tw == 0) tk_store(mine, first, scale, se, lane, K, C, row, rows_per_batch, idx, val, o_sb, o_sn);
+    if (g.live && tw == 0) tk_store(mine, first, scale, se, lane, K, C, g.row, rows_per_batch, idx, val, o_sb, o_sn);
 }
 
 extern "C" int ap_softmax_topk_rows(const ap_bf16* logits, int ld, int C, int K, float inv_temp, int* idx, float* val, int64_t o_sb, int64_t o_sn,
                                     int rows_per_batch, int64_t M, ap_stream_t stream) {
     if (M < 0 || C <= 0 || ld < C || (ld & 7) || K < 1 || K > TK_MAXK || K > C || rows_per_batch <= 0) return AP_ERR_SHAPE;
     if (!(inv_temp > 0.f) || !(inv_temp < 3.0e38f)) return AP_ERR_SHAPE;
-    if (ld > TK_MAXLD) return AP_ERR_UNSUPPORTED;
+    if (ld > RW_MAXLD) return AP_ERR_UNSUPPORTED;
     if (M == 0) return AP_OK;
     if (!logits || !idx || !val) return AP_ERR_NULL;
     if ((uintptr_t)logits & 15) return AP_ERR_SHAPE;                            // rows are moved in 16-byte chunks
@@ -265,19 +201,13 @@ extern "C" int ap_softmax_topk_rows(const ap_bf16* logits, int ld, int C, int K,
         hipLaunchKernelGGL(k_softmax_topk, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, ld, C, K, scale, idx, val, o_sb, o_sn, rows_per_batch, M);
         return ap_check_launch();
     }
-    const bool team1 = ld <= TK_TEAM1_MAXLD;
-    const int rpb = team1 ? 4 : 1;
-    const int64_t blocks = (M + rpb - 1) / rpb;
-    if (blocks > 0x7fffffffLL) return AP_ERR_SHAPE;
-    const size_t lds = (size_t)rpb * ld * sizeof(bf16_t);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k_softmax_topk_wide<4>, hipFuncAttributeMaxDynamicSharedMemorySize, TK_MAXLD * (int)sizeof(bf16_t));
-        attr = true;
-    }
-    if (team1)
-        hipLaunchKernelGGL(k_softmax_topk_wide<1>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, x, ld, C, K, scale, idx, val, o_sb, o_sn, rows_per_batch, M);
-    else
-        hipLaunchKernelGGL(k_softmax_topk_wide<4>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, x, ld, C, K, scale, idx, val, o_sb, o_sn, rows_per_batch, M);
-    return ap_check_launch();
+    return rw_launch(ld, M, [&](auto wpr, unsigned blocks) {
+        constexpr int WPR = decltype(wpr)::value;
+        const size_t lds = (size_t)(4 / WPR) * ld * sizeof(bf16_t);
+        if constexpr (WPR == 4) {                                                // (four rows of a one-wave team are 32 KB at the most)
+            if (const int rc = ap_allow_lds<k_softmax_topk_wide<4>>(RW_MAXLD * (int)sizeof(bf16_t)); rc != AP_OK) return rc;
+        }
+        hipLaunchKernelGGL(k_softmax_topk_wide<WPR>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, x, ld, C, K, scale, idx, val, o_sb, o_sn, rows_per_batch, M);
+        return ap_check_launch();
+    });
 }

@@ -96,6 +96,8 @@ def launch(lib, xs, xt, mode, T, gs, guard):
 # two); (3, 1025) .. (5, 4096): LDS rows, one wave per row; (2, 4104) ..: four waves per row; soft mode stages both rows up to (1, 40704) and
 # only the student's from (1, 40712) on -- there the teacher row, NaN-padded with its own leading dimension, is read from global memory in all three walks
 SHAPES = [(1, 8), (5, 1000), (37, 1000), (7, 1024), (3, 1025), (37, 1100), (5, 4096), (2, 4104), (2, 21843), (1, 40704), (1, 40712), (1, 65536)]
+# the last chunk of a row one chunk either side of a batch of the staging walk (256 chunks for a team of one wave, 1024 for a team of four)
+SHAPES += [(3, 2040), (3, 2041), (3, 2049), (3, 8185), (3, 8193)]
 MODES = [("soft", 0, 1.0), ("soft", 0, 3.0), ("hard", 1, 1.0)]
 
 

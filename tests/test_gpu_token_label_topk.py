@@ -23,6 +23,10 @@ M_ROWS, RPB = 37, 8                 # 37 rows in batches of 8: five batches, the
 IDX_SENTINEL, VAL_SENTINEL = -7777, -123.25
 ROW_CASES = [(5, 8, 5), (16, 16, 16), (512, 512, 16), (513, 520, 5), (1000, 1000, 5), (1001, 1008, 8), (1024, 1024, 16), (1025, 1032, 5),
              (4096, 4096, 16), (4097, 4104, 5), (21843, 21848, 8), (65536, 65536, 16)]
+# the end of a row one chunk either side of a batch of the staging walk (4 chunks per thread in flight: 256 chunks = 2048 columns for a team of
+# one wave, 1024 chunks = 8192 columns for a team of four): 255 chunks, 256 with the last partly masked, 257 (a second batch of one chunk and
+# three clamped loads); 1024 and 1025
+ROW_CASES += [(2040, 2040, 5), (2041, 2048, 16), (2049, 2056, 5), (8185, 8192, 16), (8193, 8200, 5)]
 
 
 @functools.lru_cache(maxsize=None)

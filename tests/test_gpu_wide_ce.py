@@ -104,6 +104,9 @@ WIDE_SHAPES = [(1, 1, 1025), (3, 5, 1025), (2, 17, 1100), (5, 1, 2048), (2, 3, 3
 # dense, class-major: rows_per_batch > 1 up to 1536 columns and up to 2560 take k_soft_ce_wide_cm with 12 and 20 class pairs per lane ((2, 5, 1600): the
 # second), everything else k_soft_ce_wide: one wave per row up to 4096 columns, four beyond.  Both runs of a case take the same kernel.
 WIDE_PARAMS = ([(k,) + s for k in ("dense", "sparse") for s in WIDE_SHAPES] + [("rowmajor", 1, 7, 21843), ("rowmajor", 3, 5, 1025), ("dense", 2, 5, 1600)])
+# the last chunk of a row one chunk either side of a batch of the staging walk (256 chunks = 2048 columns for a team of one wave, 1024 chunks =
+# 8192 columns for a team of four); one row per image, so that the dense cases take k_soft_ce_wide as well
+WIDE_PARAMS += [(k, b, 1, C) for C in (2040, 2041, 2049, 8185, 8193) for k, b in (("sparse", 5), ("rowmajor", 3))]
 
 
 @pytest.mark.parametrize("kind,B,N,C", WIDE_PARAMS)
