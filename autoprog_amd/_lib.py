@@ -59,6 +59,12 @@ class InputPrepArgs(Structure):
                 ("n_boxes", c_int), ("erase_mode", c_int)]
 
 
+class CropResizeArgs(Structure):
+    """ap_crop_resize_args (include/autoprog_hip.h)"""
+    _fields_ = [("u8", c_void_p), ("layout", c_int), ("B", c_int), ("Hi", c_int), ("Wi", c_int),
+                ("out", c_void_p), ("S", c_int), ("records", c_void_p), ("records_host", c_void_p)]
+
+
 class PatchMap(Structure):
     """ap_patch_map (include/autoprog_hip.h)"""
     _fields_ = [("group", c_int), ("group_stride", c_int), ("row_stride", c_int), ("kseg", c_int), ("kseg_stride", c_int)]
@@ -177,6 +183,8 @@ _SIGNATURES["ap_distill_fwd_bwd"] = (_I, [_P, _I, _P, _I, _I, _I, _F, _P, _P, _F
 # class rows of TokenLabelGTCrossEntropy on the sparse target (csrc/softce.hip): ap_soft_ce_sparse_gt_fwd_bwd(logits, ldx, idx, val, K, p_sb, p_s0,
 # p_s1, smoothing, row_loss, dlogits, grad_scale, B, C, mix_lam, mix_batches, mix_lam_dev, stream)
 _SIGNATURES["ap_soft_ce_sparse_gt_fwd_bwd"] = (_I, [_P, _I, _P, _P, _I, _L, _L, _L, _F, _P, _P, _F, _L, _I, _F, _I, _P, _P])
+# per-image crop box + flip + bilinear resize of a uint8 batch (csrc/crop.hip)
+_SIGNATURES["ap_crop_resize_u8"] = (_I, [POINTER(CropResizeArgs), _P])
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 EXPECTED_ABI = 7                     # ap_abi_version() of the library these ctypes Structures mirror (include/autoprog_hip.h)

@@ -16,7 +16,12 @@ no `cutmix_minmax`; the collate-time blend is done in fp32 on the normalised val
 images and rounds the result to uint8 again (at most half a grey level, 0.009 after normalisation); the per-pixel erase noise comes
 from a counter-based generator keyed by (seed, step) so that a launch is a pure function of its inputs (replayable in a HIP graph);
 and token labels are not mixed here: tlt's TokenLabelMixup also cuts the label maps, which is out of scope -- with a
-SparseTokenLabelTarget only normalise / erase / resize apply, and asking for Mixup there raises."""
+SparseTokenLabelTarget only normalise / erase / resize apply, and asking for Mixup there raises.
+
+In front of it, DeviceRandomResizedCrop does the loader's random-resized crop and horizontal flip on the device as well: one box and one
+flip per image drawn on the host, one launch of `ops.crop_resize_u8` (csrc/crop.hip) from the loader's fixed-size uint8 canvases to the
+uint8 batch at the stage's resolution that `prep` takes -- the per-stage crop scale of AutoProg's schedule is then an attribute, where
+the reference rebuilds its loader (main_prog.py:651-653, 840-846)."""
 import math
 import random
 
@@ -234,3 +239,141 @@ class DeviceBatchPrep:
         ev.record()
         return PreparedBatch(u8.contiguous(), self.layout, self.table(), dev, host, self.mix_enabled, self.re_count, self.re_mode,
                              self.last["lam"], self)
+
+
+class DeviceRandomResizedCrop:
+    """timm's RandomResizedCropAndInterpolation + RandomHorizontalFlip as host-side draws and one device launch (ops.crop_resize_u8,
+    csrc/crop.hip).  The loader hands over one fixed-size decoded uint8 canvas per image; `crop(u8, size)` draws a box and a flip per
+    image and lands each box at size x size directly -- the stage's resolution r, one bilinear resample without antialiasing where the
+    reference does two (RandomResizedCrop to 224 in the loader, F.interpolate to r on the GPU, main_prog.py:973-974).  The result is the
+    uint8 batch DeviceBatchPrep.prep takes.
+
+    The decisions come from this object's own random.Random(seed) (never the global streams) and are written into the next slot of a
+    ring of pinned blocks that reaches the device in one small copy, as DeviceBatchPrep's do.  The rule (timm 0.4.5 transforms.py,
+    `get_params`), per image over its extent (eh, ew), in this draw order:
+      box    up to 10 attempts: target = uniform(scale[0], scale[1]) * (eh ew), aspect = exp(uniform(log ratio[0], log ratio[1])),
+             w = int(round(sqrt(target aspect))), h = int(round(sqrt(target / aspect))), accepted iff 0 < w <= ew and 0 < h <= eh (the
+             `0 <` is added here: timm can return an empty box on a tiny image), then top = randint(0, eh - h), left = randint(0, ew - w)
+             (inclusive).  After 10 refusals the central crop with the ratio clamped: ew / eh < ratio[0]: w = ew, h = int(round(w / ratio[0]));
+             ew / eh > ratio[1]: h = eh, w = int(round(h * ratio[1])); otherwise the whole extent; top = (eh - h) // 2, left = (ew - w) // 2
+      flip   one random(), ALWAYS drawn; the image is flipped iff it is below hflip (so the stream does not depend on hflip)
+    scale, ratio and hflip are plain attributes (AutoProgDriver sets `scale` per stage from the schedule's `resize` list); `last` holds the
+    records of the last draw or centre crop, one (top, left, h, w, flip) per image."""
+    SLOTS = 8
+
+    def __init__(self, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), hflip=0.5, size=None, seed=0, layout="nchw", device="cuda"):
+        if layout not in ("nchw", "nhwc"):
+            raise ValueError("layout must be nchw or nhwc")
+        self.scale, self.ratio, self.hflip = tuple(scale), tuple(ratio), float(hflip)
+        self.size, self.seed, self.layout, self.device = size, int(seed), layout, torch.device(device)
+        self._py = random.Random(self.seed)
+        self._B = None
+        self.last = None
+
+    def _alloc(self, B):
+        ring = torch.zeros(self.SLOTS, max(B, 1) * ops.CROP_RECORD_WORDS, dtype=torch.int32)
+        self._ring = ring.pin_memory() if self.device.type == "cuda" and torch.cuda.is_available() else ring
+        self._dev = [None] * self.SLOTS
+        self._events = [None] * self.SLOTS
+        self._slot, self._B = 0, B
+
+    def _next(self, B):
+        """-> the next slot's host block as a zeroed [B, 8] int32 array"""
+        if self._B != B:
+            self._alloc(B)
+        self._slot = (self._slot + 1) % self.SLOTS
+        ev = self._events[self._slot]
+        if ev is not None:
+            ev.synchronize()                   # the copy that last read this slot has executed
+        a = self._ring[self._slot].numpy().reshape(max(B, 1), ops.CROP_RECORD_WORDS)
+        a[:] = 0
+        return a
+
+    @staticmethod
+    def _extents(B, H, W, extents):
+        if extents is None:
+            return [(H, W)] * B
+        e = np.asarray(extents.cpu() if torch.is_tensor(extents) else extents)
+        if e.shape != (B, 2) or not np.issubdtype(e.dtype, np.integer):
+            raise ValueError("extents: an integer [B, 2] array of (eh, ew)")
+        if B and (e.min() < 1 or e[:, 0].max() > H or e[:, 1].max() > W):
+            raise ValueError("extents: 1 <= eh <= %d and 1 <= ew <= %d" % (H, W))
+        return [(int(eh), int(ew)) for eh, ew in e]
+
+    def _box(self, eh, ew):
+        py, area = self._py, eh * ew
+        lo, hi = math.log(self.ratio[0]), math.log(self.ratio[1])
+        for _ in range(10):
+            target = py.uniform(self.scale[0], self.scale[1]) * area
+            aspect = math.exp(py.uniform(lo, hi))
+            w, h = int(round(math.sqrt(target * aspect))), int(round(math.sqrt(target / aspect)))
+            if 0 < w <= ew and 0 < h <= eh:
+                return py.randint(0, eh - h), py.randint(0, ew - w), h, w
+        in_ratio = ew / eh
+        if in_ratio < self.ratio[0]:
+            w = ew
+            h = min(max(int(round(w / self.ratio[0])), 1), eh)
+        elif in_ratio > self.ratio[1]:
+            h = eh
+            w = min(max(int(round(h * self.ratio[1])), 1), ew)
+        else:
+            h, w = eh, ew
+        return (eh - h) // 2, (ew - w) // 2, h, w
+
+    def draw(self, B, H, W, extents=None):
+        """-> the host block (int32 CPU tensor, B records of 8 words) of the next crop: one box and one flip per image"""
+        ext = self._extents(B, H, W, extents)
+        a = self._next(B)
+        rnd, hflip = self._py.random, self.hflip
+        self.last = [self._box(eh, ew) + (int(rnd() < hflip),) for eh, ew in ext]
+        if B:
+            a[:B, :5] = self.last              # (one assignment: a per-image write costs more host time than the draw)
+        return self._ring[self._slot]
+
+    def center_records(self, B, H, W, crop_pct=0.875, extents=None):
+        """-> the host block of the central square boxes of side int(round(crop_pct * min(eh, ew))), no flip; nothing is drawn"""
+        ext = self._extents(B, H, W, extents)
+        a = self._next(B)
+        self.last = []
+        for eh, ew in ext:
+            side = min(max(int(round(crop_pct * min(eh, ew))), 1), min(eh, ew))
+            self.last.append(((eh - side) // 2, (ew - side) // 2, side, side, 0))
+        if B:
+            a[:B, :5] = self.last
+        return self._ring[self._slot]
+
+    def _canvas(self, u8):
+        if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 4 or not u8.is_cuda:
+            raise ValueError("DeviceRandomResizedCrop: a uint8 [B,3,H,W] / [B,H,W,3] batch on the device")
+        return (u8.shape[0],) + ((u8.shape[2], u8.shape[3]) if self.layout == "nchw" else (u8.shape[1], u8.shape[2]))
+
+    def _launch(self, u8, size, host):
+        dev = self._dev[self._slot]
+        if dev is None:
+            dev = self._dev[self._slot] = torch.empty(host.numel(), dtype=torch.int32, device=u8.device)
+        dev.copy_(host, non_blocking=True)
+        ev = self._events[self._slot]
+        if ev is None:
+            ev = self._events[self._slot] = torch.cuda.Event()
+        ev.record()
+        return ops.crop_resize_u8(u8.contiguous(), size, dev, layout=self.layout, host_records=host)
+
+    def _size(self, size):
+        size = self.size if size is None else size
+        if size is None or int(size) < 1:
+            raise ValueError("DeviceRandomResizedCrop: an output size >= 1 (crop(u8, size) or the constructor's size)")
+        return int(size)
+
+    def crop(self, u8, size=None, extents=None):
+        """uint8 device batch -> uint8 [B,3,S,S] / [B,S,S,3]: draws a box and a flip per image, one copy and one launch.  extents: optional
+        integer [B,2] (eh, ew) for images that fill only the top-left part of a padded canvas (default: the whole canvas)"""
+        size = self._size(size)
+        B, H, W = self._canvas(u8)
+        return self._launch(u8, size, self.draw(B, H, W, extents))
+
+    def center(self, u8, size, crop_pct=0.875, extents=None):
+        """the same launch on the central square box of side int(round(crop_pct * min(eh, ew))), no flip, no draw: on a fixed canvas the
+        validation-time resize and centre crop"""
+        size = self._size(size)
+        B, H, W = self._canvas(u8)
+        return self._launch(u8, size, self.center_records(B, H, W, crop_pct, extents))

@@ -32,7 +32,7 @@ class AutoProgDriver:
     def __init__(self, model, loss_fn, optimizer, reducer, get_batch, r_list, l_list, dp_list, grow_epochs, steps_per_epoch,
                  search_epochs=2, auto_grow=True, probe_batches=4, time_steps=4, seed=0, log=None, original_batch_splits=1,
                  r_max=None, dist_bn="", use_graphs=False, graph_after=2, clip_grad=None, clip_mode="norm", get_val_batches=None,
-                 batch_prep=None, re_list=None, skip_nonfinite=False, teacher=None):
+                 batch_prep=None, re_list=None, skip_nonfinite=False, teacher=None, crop=None, resize_list=None):
         """model: supernet sized for l_list[-1] (e.g. volo_h12_l18); optimizer: FlatAdamWEma over it; reducer: its
         GradientBucketReducer; r_list / l_list / dp_list / grow_epochs: the stage schedule (prog/progressive.py:4-31);
         get_batch(r): a training batch (images at ANY size -- the stem resizes to r -- and a token-label target for r // 16).
@@ -76,7 +76,24 @@ class AutoProgDriver:
         recipe, distillation with Mixup / CutMix.
         An EMA copy of the student teaches like any other network: TeacherLabeler(optimizer.ema_model(i), ...) /
         TeacherLogits(optimizer.ema_model(i)).  Every live shadow module of the optimizer (FlatAdamWEma.live_ema_models) is kept at the
-        student's elastic configuration -- depth and resolution of the stage or of a search's candidate -- and grows with it."""
+        student's elastic configuration -- depth and resolution of the stage or of a search's candidate -- and grows with it.
+        crop: a data.DeviceRandomResizedCrop (needs a batch_prep).  A uint8 image tensor from get_batch(r, ...) -- the loader's fixed-size
+        decoded canvases -- then goes through crop.crop(images, r) in front of batch_prep.prep: the random-resized crop and flip land at the
+        stage's (or a search candidate's) resolution in one launch, the preparation's resize is then the identity, and Mixup / CutMix /
+        erase boxes are drawn in the r x r frame (timm's rules are relative to the image size).  The launch stays outside captured graphs:
+        its output reaches a graph through the copy GraphedStep.step makes into its static uint8 buffer.  A teacher sees the crop the
+        student sees.  resize_list: the per-stage crop scale range (the eighth value of prog.progressive.progressive_schedule, which the
+        reference realises by rebuilding its loader, main_prog.py:651-653, 840-846): crop.scale is set to tuple(resize_list[stage]) at
+        every stage change, where re_prob is set; a search crops with the scale of the stage it starts from.  Both None (default):
+        nothing changes."""
+        if crop is not None and batch_prep is None:
+            raise ValueError("crop needs a batch_prep: the cropped uint8 batch is what DeviceBatchPrep.prep takes")
+        if crop is not None and getattr(crop, "layout", None) != getattr(batch_prep, "layout", None):
+            raise ValueError("crop and batch_prep must use the same layout")
+        if resize_list is not None:
+            if crop is None or len(resize_list) != len(r_list) or any(len(tuple(s)) != 2 for s in resize_list):
+                raise ValueError("resize_list needs a crop and one [lo, hi] entry per stage")
+        self.crop, self.resize_list = crop, ([tuple(s) for s in resize_list] if resize_list is not None else None)
         if teacher is not None:
             from .teacher import TeacherLogits
             if batch_prep is not None and getattr(batch_prep, "mix_enabled", False) and not isinstance(teacher, TeacherLogits):
@@ -117,6 +134,8 @@ class AutoProgDriver:
     def _prepared_batch(self, *a):
         images, target = self._raw_get_batch(*a)
         if torch.is_tensor(images) and images.dtype == torch.uint8:
+            if self.crop is not None:                                      # a[0]: the resolution of the stage or of the search's candidate
+                images = self.crop.crop(images, a[0])
             images = self.batch_prep.prep(images)
             if self.teacher is None and torch.is_tensor(target) and target.dim() == 1 and not target.dtype.is_floating_point:
                 target = images.target(target)
@@ -343,6 +362,8 @@ class AutoProgDriver:
                 stage = self.grow_epochs.index(epoch)
                 if self.re_list is not None:                               # the stage's loader is built with its own re_prob
                     self.batch_prep.re_prob = float(self.re_list[stage])
+                if self.resize_list is not None:                           # ... and with its own crop scale range
+                    self.crop.scale = tuple(self.resize_list[stage])
                 if self.auto_grow and stage < len(self.grow_epochs) - 1:
                     r, l = self.search(stage, epoch)
                     skip.update(range(epoch, epoch + self.search_epochs))      # the search consumed these epochs (main_prog.py:856-857)

@@ -657,6 +657,29 @@ typedef struct ap_input_prep_args {
 } ap_input_prep_args;
 int ap_input_prep(const ap_input_prep_args* args, ap_stream_t stream);
 
+/* ---- per-image crop box + horizontal flip + bilinear resize of a uint8 batch in one launch (additive in ABI version 7; csrc/crop.hip).
+ * The random-resized crop and flip of the reference's loader, whose per-stage scale range it realises by rebuilding the loader
+ * (main_prog.py:651-653, 1513-1515; the rebuilds at :711-712, :840-846).  u8: [B,3,Hi,Wi] (AP_PREP_NCHW) or [B,Hi,Wi,3] (AP_PREP_NHWC),
+ * 16-byte aligned; out: uint8 [B,3,S,S] / [B,S,S,3] in the same layout, any S >= 1, any alignment.
+ * records (DEVICE): B records of 8 int32 words: top, left, h, w, flip, then three zero words.  Image b's output is the box
+ * rows [top, top + h) x columns [left, left + w) resized to S x S as if the image were cropped first (fp32, bilinear, align_corners = False;
+ * NO antialiasing when scaling down, as the reference's own 224 -> r F.interpolate): for output column ox, o = flip ? S-1-ox : ox,
+ * f = max((o + 0.5) * (w / S) - 0.5, 0), x0 = min(floor(f), w-1), x1 = min(x0+1, w-1), lx = f - x0; rows the same with h, never flipped;
+ * v = (1-ly)*((1-lx)*p00 + lx*p01) + ly*((1-lx)*p10 + lx*p11); out = clamp(rint(v), 0, 255), half to even; every operation rounded.
+ * records_host (nullable): a host copy of the records; when given every record is checked against the image before the launch
+ * (h, w >= 1, the box inside Hi x Wi, flip in {0, 1}: AP_ERR_SHAPE).  The kernel clamps every record into the image, so a record it
+ * was not shown on the host cannot make it read or write out of bounds; it reads nothing past the last byte of the batch.
+ * AP_ERR_NULL: args, u8, out or records NULL.  AP_ERR_SHAPE: a non-positive size, a bad layout, a misaligned u8, a bad host record, more
+ * than 2^40 input bytes.  AP_ERR_UNSUPPORTED: the source rows of one output row exceed the 60 KB of LDS a launch takes (the budget depends
+ * on Hi, Wi, S and the layout alone, never on the records).  B == 0 succeeds without a launch.  Every check comes before the launch. */
+typedef struct ap_crop_resize_args {
+    const unsigned char* u8; int layout; int B, Hi, Wi;
+    unsigned char* out; int S;
+    const int* records;              /* DEVICE [B][8] */
+    const int* records_host;         /* nullable host copy, validated */
+} ap_crop_resize_args;
+int ap_crop_resize_u8(const ap_crop_resize_args* args, ap_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
