@@ -65,6 +65,11 @@ class CropResizeArgs(Structure):
                 ("out", c_void_p), ("S", c_int), ("records", c_void_p), ("records_host", c_void_p)]
 
 
+class CropResampleArgs(Structure):
+    """ap_crop_resample_args (include/autoprog_hip.h)"""
+    _fields_ = CropResizeArgs._fields_
+
+
 class PatchMap(Structure):
     """ap_patch_map (include/autoprog_hip.h)"""
     _fields_ = [("group", c_int), ("group_stride", c_int), ("row_stride", c_int), ("kseg", c_int), ("kseg_stride", c_int)]
@@ -185,6 +190,8 @@ _SIGNATURES["ap_distill_fwd_bwd"] = (_I, [_P, _I, _P, _I, _I, _I, _F, _P, _P, _F
 _SIGNATURES["ap_soft_ce_sparse_gt_fwd_bwd"] = (_I, [_P, _I, _P, _P, _I, _L, _L, _L, _F, _P, _P, _F, _L, _I, _F, _I, _P, _P])
 # per-image crop box + flip + bilinear resize of a uint8 batch (csrc/crop.hip)
 _SIGNATURES["ap_crop_resize_u8"] = (_I, [POINTER(CropResizeArgs), _P])
+# the same with Pillow's antialiased bilinear / bicubic filters, byte for byte (csrc/resample.hip)
+_SIGNATURES["ap_crop_resample_u8"] = (_I, [POINTER(CropResampleArgs), _P])
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 EXPECTED_ABI = 7                     # ap_abi_version() of the library these ctypes Structures mirror (include/autoprog_hip.h)

@@ -258,12 +258,23 @@ class DeviceRandomResizedCrop:
              ew / eh > ratio[1]: h = eh, w = int(round(h * ratio[1])); otherwise the whole extent; top = (eh - h) // 2, left = (ew - w) // 2
       flip   one random(), ALWAYS drawn; the image is flipped iff it is below hflip (so the stream does not depend on hflip)
     scale, ratio and hflip are plain attributes (AutoProgDriver sets `scale` per stage from the schedule's `resize` list); `last` holds the
-    records of the last draw or centre crop, one (top, left, h, w, flip) per image."""
-    SLOTS = 8
+    records of the last draw or centre crop, one (top, left, h, w, flip) per image.
 
-    def __init__(self, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), hflip=0.5, size=None, seed=0, layout="nchw", device="cuda"):
+    interpolation (a plain attribute too): None is the two-tap bilinear sample above.  "bilinear", "bicubic" or "random" resample each
+    box as the reference's loader does, with Pillow's antialiased filter (ops.crop_resample_u8, csrc/resample.hip: byte for byte
+    Image.crop(box).resize((size, size), filter), flipped afterwards).  `last` then holds (top, left, h, w, flip, filter) with filter
+    ops.RESAMPLE_BILINEAR / RESAMPLE_BICUBIC.  A fixed filter draws nothing more; "random" is timm 0.4.5's
+    `random.choice(self.interpolation)` inside `__call__`, after `get_params` and before the flip transform: per image the draw order
+    is box, then choice((bilinear, bicubic)), then flip."""
+    SLOTS = 8
+    FILTERS = {"bilinear": ops.RESAMPLE_BILINEAR, "bicubic": ops.RESAMPLE_BICUBIC}
+
+    def __init__(self, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), hflip=0.5, size=None, seed=0, layout="nchw", device="cuda",
+                 interpolation=None):
         if layout not in ("nchw", "nhwc"):
             raise ValueError("layout must be nchw or nhwc")
+        self._filter(interpolation, True)
+        self.interpolation = interpolation
         self.scale, self.ratio, self.hflip = tuple(scale), tuple(ratio), float(hflip)
         self.size, self.seed, self.layout, self.device = size, int(seed), layout, torch.device(device)
         self._py = random.Random(self.seed)
@@ -320,26 +331,50 @@ class DeviceRandomResizedCrop:
             h, w = eh, ew
         return (eh - h) // 2, (ew - w) // 2, h, w
 
+    @classmethod
+    def _filter(cls, interpolation, random_too):
+        """None -> 0 (the two-tap sample), a named filter -> its code, "random" -> None"""
+        if interpolation is None:
+            return 0
+        if interpolation == "random" and random_too:
+            return None
+        if interpolation not in cls.FILTERS:
+            raise ValueError("interpolation must be None, 'bilinear', 'bicubic'%s, got %r" % (" or 'random'" if random_too else "", interpolation))
+        return cls.FILTERS[interpolation]
+
     def draw(self, B, H, W, extents=None):
-        """-> the host block (int32 CPU tensor, B records of 8 words) of the next crop: one box and one flip per image"""
+        """-> the host block (int32 CPU tensor, B records of 8 words) of the next crop: one box and one flip per image, and with
+        interpolation "random" one filter"""
         ext = self._extents(B, H, W, extents)
         a = self._next(B)
         rnd, hflip = self._py.random, self.hflip
-        self.last = [self._box(eh, ew) + (int(rnd() < hflip),) for eh, ew in ext]
+        filt = self._filter(self.interpolation, True)
+        if filt == 0:
+            self.last = [self._box(eh, ew) + (int(rnd() < hflip),) for eh, ew in ext]
+        elif filt is None:
+            choice, both = self._py.choice, (ops.RESAMPLE_BILINEAR, ops.RESAMPLE_BICUBIC)
+            self.last = []
+            for eh, ew in ext:
+                box, f = self._box(eh, ew), choice(both)            # box, filter, flip: timm's order
+                self.last.append(box + (int(rnd() < hflip), f))
+        else:
+            self.last = [self._box(eh, ew) + (int(rnd() < hflip), filt) for eh, ew in ext]
         if B:
-            a[:B, :5] = self.last              # (one assignment: a per-image write costs more host time than the draw)
+            a[:B, :5 + (filt != 0)] = self.last    # (one assignment: a per-image write costs more host time than the draw)
         return self._ring[self._slot]
 
-    def center_records(self, B, H, W, crop_pct=0.875, extents=None):
-        """-> the host block of the central square boxes of side int(round(crop_pct * min(eh, ew))), no flip; nothing is drawn"""
+    def center_records(self, B, H, W, crop_pct=0.875, extents=None, interpolation=None):
+        """-> the host block of the central square boxes of side int(round(crop_pct * min(eh, ew))), no flip; nothing is drawn.
+        interpolation: None (the object's setting), "bilinear" or "bicubic"; "random" is refused, here and as the object's setting"""
+        filt = self._filter(self.interpolation if interpolation is None else interpolation, False)
         ext = self._extents(B, H, W, extents)
         a = self._next(B)
         self.last = []
         for eh, ew in ext:
             side = min(max(int(round(crop_pct * min(eh, ew))), 1), min(eh, ew))
-            self.last.append(((eh - side) // 2, (ew - side) // 2, side, side, 0))
+            self.last.append(((eh - side) // 2, (ew - side) // 2, side, side, 0) + ((filt,) if filt else ()))
         if B:
-            a[:B, :5] = self.last
+            a[:B, :5 + (filt != 0)] = self.last
         return self._ring[self._slot]
 
     def _canvas(self, u8):
@@ -347,7 +382,7 @@ class DeviceRandomResizedCrop:
             raise ValueError("DeviceRandomResizedCrop: a uint8 [B,3,H,W] / [B,H,W,3] batch on the device")
         return (u8.shape[0],) + ((u8.shape[2], u8.shape[3]) if self.layout == "nchw" else (u8.shape[1], u8.shape[2]))
 
-    def _launch(self, u8, size, host):
+    def _launch(self, u8, size, host, antialias):
         dev = self._dev[self._slot]
         if dev is None:
             dev = self._dev[self._slot] = torch.empty(host.numel(), dtype=torch.int32, device=u8.device)
@@ -356,7 +391,7 @@ class DeviceRandomResizedCrop:
         if ev is None:
             ev = self._events[self._slot] = torch.cuda.Event()
         ev.record()
-        return ops.crop_resize_u8(u8.contiguous(), size, dev, layout=self.layout, host_records=host)
+        return (ops.crop_resample_u8 if antialias else ops.crop_resize_u8)(u8.contiguous(), size, dev, layout=self.layout, host_records=host)
 
     def _size(self, size):
         size = self.size if size is None else size
@@ -369,11 +404,15 @@ class DeviceRandomResizedCrop:
         integer [B,2] (eh, ew) for images that fill only the top-left part of a padded canvas (default: the whole canvas)"""
         size = self._size(size)
         B, H, W = self._canvas(u8)
-        return self._launch(u8, size, self.draw(B, H, W, extents))
+        return self._launch(u8, size, self.draw(B, H, W, extents), self.interpolation is not None)
 
-    def center(self, u8, size, crop_pct=0.875, extents=None):
+    def center(self, u8, size, crop_pct=0.875, extents=None, interpolation=None):
         """the same launch on the central square box of side int(round(crop_pct * min(eh, ew))), no flip, no draw: on a fixed canvas the
-        validation-time resize and centre crop"""
+        validation-time resize and centre crop.  interpolation as center_records'.  With "bicubic" and crop_pct = 0.96 this stands where
+        the reference's validation transform does (Pillow bicubic), in the other order: the reference resizes the shorter side to
+        floor(size / crop_pct) and then cuts the central size x size; this cuts the central square of side round(crop_pct * min(eh, ew))
+        and resizes it to size x size"""
         size = self._size(size)
         B, H, W = self._canvas(u8)
-        return self._launch(u8, size, self.center_records(B, H, W, crop_pct, extents))
+        host = self.center_records(B, H, W, crop_pct, extents, interpolation)
+        return self._launch(u8, size, host, (self.interpolation if interpolation is None else interpolation) is not None)

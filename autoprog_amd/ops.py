@@ -12,7 +12,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib
-from ._lib import CropResizeArgs, GemmEpilogue, InputPrepArgs, LnReduce, TnProblem, LN_MAX_BATCH, PREP_MAX_BOXES, TN_MAX_GROUP, TN_MAX_GROUP_DET, AutoProgHipError, check, lib
+from ._lib import CropResampleArgs, CropResizeArgs, GemmEpilogue, InputPrepArgs, LnReduce, TnProblem, LN_MAX_BATCH, PREP_MAX_BOXES, TN_MAX_GROUP, TN_MAX_GROUP_DET, AutoProgHipError, check, lib
 
 BF16 = torch.bfloat16
 
@@ -1152,35 +1152,50 @@ def input_prep(u8, size, out="s2d16", table=None, params=None, layout="nchw", mi
 CROP_RECORD_WORDS = 8                             # a record of ap_crop_resize_u8: top, left, h, w, flip, three zero words
 
 
+def _crop_launch(what, args_type, entry, u8, size, records, layout, out, host_records):
+    _req(u8, torch.uint8, "u8"); _req(records, torch.int32, "records")
+    if layout not in ("nchw", "nhwc") or u8.dim() != 4 or u8.shape[1 if layout == "nchw" else 3] != 3:
+        raise AutoProgHipError("%s: a uint8 [B,3,H,W] (nchw) or [B,H,W,3] (nhwc) batch, got %s as %s" % (what, tuple(u8.shape), layout))
+    B, size = u8.shape[0], int(size)
+    Hi, Wi = (u8.shape[2], u8.shape[3]) if layout == "nchw" else (u8.shape[1], u8.shape[2])
+    if size < 1:
+        raise AutoProgHipError("%s: size %d" % (what, size))
+    words = B * CROP_RECORD_WORDS
+    if records.numel() < words or (host_records is not None and (host_records.is_cuda or host_records.dtype != torch.int32
+                                                                 or not host_records.is_contiguous() or host_records.numel() < words)):
+        raise AutoProgHipError("%s: %d images need %d int32 words of records (and the same in a CPU int32 host copy)" % (what, B, words))
+    shape = (B, 3, size, size) if layout == "nchw" else (B, size, size, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=u8.device)
+    elif tuple(_req(out, torch.uint8, "out").shape) != shape:
+        raise AutoProgHipError("%s: out must be %s, got %s" % (what, shape, tuple(out.shape)))
+    a = args_type()
+    a.u8, a.layout, a.B, a.Hi, a.Wi = u8.data_ptr(), int(layout == "nhwc"), B, Hi, Wi
+    a.out, a.S, a.records = out.data_ptr(), size, records.data_ptr()
+    if host_records is not None:
+        a.records_host = host_records.data_ptr()
+    check(entry(ctypes.byref(a), _stream()), "ap_" + what)
+    return out
+
+
 def crop_resize_u8(u8, size, records, layout="nchw", out=None, host_records=None):
     """uint8 [B,3,Hi,Wi] (layout "nchw") or [B,Hi,Wi,3] ("nhwc") -> uint8 [B,3,size,size] / [B,size,size,3]: image b's box
     (records[b] = top, left, h, w, flip, 0, 0, 0; int32, on the device) resized bilinearly to size x size, flipped along the width where
     flip is 1, in one launch (include/autoprog_hip.h, ap_crop_resize_u8; no antialiasing).  `out`: a uint8 device tensor of the result's
     shape to write into (contiguous, any alignment); `host_records`: a CPU copy of `records` whose boxes are checked against the image
     before the launch."""
-    _req(u8, torch.uint8, "u8"); _req(records, torch.int32, "records")
-    if layout not in ("nchw", "nhwc") or u8.dim() != 4 or u8.shape[1 if layout == "nchw" else 3] != 3:
-        raise AutoProgHipError("crop_resize_u8: a uint8 [B,3,H,W] (nchw) or [B,H,W,3] (nhwc) batch, got %s as %s" % (tuple(u8.shape), layout))
-    B, size = u8.shape[0], int(size)
-    Hi, Wi = (u8.shape[2], u8.shape[3]) if layout == "nchw" else (u8.shape[1], u8.shape[2])
-    if size < 1:
-        raise AutoProgHipError("crop_resize_u8: size %d" % size)
-    words = B * CROP_RECORD_WORDS
-    if records.numel() < words or (host_records is not None and (host_records.is_cuda or host_records.dtype != torch.int32
-                                                                 or not host_records.is_contiguous() or host_records.numel() < words)):
-        raise AutoProgHipError("crop_resize_u8: %d images need %d int32 words of records (and the same in a CPU int32 host copy)" % (B, words))
-    shape = (B, 3, size, size) if layout == "nchw" else (B, size, size, 3)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=u8.device)
-    elif tuple(_req(out, torch.uint8, "out").shape) != shape:
-        raise AutoProgHipError("crop_resize_u8: out must be %s, got %s" % (shape, tuple(out.shape)))
-    a = CropResizeArgs()
-    a.u8, a.layout, a.B, a.Hi, a.Wi = u8.data_ptr(), int(layout == "nhwc"), B, Hi, Wi
-    a.out, a.S, a.records = out.data_ptr(), size, records.data_ptr()
-    if host_records is not None:
-        a.records_host = host_records.data_ptr()
-    check(lib.ap_crop_resize_u8(ctypes.byref(a), _stream()), "ap_crop_resize_u8")
-    return out
+    return _crop_launch("crop_resize_u8", CropResizeArgs, lib.ap_crop_resize_u8, u8, size, records, layout, out, host_records)
+
+
+RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 1, 2        # word 5 of a record of ap_crop_resample_u8 (AP_RESAMPLE_*)
+
+
+def crop_resample_u8(u8, size, records, layout="nchw", out=None, host_records=None):
+    """crop_resize_u8 with Pillow's antialiased filters: image b's box (records[b] = top, left, h, w, flip, filter, 0, 0; filter
+    RESAMPLE_BILINEAR or RESAMPLE_BICUBIC, per image) comes out as Pillow's Image.crop(box).resize((size, size), filter) gives it, byte for
+    byte, mirrored along the width afterwards where flip is 1, in one launch (include/autoprog_hip.h, ap_crop_resample_u8).  Arguments
+    as crop_resize_u8's."""
+    return _crop_launch("crop_resample_u8", CropResampleArgs, lib.ap_crop_resample_u8, u8, size, records, layout, out, host_records)
 
 
 # ------------------------------------------------------------------------------------- stem 7x7 / stride 2 convolution (3 -> 64)

@@ -680,6 +680,44 @@ typedef struct ap_crop_resize_args {
 } ap_crop_resize_args;
 int ap_crop_resize_u8(const ap_crop_resize_args* args, ap_stream_t stream);
 
+/* ---- the same launch with Pillow's ANTIALIASED bilinear / bicubic filters, byte for byte (additive in ABI version 7; csrc/resample.hip).
+ * The resample of the reference's loader: timm's RandomResizedCropAndInterpolation is Pillow's Image.resize, `--train-interpolation random`
+ * picks bilinear or bicubic per image (main_prog.py:211, :632-658), validation is bicubic (models/volo.py:35-44).  Arguments as
+ * ap_crop_resize_u8's.  records (DEVICE): B records of 8 int32 words: top, left, h, w, flip, filter, then two zero words; filter is
+ * AP_RESAMPLE_BILINEAR or AP_RESAMPLE_BICUBIC and may differ from image to image.  Image b's output is what Pillow's
+ * Image.crop(box).resize((S, S), filter) gives in mode RGB: two separable passes, the horizontal one first and ROUNDED TO UINT8, the
+ * vertical one on its result.  For one axis of box extent n (w or h), in float64 with every operation rounded on its own:
+ *     scale = n / S;  fs = max(scale, 1.0);  support = sup0 * fs;  ss = 1.0 / fs                  sup0: 1.0 bilinear, 2.0 bicubic
+ *     for o in 0 .. S-1:
+ *         center = (o + 0.5) * scale
+ *         xmin = max((int)(center - support + 0.5), 0);  xmax = min((int)(center + support + 0.5), n)             C truncation
+ *         k[i] = filt((i + xmin - center + 0.5) * ss)  for i in 0 .. xmax - xmin - 1
+ *         ww = k[0] + k[1] + ... in this order;  if ww != 0: k[i] = k[i] / ww
+ *         K[i] = (int)(k[i] * 4194304.0 + (k[i] < 0 ? -0.5 : 0.5))                                2^22, C truncation
+ *         out[o] = clip((2097152 + sum_i src[xmin + i] * K[i]) >> 22, 0, 255)                     int32, arithmetic shift
+ *     bilinear: x = |x|;  x < 1 ? 1 - x : 0
+ *     bicubic (a = -0.5): x = |x|;  x < 1 ? ((a + 2) x - (a + 3)) x x + 1 : x < 2 ? (((x - 5) x + 8) x - 4) a : 0
+ * The support is clipped to the BOX, not the image: the image is cropped first, as timm's F.resized_crop does.  The flip acts on the
+ * result: output column ox of a flipped image is column S - 1 - ox of the resampled box (timm resizes, then flips; resampling a mirrored
+ * box gives other bytes).  Rows are never flipped.  A box with h = w = S comes back as the slice under both filters.
+ * records_host (nullable): as ap_crop_resize_u8's, and the filter must be 1 or 2 (AP_ERR_SHAPE).  The kernel clamps every record into the
+ * image and any other filter code to AP_RESAMPLE_BILINEAR, so a record it was not shown on the host cannot make it read or write out of
+ * bounds; it reads nothing past the last byte of the batch.
+ * AP_ERR_NULL, AP_ERR_SHAPE: as ap_crop_resize_u8.  AP_ERR_UNSUPPORTED: a workgroup keeps in LDS, for tr >= 1 output rows of the whole
+ * image under bicubic, the box rows they read (ceil((tr - 1) Hi / S + 4 max(Hi / S, 1)) + 2, at most Hi, of Wi pixels plus 30 bytes per
+ * plane), the same number of intermediate rows of 3 S bytes and both coefficient tables (S windows of ceil(2 max(Wi / S, 1)) * 2 + 1
+ * int32, tr of ceil(2 max(Hi / S, 1)) * 2 + 1); when that exceeds 80 KB at tr = 1, or the runtime refuses more than 64 KB to a launch.
+ * The budget depends on Hi, Wi, S and the layout alone, never on the records.  B == 0 succeeds without a launch.  Every check comes
+ * before the launch. */
+enum { AP_RESAMPLE_BILINEAR = 1, AP_RESAMPLE_BICUBIC = 2 };      /* word 5 of a record */
+typedef struct ap_crop_resample_args {
+    const unsigned char* u8; int layout; int B, Hi, Wi;
+    unsigned char* out; int S;
+    const int* records;              /* DEVICE [B][8] */
+    const int* records_host;         /* nullable host copy, validated */
+} ap_crop_resample_args;
+int ap_crop_resample_u8(const ap_crop_resample_args* args, ap_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
