@@ -70,6 +70,12 @@ class CropResampleArgs(Structure):
     _fields_ = CropResizeArgs._fields_
 
 
+class RandAugArgs(Structure):
+    """ap_randaug_args (include/autoprog_hip.h)"""
+    _fields_ = [("u8", c_void_p), ("layout", c_int), ("B", c_int), ("S", c_int), ("out", c_void_p), ("scratch", c_void_p),
+                ("records", c_void_p), ("records_host", c_void_p), ("n_layers", c_int), ("fill", ctypes.c_ubyte * 3)]
+
+
 class PatchMap(Structure):
     """ap_patch_map (include/autoprog_hip.h)"""
     _fields_ = [("group", c_int), ("group_stride", c_int), ("row_stride", c_int), ("kseg", c_int), ("kseg_stride", c_int)]
@@ -192,6 +198,8 @@ _SIGNATURES["ap_soft_ce_sparse_gt_fwd_bwd"] = (_I, [_P, _I, _P, _P, _I, _L, _L, 
 _SIGNATURES["ap_crop_resize_u8"] = (_I, [POINTER(CropResizeArgs), _P])
 # the same with Pillow's antialiased bilinear / bicubic filters, byte for byte (csrc/resample.hip)
 _SIGNATURES["ap_crop_resample_u8"] = (_I, [POINTER(CropResampleArgs), _P])
+# RandAugment's ops on a uint8 batch, one launch per layer, byte for byte Pillow's (csrc/randaug.hip)
+_SIGNATURES["ap_randaug_u8"] = (_I, [POINTER(RandAugArgs), _P])
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 EXPECTED_ABI = 7                     # ap_abi_version() of the library these ctypes Structures mirror (include/autoprog_hip.h)

@@ -21,9 +21,14 @@ SparseTokenLabelTarget only normalise / erase / resize apply, and asking for Mix
 In front of it, DeviceRandomResizedCrop does the loader's random-resized crop and horizontal flip on the device as well: one box and one
 flip per image drawn on the host, one launch of `ops.crop_resize_u8` (csrc/crop.hip) from the loader's fixed-size uint8 canvases to the
 uint8 batch at the stage's resolution that `prep` takes -- the per-stage crop scale of AutoProg's schedule is then an attribute, where
-the reference rebuilds its loader (main_prog.py:651-653, 840-846)."""
+the reference rebuilds its loader (main_prog.py:651-653, 840-846).
+
+Between the two, where timm's transform chain has it, DeviceRandAugment applies the auto-augment step (`--aa rand-m9-mstd0.5-inc1`) to
+that uint8 batch: the ops and their arguments drawn on the host in timm's order, one launch of `ops.randaug_u8` (csrc/randaug.hip) per
+layer, every op Pillow's bytes -- the per-stage magnitude of AutoProg's schedule is an attribute as well."""
 import math
 import random
+import re
 
 import numpy as np
 import torch
@@ -416,3 +421,225 @@ class DeviceRandomResizedCrop:
         B, H, W = self._canvas(u8)
         host = self.center_records(B, H, W, crop_pct, extents, interpolation)
         return self._launch(u8, size, host, (self.interpolation if interpolation is None else interpolation) is not None)
+
+
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+RANDAUG_OPS = ("AutoContrast", "Equalize", "Invert", "Rotate", "Posterize", "Solarize", "SolarizeAdd", "Color", "Contrast", "Brightness",
+               "Sharpness", "ShearX", "ShearY", "TranslateXRel", "TranslateYRel")      # timm's _RAND_TRANSFORMS, in its order
+_RA_MAX_LEVEL = 10.0
+_RA_ENHANCE = {"Color": ops.RA_COLOR, "Contrast": ops.RA_CONTRAST, "Brightness": ops.RA_BRIGHTNESS, "Sharpness": ops.RA_SHARPNESS}
+_RA_NO_MATRIX = (0.0,) * 6
+RANDAUG_NONE = (ops.RA_NONE, 0, 0, 0.0, _RA_NO_MATRIX)                                 # the record of a skipped op
+
+
+def parse_randaug_spec(spec):
+    """'rand-m9-mstd0.5-inc1' -> dict(magnitude, n, mstd, inc); '' or None -> None (no auto-augment).  timm 0.4.5's
+    rand_augment_transform: sections split at '-', the first is 'rand', each other one a key and a number: m (magnitude, int; 10 where it
+    is missing), n (layers, default 2), mstd (float), inc (0 / 1: here inc0 selects the non-increasing level rules, where timm's
+    `bool('0')` selects the increasing ones).  w (op weights) and any other key are refused with ValueError"""
+    if spec is None or spec == "":
+        return None
+    parts = str(spec).split("-")
+    if parts[0] != "rand":
+        raise ValueError("DeviceRandAugment: a 'rand-...' spec, got %r (AutoAugment and AugMix policies are not implemented)" % (spec,))
+    cfg = dict(magnitude=int(_RA_MAX_LEVEL), n=2, mstd=0.0, inc=False)
+    for sec in parts[1:]:
+        cs = re.split(r"(\d.*)", sec)
+        if len(cs) < 2:
+            raise ValueError("DeviceRandAugment: section %r of %r has no number" % (sec, spec))
+        key, val = cs[:2]
+        if key == "m":
+            cfg["magnitude"] = int(val)
+        elif key == "n":
+            cfg["n"] = int(val)
+        elif key == "mstd":
+            cfg["mstd"] = float(val)
+        elif key == "inc":
+            cfg["inc"] = bool(int(val))
+        elif key == "w":
+            raise ValueError("DeviceRandAugment: op weights (%r) are not implemented: the ops are drawn uniformly" % (sec,))
+        else:
+            raise ValueError("DeviceRandAugment: unknown section %r of %r" % (sec, spec))
+    if not 1 <= cfg["n"] <= ops.RANDAUG_MAX_LAYERS:
+        raise ValueError("DeviceRandAugment: n must be 1..%d" % ops.RANDAUG_MAX_LAYERS)
+    return cfg
+
+
+class DeviceRandAugment:
+    """timm 0.4.5's rand_augment_transform + RandAugment + AugmentOp as host-side draws and one device launch per layer
+    (ops.randaug_u8, csrc/randaug.hip: every op byte for byte what Pillow makes of it).  In timm's transform chain the step sits between
+    RandomResizedCropAndInterpolation + RandomHorizontalFlip and the normalisation: `aug(u8)` takes the uint8 [B,3,S,S] / [B,S,S,3] batch
+    DeviceRandomResizedCrop.crop returns and gives a uint8 batch of the same shape, which DeviceBatchPrep.prep takes.  The input is not
+    modified; the result lives in a buffer kept per shape and is overwritten by the next call at that shape.
+
+    The decisions come from this object's own numpy.random.RandomState(seed) -- timm draws the ops with numpy -- and random.Random(seed)
+    -- and everything else with `random` -- never from the global streams, and are written into the next slot of a ring of pinned record
+    blocks that reaches the device in one small copy.  Per image, first the ops: RandomState.choice(15, n), uniform with replacement,
+    over RANDAUG_OPS.  Then per op, in this order:
+      1. prob < 1 and random() > prob: the op is skipped (a "none" record) and draws nothing more
+      2. mag = gauss(magnitude, magnitude_std) if magnitude_std > 0 else magnitude, clipped to [0, 10]
+      3. the level, with L = mag / 10 and neg(v) = -v if random() > 0.5 else v:
+           Rotate neg(30 L) degrees; ShearX / ShearY neg(0.3 L); TranslateXRel / TranslateYRel neg(0.45 L) * S pixels;
+           Color / Contrast / Brightness / Sharpness the factor 1.0 + neg(0.9 L) (inc0: 1.8 L + 0.1, no draw);
+           Posterize 4 - int(4 L) bits (inc0: int(4 L)); Solarize the threshold 256 - int(256 L) (inc0: int(256 L));
+           SolarizeAdd int(110 L); AutoContrast, Equalize and Invert draw nothing
+      4. the five geometric ops: choice((bilinear, bicubic)), timm's _RANDOM_INTERPOLATION
+    The affine matrices are built here in Python floats, as Pillow's Python layer does: ShearX (1, s, 0, 0, 1, 0), ShearY (1, 0, 0, s, 1, 0),
+    TranslateX (1, 0, p, 0, 1, 0), TranslateY (1, 0, 0, 0, 1, p), Rotate Image.rotate's (a = -radians(deg % 360), entries rounded to 15
+    digits, centred on (S / 2, S / 2); deg % 360 == 0 is a copy).  Enhance factors are stored as float32, as Pillow's C layer takes them.
+    The fill colour of the geometric ops is timm's img_mean: tuple(min(255, round(255 x)) for x in mean).
+
+    magnitude, magnitude_std and prob are plain attributes read at draw time (AutoProgDriver sets the magnitude per stage from the
+    schedule's `aa` list through set_spec, where the reference rebuilds its loader and its worker processes); `last` holds the records of
+    the last draw: per image a list of n_layers tuples (op, filter, int argument, factor, matrix) with op one of ops.RA_*.
+    A spec of "" or None disables the object: `aug(u8)` then returns its input and draws nothing.
+    Not implemented: op weights (w), mstd = inf (uniform magnitudes), the constant-pixel translate ops, AutoAugment and AugMix policies."""
+    SLOTS = 8
+
+    def __init__(self, spec="rand-m9-mstd0.5-inc1", mean=IMAGENET_MEAN, seed=0, layout="nchw", device="cuda"):
+        if layout not in ("nchw", "nhwc"):
+            raise ValueError("layout must be nchw or nhwc")
+        self.prob = 0.5
+        self.magnitude, self.magnitude_std, self.n_layers, self.increasing = int(_RA_MAX_LEVEL), 0.0, 2, False
+        self.set_spec(spec)
+        self.fill = tuple(min(255, round(255 * x)) for x in mean)
+        self.seed, self.layout, self.device = int(seed), layout, torch.device(device)
+        self._np = np.random.RandomState(self.seed & 0xffffffff)
+        self._py = random.Random(self.seed)
+        self._key = None
+        self._buffers = {}
+        self.last = None
+
+    def set_spec(self, spec):
+        """takes magnitude, magnitude_std, n_layers and the level rules from a spec; "" / None disables the object and keeps them"""
+        cfg = parse_randaug_spec(spec)
+        self.spec, self.enabled = spec, cfg is not None
+        if cfg is not None:
+            self.magnitude, self.magnitude_std, self.n_layers, self.increasing = cfg["magnitude"], cfg["mstd"], cfg["n"], cfg["inc"]
+
+    # ---- the draw
+    def _neg(self, v):
+        return -v if self._py.random() > 0.5 else v
+
+    @staticmethod
+    def rotate_matrix(deg, S):
+        """Image.rotate's matrix for an S x S image about its centre; None where Pillow returns a copy"""
+        deg = deg % 360.0
+        if deg == 0:
+            return None
+        a = -math.radians(deg)
+        m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+        c = S / 2.0
+        m[2] = m[0] * -c + m[1] * -c + m[2] + c
+        m[5] = m[3] * -c + m[4] * -c + m[5] + c
+        return tuple(m)
+
+    def _draw_op(self, name, S):
+        py = self._py
+        if self.prob < 1.0 and py.random() > self.prob:
+            return RANDAUG_NONE
+        mag = self.magnitude
+        if self.magnitude_std > 0:
+            mag = py.gauss(mag, self.magnitude_std)
+        L = min(_RA_MAX_LEVEL, max(0, mag)) / _RA_MAX_LEVEL
+        if name == "AutoContrast":
+            return (ops.RA_AUTOCONTRAST, 0, 0, 0.0, _RA_NO_MATRIX)
+        if name == "Equalize":
+            return (ops.RA_EQUALIZE, 0, 0, 0.0, _RA_NO_MATRIX)
+        if name == "Invert":
+            return (ops.RA_INVERT, 0, 0, 0.0, _RA_NO_MATRIX)
+        if name in _RA_ENHANCE:
+            f = 1.0 + self._neg(L * 0.9) if self.increasing else L * 1.8 + 0.1
+            return (_RA_ENHANCE[name], 0, 0, float(np.float32(f)), _RA_NO_MATRIX)
+        if name == "Posterize":
+            bits = 4 - int(L * 4) if self.increasing else int(L * 4)
+            return (ops.RA_POSTERIZE, 0, bits, 0.0, _RA_NO_MATRIX) if bits < 8 else RANDAUG_NONE
+        if name == "Solarize":
+            return (ops.RA_SOLARIZE, 0, 256 - int(L * 256) if self.increasing else int(L * 256), 0.0, _RA_NO_MATRIX)
+        if name == "SolarizeAdd":
+            return (ops.RA_SOLARIZE_ADD, 0, int(L * 110), 0.0, _RA_NO_MATRIX)
+        if name == "Rotate":
+            m = self.rotate_matrix(self._neg(L * 30.0), S)
+        elif name in ("ShearX", "ShearY"):
+            s = self._neg(L * 0.3)
+            m = (1.0, s, 0.0, 0.0, 1.0, 0.0) if name == "ShearX" else (1.0, 0.0, 0.0, s, 1.0, 0.0)
+        elif name in ("TranslateXRel", "TranslateYRel"):
+            p = self._neg(L * 0.45) * S
+            m = (1.0, 0.0, p, 0.0, 1.0, 0.0) if name == "TranslateXRel" else (1.0, 0.0, 0.0, 0.0, 1.0, p)
+        else:
+            raise ValueError("unknown op %r" % (name,))
+        filt = py.choice((ops.RESAMPLE_BILINEAR, ops.RESAMPLE_BICUBIC))      # drawn before Pillow decides that a rotation is a copy
+        return (ops.RA_AFFINE, filt, 0, 0.0, tuple(float(v) for v in m)) if m is not None else RANDAUG_NONE
+
+    @staticmethod
+    def pack(records, block):
+        """per-image lists of record tuples -> the int32 words of `block` (a numpy int32 array of B * n * 16 words at least)"""
+        flat = [r for image in records for r in image]
+        a = block[:len(flat) * ops.RANDAUG_RECORD_WORDS].reshape(len(flat), ops.RANDAUG_RECORD_WORDS)
+        a[:] = 0
+        if flat:
+            a[:, 0:3] = [r[:3] for r in flat]
+            a[:, 3:4].view(np.float32)[:, 0] = [r[3] for r in flat]
+            a[:, 4:16].view(np.float64)[:] = [r[4] for r in flat]
+
+    @staticmethod
+    def unpack(block, B, n_layers):
+        """the inverse of pack: -> per-image lists of n_layers record tuples"""
+        a = np.ascontiguousarray(np.asarray(block).reshape(-1)[:B * n_layers * ops.RANDAUG_RECORD_WORDS]).reshape(B * n_layers, ops.RANDAUG_RECORD_WORDS)
+        f, m = a[:, 3:4].view(np.float32)[:, 0], a[:, 4:16].view(np.float64)
+        flat = [(int(a[i, 0]), int(a[i, 1]), int(a[i, 2]), float(f[i]), tuple(float(v) for v in m[i])) for i in range(B * n_layers)]
+        return [flat[b * n_layers:(b + 1) * n_layers] for b in range(B)]
+
+    def _alloc(self, B, n):
+        ring = torch.zeros(self.SLOTS, max(B * n, 1) * ops.RANDAUG_RECORD_WORDS, dtype=torch.int32)
+        self._ring = ring.pin_memory() if self.device.type == "cuda" and torch.cuda.is_available() else ring
+        self._dev = [None] * self.SLOTS
+        self._events = [None] * self.SLOTS
+        self._slot, self._key = 0, (B, n)
+
+    def draw(self, B, S):
+        """-> the host block (int32 CPU tensor, B x n_layers records of 16 words) of the next call on B images of S x S pixels"""
+        n = int(self.n_layers)
+        if not 1 <= n <= ops.RANDAUG_MAX_LAYERS:
+            raise ValueError("DeviceRandAugment: n_layers must be 1..%d" % ops.RANDAUG_MAX_LAYERS)
+        if self._key != (B, n):
+            self._alloc(B, n)
+        self._slot = (self._slot + 1) % self.SLOTS
+        ev = self._events[self._slot]
+        if ev is not None:
+            ev.synchronize()                   # the copy that last read this slot has executed
+        # one call for the batch: RandomState.choice(15, B n) is the stream of B calls of choice(15, n) (32 bits and one rejection test
+        # per element either way), without a numpy call per image on the host's critical path
+        picks = self._np.choice(len(RANDAUG_OPS), B * n).reshape(B, n).tolist() if B else []
+        draw_op = self._draw_op
+        self.last = [[draw_op(RANDAUG_OPS[k], S) for k in image] for image in picks]
+        host = self._ring[self._slot]
+        self.pack(self.last, host.numpy())
+        return host
+
+    def __call__(self, u8):
+        """uint8 device batch -> the augmented uint8 batch: draws n_layers ops per image, one copy and n_layers launches"""
+        if not self.enabled:
+            return u8
+        if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 4 or not u8.is_cuda:
+            raise ValueError("DeviceRandAugment: a uint8 [B,3,S,S] / [B,S,S,3] batch on the device")
+        B, S, W = (u8.shape[0], u8.shape[2], u8.shape[3]) if self.layout == "nchw" else (u8.shape[0], u8.shape[1], u8.shape[2])
+        if S != W:
+            raise ValueError("DeviceRandAugment: square images (the crop's output), got %s" % (tuple(u8.shape),))
+        key = (tuple(u8.shape), u8.device)
+        if key not in self._buffers:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("DeviceRandAugment: the buffers for %s do not exist yet: call the object once outside the capture" % (key[0],))
+            self._buffers[key] = (torch.empty_like(u8, memory_format=torch.contiguous_format),
+                                  torch.empty_like(u8, memory_format=torch.contiguous_format))
+        out, scratch = self._buffers[key]
+        host = self.draw(B, S)
+        dev = self._dev[self._slot]
+        if dev is None:
+            dev = self._dev[self._slot] = torch.empty(host.numel(), dtype=torch.int32, device=u8.device)
+        dev.copy_(host, non_blocking=True)
+        ev = self._events[self._slot]
+        if ev is None:
+            ev = self._events[self._slot] = torch.cuda.Event()
+        ev.record()
+        return ops.randaug_u8(u8.contiguous(), dev, self.n_layers, self.fill, layout=self.layout, out=out, scratch=scratch, host_records=host)

@@ -12,7 +12,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib
-from ._lib import CropResampleArgs, CropResizeArgs, GemmEpilogue, InputPrepArgs, LnReduce, TnProblem, LN_MAX_BATCH, PREP_MAX_BOXES, TN_MAX_GROUP, TN_MAX_GROUP_DET, AutoProgHipError, check, lib
+from ._lib import CropResampleArgs, CropResizeArgs, GemmEpilogue, InputPrepArgs, LnReduce, RandAugArgs, TnProblem, LN_MAX_BATCH, PREP_MAX_BOXES, TN_MAX_GROUP, TN_MAX_GROUP_DET, AutoProgHipError, check, lib
 
 BF16 = torch.bfloat16
 
@@ -1196,6 +1196,51 @@ def crop_resample_u8(u8, size, records, layout="nchw", out=None, host_records=No
     byte, mirrored along the width afterwards where flip is 1, in one launch (include/autoprog_hip.h, ap_crop_resample_u8).  Arguments
     as crop_resize_u8's."""
     return _crop_launch("crop_resample_u8", CropResampleArgs, lib.ap_crop_resample_u8, u8, size, records, layout, out, host_records)
+
+
+# ------------------------------------------------------------------------------------- RandAugment's ops on a uint8 batch
+RANDAUG_RECORD_WORDS, RANDAUG_MAX_LAYERS = 16, 8  # AP_RANDAUG_RECORD_WORDS / AP_RANDAUG_MAX_LAYERS
+(RA_NONE, RA_AUTOCONTRAST, RA_EQUALIZE, RA_INVERT, RA_SOLARIZE, RA_SOLARIZE_ADD, RA_POSTERIZE, RA_BRIGHTNESS, RA_CONTRAST, RA_COLOR,
+ RA_SHARPNESS, RA_AFFINE) = range(12)             # word 0 of a record of ap_randaug_u8 (AP_RA_*)
+
+
+def randaug_u8(u8, records, n_layers, fill, layout="nchw", out=None, scratch=None, host_records=None):
+    """uint8 [B,3,S,S] (layout "nchw") or [B,S,S,3] ("nhwc") -> a new uint8 batch of the same shape: image b goes through its n_layers
+    records (int32, on the device, [B, n_layers, RANDAUG_RECORD_WORDS]: op code RA_*, filter RESAMPLE_*, an int argument, a float32
+    argument, six float64 affine coefficients) in order, each op byte for byte what Pillow makes of it, one launch per layer
+    (include/autoprog_hip.h, ap_randaug_u8).  `fill`: the (R, G, B) bytes of pixels an affine op maps from outside the image.  The input is
+    not modified.  `out` / `scratch`: uint8 device tensors of the input's shape to write into (scratch is only used with n_layers > 1;
+    allocated when not given); `host_records`: a CPU copy of `records` whose op and filter codes are checked before the launch."""
+    _req(u8, torch.uint8, "u8"); _req(records, torch.int32, "records")
+    if layout not in ("nchw", "nhwc") or u8.dim() != 4 or u8.shape[1 if layout == "nchw" else 3] != 3 or u8.shape[2] != u8.shape[3 if layout == "nchw" else 1]:
+        raise AutoProgHipError("randaug_u8: a square uint8 [B,3,S,S] (nchw) or [B,S,S,3] (nhwc) batch, got %s as %s" % (tuple(u8.shape), layout))
+    B, S, n_layers = u8.shape[0], u8.shape[2], int(n_layers)
+    fill = tuple(int(v) for v in fill)
+    if not 1 <= n_layers <= RANDAUG_MAX_LAYERS or len(fill) != 3 or min(fill) < 0 or max(fill) > 255:
+        raise AutoProgHipError("randaug_u8: n_layers 1..%d and three fill bytes, got %d and %s" % (RANDAUG_MAX_LAYERS, n_layers, fill))
+    words = B * n_layers * RANDAUG_RECORD_WORDS
+    if records.numel() < words or (host_records is not None and (host_records.is_cuda or host_records.dtype != torch.int32
+                                                                 or not host_records.is_contiguous() or host_records.numel() < words)):
+        raise AutoProgHipError("randaug_u8: %d images x %d layers need %d int32 words of records (and the same in a CPU int32 host copy)"
+                               % (B, n_layers, words))
+    if out is None:
+        out = torch.empty_like(u8)
+    elif tuple(_req(out, torch.uint8, "out").shape) != tuple(u8.shape):
+        raise AutoProgHipError("randaug_u8: out must be %s, got %s" % (tuple(u8.shape), tuple(out.shape)))
+    a = RandAugArgs()
+    if n_layers > 1:
+        if scratch is None:
+            scratch = torch.empty_like(u8)
+        elif tuple(_req(scratch, torch.uint8, "scratch").shape) != tuple(u8.shape):
+            raise AutoProgHipError("randaug_u8: scratch must be %s, got %s" % (tuple(u8.shape), tuple(scratch.shape)))
+        a.scratch = scratch.data_ptr()
+    a.u8, a.layout, a.B, a.S = u8.data_ptr(), int(layout == "nhwc"), B, S
+    a.out, a.records, a.n_layers = out.data_ptr(), records.data_ptr(), n_layers
+    a.fill[0], a.fill[1], a.fill[2] = fill
+    if host_records is not None:
+        a.records_host = host_records.data_ptr()
+    check(lib.ap_randaug_u8(ctypes.byref(a), _stream()), "ap_randaug_u8")
+    return out
 
 
 # ------------------------------------------------------------------------------------- stem 7x7 / stride 2 convolution (3 -> 64)

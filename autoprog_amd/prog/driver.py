@@ -10,9 +10,10 @@ driver keeps ONE network sized for the deepest stage with its flat parameter / m
 between stages with `FlatAdamWEma.grow` (prog/elastic.py) and `set_sample_config` -- a candidate of a search is a mask and a
 resolution, nothing is copied to evaluate it.  The per-step input resize runs on the device (ap_resize_bilinear_nhwc).
 
-Out of scope: data loading, augmentation strength schedules (only DropPath lives in the model), LR scheduler,
-checkpoint files -- the caller supplies `get_batch(r) -> (images, target)` and reads `history`.  Validation (prog/validate.py) runs after
-every training epoch when the caller also supplies `get_val_batches`.
+Out of scope: data loading and decoding, LR scheduler, checkpoint files (the augmentation strength schedules are
+attributes set per stage: DropPath in the model, re_list / resize_list / aa_list on the data objects) -- the caller supplies
+`get_batch(r) -> (images, target)` and reads `history`.  Validation (prog/validate.py) runs after every training epoch when the caller
+also supplies `get_val_batches`.
 """
 import random
 import time
@@ -32,7 +33,8 @@ class AutoProgDriver:
     def __init__(self, model, loss_fn, optimizer, reducer, get_batch, r_list, l_list, dp_list, grow_epochs, steps_per_epoch,
                  search_epochs=2, auto_grow=True, probe_batches=4, time_steps=4, seed=0, log=None, original_batch_splits=1,
                  r_max=None, dist_bn="", use_graphs=False, graph_after=2, clip_grad=None, clip_mode="norm", get_val_batches=None,
-                 batch_prep=None, re_list=None, skip_nonfinite=False, teacher=None, crop=None, resize_list=None):
+                 batch_prep=None, re_list=None, skip_nonfinite=False, teacher=None, crop=None, resize_list=None, *, augment=None,
+                 aa_list=None):
         """model: supernet sized for l_list[-1] (e.g. volo_h12_l18); optimizer: FlatAdamWEma over it; reducer: its
         GradientBucketReducer; r_list / l_list / dp_list / grow_epochs: the stage schedule (prog/progressive.py:4-31);
         get_batch(r): a training batch (images at ANY size -- the stem resizes to r -- and a token-label target for r // 16).
@@ -85,7 +87,26 @@ class AutoProgDriver:
         student sees.  resize_list: the per-stage crop scale range (the eighth value of prog.progressive.progressive_schedule, which the
         reference realises by rebuilding its loader, main_prog.py:651-653, 840-846): crop.scale is set to tuple(resize_list[stage]) at
         every stage change, where re_prob is set; a search crops with the scale of the stage it starts from.  Both None (default):
-        nothing changes."""
+        nothing changes.
+        augment (keyword only): a data.DeviceRandAugment (needs a batch_prep, in the same layout).  A uint8 image tensor then goes
+        crop -> augment -> batch_prep.prep, timm's order: the auto-augment step works on the cropped, flipped uint8 image and hands a uint8
+        image to the normalisation.  Like the crop its launches stay outside captured graphs, and a teacher sees the pixels the student
+        sees.  aa_list (keyword only): the per-stage RandAugment spec (the fifth value of prog.progressive.progressive_schedule, e.g.
+        "rand-m4-mstd0.5-inc1"; the reference rebuilds its loader and worker processes for it, main_prog.py:651-656): augment.set_spec(
+        aa_list[stage]) at every stage change, where re_prob and crop.scale are set -- the magnitude becomes an attribute, and "" switches
+        the step off for the stage.  A search augments with the spec of the stage it starts from, as it erases and crops.  Both None
+        (default): nothing changes."""
+        if augment is not None and batch_prep is None:
+            raise ValueError("augment needs a batch_prep: the augmented uint8 batch is what DeviceBatchPrep.prep takes")
+        if augment is not None and getattr(augment, "layout", None) != getattr(batch_prep, "layout", None):
+            raise ValueError("augment and batch_prep must use the same layout")
+        if aa_list is not None:
+            if augment is None or len(aa_list) != len(r_list):
+                raise ValueError("aa_list needs an augment and one spec per stage")
+            from ..data import parse_randaug_spec
+            for spec in aa_list:
+                parse_randaug_spec(spec)                                   # (a bad spec is refused here, not at its stage)
+        self.augment, self.aa_list = augment, (list(aa_list) if aa_list is not None else None)
         if crop is not None and batch_prep is None:
             raise ValueError("crop needs a batch_prep: the cropped uint8 batch is what DeviceBatchPrep.prep takes")
         if crop is not None and getattr(crop, "layout", None) != getattr(batch_prep, "layout", None):
@@ -136,6 +157,8 @@ class AutoProgDriver:
         if torch.is_tensor(images) and images.dtype == torch.uint8:
             if self.crop is not None:                                      # a[0]: the resolution of the stage or of the search's candidate
                 images = self.crop.crop(images, a[0])
+            if self.augment is not None:
+                images = self.augment(images)
             images = self.batch_prep.prep(images)
             if self.teacher is None and torch.is_tensor(target) and target.dim() == 1 and not target.dtype.is_floating_point:
                 target = images.target(target)
@@ -364,6 +387,8 @@ class AutoProgDriver:
                     self.batch_prep.re_prob = float(self.re_list[stage])
                 if self.resize_list is not None:                           # ... and with its own crop scale range
                     self.crop.scale = tuple(self.resize_list[stage])
+                if self.aa_list is not None:                               # ... and with its own auto-augment magnitude
+                    self.augment.set_spec(self.aa_list[stage])
                 if self.auto_grow and stage < len(self.grow_epochs) - 1:
                     r, l = self.search(stage, epoch)
                     skip.update(range(epoch, epoch + self.search_epochs))      # the search consumed these epochs (main_prog.py:856-857)

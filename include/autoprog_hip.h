@@ -718,6 +718,69 @@ typedef struct ap_crop_resample_args {
 } ap_crop_resample_args;
 int ap_crop_resample_u8(const ap_crop_resample_args* args, ap_stream_t stream);
 
+/* ---- RandAugment on a uint8 batch, byte for byte what Pillow makes of an RGB image (additive in ABI version 7; csrc/randaug.hip).
+ * The auto-augment step of the reference's loader (timm's rand_augment_transform, `--aa rand-m9-mstd0.5-inc1`), which sits between the
+ * random-resized crop and the normalisation and whose magnitude AutoProg ramps per stage by rebuilding the loader (main_prog.py:651-656,
+ * 1443-1518).  u8: [B,3,S,S] (AP_PREP_NCHW) or [B,S,S,3] (AP_PREP_NHWC), any alignment, never written; out: the same shape and layout;
+ * scratch: the same size again, needed when n_layers > 1 (its contents afterwards are unspecified).  u8, out and scratch are distinct.
+ * records (DEVICE): B x n_layers records of AP_RANDAUG_RECORD_WORDS = 16 int32 words, image b's layer j at record b * n_layers + j.  The
+ * layers of an image are applied in order, one launch per layer.  A record:
+ *     word 0      op code, AP_RA_*
+ *     word 1      resample filter of AP_RA_AFFINE: AP_RESAMPLE_BILINEAR or AP_RESAMPLE_BICUBIC; 0 for the other ops
+ *     word 2      int argument: Solarize's threshold t (0..256), SolarizeAdd's a, Posterize's bits
+ *     word 3      float32 argument (its bit pattern): the factor f of Brightness / Contrast / Color / Sharpness
+ *     words 4-15  six float64 m0 .. m5, little endian (word 4 the low half of m0): the matrix of AP_RA_AFFINE
+ * fill: the colour (R, G, B) of pixels an affine op maps from outside the image.  "trunc" is C's conversion toward zero.
+ *   NONE          copy.
+ *   table ops     out = lut[c][in], one table of 256 entries per channel:
+ *     INVERT        255 - i
+ *     SOLARIZE      i < t ? i : 255 - i
+ *     SOLARIZE_ADD  i < 128 ? min(255, i + a) : i
+ *     POSTERIZE     i & ~(2^(8 - bits) - 1); bits = 0 gives black, bits >= 8 the identity
+ *     BRIGHTNESS    blend(0, i, f)
+ *     CONTRAST      blend(m, i, f) with m = trunc((double)(sum of L over the image) / (double)(S S) + 0.5),
+ *                   L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16
+ *     AUTOCONTRAST  lo, hi = smallest, largest value of the channel; hi <= lo: identity; else in float64, every operation rounded on its
+ *                   own: scale = 255.0 / (hi - lo); offset = -lo * scale; lut[i] = clip(trunc(i * scale + offset), 0, 255)
+ *     EQUALIZE      h = the channel's histogram; at most one non-empty bin: identity; step = (S S - h[last non-empty bin]) / 255 (integer);
+ *                   step == 0: identity; else n = step / 2; for i = 0 .. 255: lut[i] = min(255, n / step); n += h[i]
+ *   COLOR         out[c] = blend(L, in[c], f) with the pixel's own L.
+ *   SHARPNESS     out = blend(smooth, in, f); smooth = in on rows and columns 0 and S - 1, elsewhere in float32, every operation rounded on
+ *                 its own, k1 = 1.0f / 13.0f, k5 = 5.0f / 13.0f: ss = 0.5f; for the rows y + 1, y, y - 1 in this order:
+ *                 ss += (in[x-1] * ka + in[x] * kb) + in[x+1] * kc, the centre tap k5 and every other k1; smooth = ss <= 0 ? 0 : ss >= 255 ?
+ *                 255 : trunc(ss).  (Pillow's ImageFilter.SMOOTH.)
+ *   blend(d, i, f)  float32, unfused: t = (float)d + f * (float)(i - d), the difference taken in int.  0 <= f <= 1: trunc(t); otherwise
+ *                 t <= 0 ? 0 : t >= 255 ? 255 : trunc(t).
+ *   AFFINE        float64, unfused.  For output pixel (x, y): xin = m0 (x + 0.5) + m1 (y + 0.5) + m2, yin = m3 (x + 0.5) + m4 (y + 0.5) + m5.
+ *                 Unless 0 <= xin < S and 0 <= yin < S (a NaN fails this) the pixel is `fill`.  Otherwise xin -= 0.5, yin -= 0.5,
+ *                 X = floor(xin), Y = floor(yin), dx = xin - X, dy = yin - Y; columns are clamped to [0, S - 1].
+ *     bilinear      v1 = a + (b - a) dx on columns X, X + 1 of row clamp(Y); v2 the same on row Y + 1 if 0 <= Y + 1 < S, else v1;
+ *                   out = trunc(v1 + (v2 - v1) dy)
+ *     bicubic       cub(v1, v2, v3, v4, d) = v2 + d ((-v1 + v3) + d ((2 (v1 - v2) + v3 - v4) + d (-v1 + v2 - v3 + v4))); the first row value
+ *                   is cub over columns X - 1 .. X + 2 of row clamp(Y - 1); rows Y, Y + 1, Y + 2 give theirs the same way if inside the
+ *                   image, otherwise the value of the row before; v = cub of the four row values with dy;
+ *                   out = v <= 0 ? 0 : v >= 255 ? 255 : trunc(v)
+ *                 (Image.transform(size, AFFINE, m, resample, fillcolor=fill), which also serves Image.rotate.)
+ * records_host (nullable): a host copy of the records; when given, an op code outside AP_RA_* or an affine record whose filter is not 1 or
+ * 2 is refused (AP_ERR_SHAPE).  The kernel treats an unknown op code as AP_RA_NONE and any other filter code as AP_RESAMPLE_BILINEAR and
+ * clamps every source index, so a record it was not shown on the host cannot make it read or write out of bounds.
+ * AP_ERR_NULL: args, u8, out or records NULL, scratch NULL with n_layers > 1.  AP_ERR_SHAPE: B < 0 or > 65 535, S < 1 or > 16 384, a bad
+ * layout, n_layers outside 1 .. AP_RANDAUG_MAX_LAYERS, aliased buffers, a bad host record.  B == 0 succeeds without a launch.  Every
+ * check comes before the first launch. */
+enum { AP_RA_NONE = 0, AP_RA_AUTOCONTRAST = 1, AP_RA_EQUALIZE = 2, AP_RA_INVERT = 3, AP_RA_SOLARIZE = 4, AP_RA_SOLARIZE_ADD = 5,
+       AP_RA_POSTERIZE = 6, AP_RA_BRIGHTNESS = 7, AP_RA_CONTRAST = 8, AP_RA_COLOR = 9, AP_RA_SHARPNESS = 10, AP_RA_AFFINE = 11 };
+enum { AP_RANDAUG_RECORD_WORDS = 16, AP_RANDAUG_MAX_LAYERS = 8 };
+typedef struct ap_randaug_args {
+    const unsigned char* u8; int layout; int B, S;
+    unsigned char* out;
+    unsigned char* scratch;          /* nullable when n_layers == 1 */
+    const int* records;              /* DEVICE [B][n_layers][16] */
+    const int* records_host;         /* nullable host copy, validated */
+    int n_layers;
+    unsigned char fill[3];
+} ap_randaug_args;
+int ap_randaug_u8(const ap_randaug_args* args, ap_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
