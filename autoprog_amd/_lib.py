@@ -76,6 +76,14 @@ class RandAugArgs(Structure):
                 ("records", c_void_p), ("records_host", c_void_p), ("n_layers", c_int), ("fill", ctypes.c_ubyte * 3)]
 
 
+class LabelMapCropArgs(Structure):
+    """ap_label_map_crop_args (include/autoprog_hip.h)"""
+    _fields_ = [("scores", c_void_p), ("score_dtype", c_int), ("score_stride", c_int64), ("classes", c_void_p), ("class_dtype", c_int),
+                ("class_stride", c_int64), ("labels", c_void_p), ("boxes", c_void_p), ("boxes_host", c_void_p), ("idx", c_void_p),
+                ("val", c_void_p), ("dropped", c_void_p), ("B", c_int), ("Kin", c_int), ("Hm", c_int), ("Wm", c_int), ("P", c_int),
+                ("K", c_int), ("C", c_int)]
+
+
 class PatchMap(Structure):
     """ap_patch_map (include/autoprog_hip.h)"""
     _fields_ = [("group", c_int), ("group_stride", c_int), ("row_stride", c_int), ("kseg", c_int), ("kseg_stride", c_int)]
@@ -200,6 +208,8 @@ _SIGNATURES["ap_crop_resize_u8"] = (_I, [POINTER(CropResizeArgs), _P])
 _SIGNATURES["ap_crop_resample_u8"] = (_I, [POINTER(CropResampleArgs), _P])
 # RandAugment's ops on a uint8 batch, one launch per layer, byte for byte Pillow's (csrc/randaug.hip)
 _SIGNATURES["ap_randaug_u8"] = (_I, [POINTER(RandAugArgs), _P])
+# stored top-k label maps -> the pairs of a SparseTokenLabelTarget, ROI-aligned to each image's crop box (csrc/labelmap.hip)
+_SIGNATURES["ap_label_map_crop"] = (_I, [POINTER(LabelMapCropArgs), _P])
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 EXPECTED_ABI = 7                     # ap_abi_version() of the library these ctypes Structures mirror (include/autoprog_hip.h)

@@ -25,7 +25,11 @@ the reference rebuilds its loader (main_prog.py:651-653, 840-846).
 
 Between the two, where timm's transform chain has it, DeviceRandAugment applies the auto-augment step (`--aa rand-m9-mstd0.5-inc1`) to
 that uint8 batch: the ops and their arguments drawn on the host in timm's order, one launch of `ops.randaug_u8` (csrc/randaug.hip) per
-layer, every op Pillow's bytes -- the per-stage magnitude of AutoProg's schedule is an attribute as well."""
+layer, every op Pillow's bytes -- the per-stage magnitude of AutoProg's schedule is an attribute as well.
+
+Beside the crop, DeviceLabelMapCrop cuts the stored token-label maps of the batch (StoredLabelMaps: tlt's top-k (score, class) maps) to
+the boxes the crop just drew and flips them with the images: one launch of `ops.label_map_crop` (csrc/labelmap.hip) fills the
+SparseTokenLabelTarget of the stage's token grid, where the reference's loader ROI-aligns the maps on the CPU (main_prog.py:994-1004)."""
 import math
 import random
 import re
@@ -285,6 +289,7 @@ class DeviceRandomResizedCrop:
         self._py = random.Random(self.seed)
         self._B = None
         self.last = None
+        self.last_extents = None               # the (eh, ew) of every image of the last draw or centre crop (DeviceLabelMapCrop reads both)
 
     def _alloc(self, B):
         ring = torch.zeros(self.SLOTS, max(B, 1) * ops.CROP_RECORD_WORDS, dtype=torch.int32)
@@ -350,7 +355,7 @@ class DeviceRandomResizedCrop:
     def draw(self, B, H, W, extents=None):
         """-> the host block (int32 CPU tensor, B records of 8 words) of the next crop: one box and one flip per image, and with
         interpolation "random" one filter"""
-        ext = self._extents(B, H, W, extents)
+        ext = self.last_extents = self._extents(B, H, W, extents)
         a = self._next(B)
         rnd, hflip = self._py.random, self.hflip
         filt = self._filter(self.interpolation, True)
@@ -372,7 +377,7 @@ class DeviceRandomResizedCrop:
         """-> the host block of the central square boxes of side int(round(crop_pct * min(eh, ew))), no flip; nothing is drawn.
         interpolation: None (the object's setting), "bilinear" or "bicubic"; "random" is refused, here and as the object's setting"""
         filt = self._filter(self.interpolation if interpolation is None else interpolation, False)
-        ext = self._extents(B, H, W, extents)
+        ext = self.last_extents = self._extents(B, H, W, extents)
         a = self._next(B)
         self.last = []
         for eh, ew in ext:
@@ -423,8 +428,120 @@ class DeviceRandomResizedCrop:
         return self._launch(u8, size, host, (self.interpolation if interpolation is None else interpolation) is not None)
 
 
+class StoredLabelMaps:
+    """the stored token labels of a batch, as the loader hands them over beside the canvases: integer labels [B] and the top-k label maps
+    of the same images.  maps: tlt's tensor [B, 2, Kin, Hm, Wm] (half or float: [:, 0] the scores, [:, 1] the classes, read as two views
+    without a copy), or (scores [B, Kin, Hm, Wm], classes) with int32 classes -- label sets beyond 2048 classes need the second form,
+    fp16 does not hold their class numbers exactly.  A map covers its image's extent, not the padded canvas."""
+
+    def __init__(self, labels, maps):
+        if torch.is_tensor(maps):
+            if maps.dim() != 5 or maps.shape[1] != 2 or maps.dtype not in (torch.float16, torch.float32):
+                raise ValueError("StoredLabelMaps: a half or float [B, 2, Kin, Hm, Wm] tensor, or (scores, classes)")
+            scores, classes = maps[:, 0], maps[:, 1]
+        else:
+            scores, classes = maps
+            if not (torch.is_tensor(scores) and torch.is_tensor(classes)) or scores.dim() != 4 or scores.shape != classes.shape:
+                raise ValueError("StoredLabelMaps: scores and classes must both be [B, Kin, Hm, Wm]")
+            if scores.dtype not in (torch.float16, torch.float32) or classes.dtype not in (torch.int32, scores.dtype):
+                raise ValueError("StoredLabelMaps: half or float scores, classes int32 or in the scores' dtype")
+        if not torch.is_tensor(labels) or labels.dim() != 1 or labels.dtype.is_floating_point or labels.shape[0] != scores.shape[0]:
+            raise ValueError("StoredLabelMaps: integer labels [B] for the B images of the maps")
+        self.labels, self.scores, self.classes = labels.to(device=scores.device, dtype=torch.int64).contiguous(), scores, classes
+
+
+class DeviceLabelMapCrop:
+    """tlt's token labels from stored maps, cut where the box is known: `target(stored, crop, r)` ROI-aligns the StoredLabelMaps of a
+    batch to the boxes DeviceRandomResizedCrop just drew for it (crop.last, crop.last_extents), flips them with the images, and returns
+    the SparseTokenLabelTarget [B, 2 + P P, k] at the stage's token grid P = r // 16 -- one small copy of the B box records and one
+    launch of ops.label_map_crop (csrc/labelmap.hip).  The reference's loader does this on the CPU before create_token_label_target
+    (main_prog.py:994-1004), where the box still belongs to the loader.
+
+    The records are formed on the host in float64 and rounded to fp32: with the box (top, left, h, w) on an image of extent (eh, ew) and
+    maps of Hm x Wm,  x1 = left Wm / ew,  y1 = top Hm / eh,  x2 = (left + w) Wm / ew,  y2 = (top + h) Hm / eh,  then the flip.  They go
+    into this object's own ring of pinned blocks, as the crop's do.  The target of a (B, r) is kept and refilled in place by the next call
+    (as prog.teacher.TeacherLabeler's).  k <= 8: the mix-token class row of the loss carries 2 k pairs.  Scores are written raw; smoothing
+    is the target's attribute, applied where the loss reads the pairs.  Mixup / CutMix of token labels is not done."""
+    SLOTS = 8
+
+    def __init__(self, k=8, smoothing=0.1, num_classes=1000):
+        if not 1 <= int(k) <= ops.LABEL_MAP_MAX_K:
+            raise ValueError("DeviceLabelMapCrop: k must be 1 .. %d, got %d" % (ops.LABEL_MAP_MAX_K, int(k)))
+        if not 1 <= int(num_classes) <= 65536:
+            raise ValueError("DeviceLabelMapCrop: num_classes must be 1 .. 65536")
+        self.k, self.smoothing, self.num_classes = int(k), float(smoothing), int(num_classes)
+        self._B = None
+        self._targets = {}                     # (B, r) -> the target of that configuration, refilled by every call
+        self.last = None                       # the records of the last call: (x1, y1, x2, y2, flip) per image, as fp32 values
+
+    def _alloc(self, B, pinned):
+        ring = torch.zeros(self.SLOTS, max(B, 1) * ops.LABEL_MAP_BOX_WORDS, dtype=torch.float32)
+        self._ring = ring.pin_memory() if pinned else ring
+        self._dev = [None] * self.SLOTS
+        self._events = [None] * self.SLOTS
+        self._slot, self._B = 0, B
+
+    def records(self, crop, B, Hm, Wm, pinned=False):
+        """-> the host block (fp32 CPU tensor, B records of 8 words) of the boxes `crop` drew last, in the pixel units of Hm x Wm maps"""
+        last, ext = getattr(crop, "last", None), getattr(crop, "last_extents", None)
+        if last is None or ext is None or len(last) != B or len(ext) != B:
+            raise ValueError("DeviceLabelMapCrop: crop.last does not belong to a batch of %d images (crop the batch first)" % B)
+        if self._B != B:
+            self._alloc(B, pinned)
+        self._slot = (self._slot + 1) % self.SLOTS
+        ev = self._events[self._slot]
+        if ev is not None:
+            ev.synchronize()                   # the copy that last read this slot has executed
+        a = self._ring[self._slot].numpy().reshape(max(B, 1), ops.LABEL_MAP_BOX_WORDS)
+        a[:] = 0
+        if B:
+            box = np.asarray([rec[:5] for rec in last], dtype=np.float64)           # top, left, h, w, flip
+            e = np.asarray(ext, dtype=np.float64)
+            a[:B, 0], a[:B, 1] = box[:, 1] * Wm / e[:, 1], box[:, 0] * Hm / e[:, 0]
+            a[:B, 2], a[:B, 3] = (box[:, 1] + box[:, 3]) * Wm / e[:, 1], (box[:, 0] + box[:, 2]) * Hm / e[:, 0]
+            a[:B, 4] = box[:, 4]
+        self.last = [tuple(float(v) for v in row[:5]) for row in a[:B]]
+        return self._ring[self._slot]
+
+    def target(self, stored, crop, r, out=None):
+        """stored: the StoredLabelMaps of the batch `crop` cropped last; r: the resolution it was cropped to.  -> the
+        SparseTokenLabelTarget [B, 2 + (r // 16)^2, k] of this (B, r), overwritten by the next call with the same (B, r).  out: a target of
+        that shape to fill instead."""
+        from .loss.cross_entropy import SparseTokenLabelTarget
+        if not isinstance(stored, StoredLabelMaps):
+            raise ValueError("DeviceLabelMapCrop.target: a StoredLabelMaps")
+        if not stored.scores.is_cuda:
+            raise ops.AutoProgHipError("DeviceLabelMapCrop.target: maps on the device (the HIP path has no CPU fallback)")
+        B, _, Hm, Wm = stored.scores.shape
+        P = int(r) // 16
+        if P < 1:
+            raise ValueError("DeviceLabelMapCrop.target: r = %d has no token grid (r // 16 < 1)" % int(r))
+        host = self.records(crop, B, Hm, Wm, pinned=True)
+        dev = self._dev[self._slot]
+        if dev is None:
+            dev = self._dev[self._slot] = torch.empty(host.numel(), dtype=torch.float32, device=stored.scores.device)
+        dev.copy_(host, non_blocking=True)
+        ev = self._events[self._slot]
+        if ev is None:
+            ev = self._events[self._slot] = torch.cuda.Event()
+        ev.record()
+        key, shape = (B, int(r)), (B, 2 + P * P, self.k)
+        if out is None:
+            out = self._targets.get(key)
+            if out is None or out.idx.device != stored.scores.device:
+                out = self._targets[key] = SparseTokenLabelTarget(torch.empty(shape, dtype=torch.int32, device=stored.scores.device),
+                                                                  torch.empty(shape, dtype=torch.float32, device=stored.scores.device))
+        elif not (isinstance(out, SparseTokenLabelTarget) and tuple(out.idx.shape) == shape and out.idx.is_contiguous()
+                  and out.val.is_contiguous() and out.idx.device == stored.scores.device):
+            raise ValueError("DeviceLabelMapCrop.target: out must be a contiguous SparseTokenLabelTarget %s on the maps' device" % (shape,))
+        out.smoothing = self.smoothing
+        ops.label_map_crop(stored.scores, stored.classes, stored.labels, dev, P, self.k, self.num_classes, out=(out.idx, out.val),
+                           host_records=host)
+        return out
+
+
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
-RANDAUG_OPS = ("AutoContrast", "Equalize", "Invert", "Rotate", "Posterize", "Solarize", "SolarizeAdd", "Color", "Contrast", "Brightness",
+RANDAUG_OPS =("AutoContrast", "Equalize", "Invert", "Rotate", "Posterize", "Solarize", "SolarizeAdd", "Color", "Contrast", "Brightness",
                "Sharpness", "ShearX", "ShearY", "TranslateXRel", "TranslateYRel")      # timm's _RAND_TRANSFORMS, in its order
 _RA_MAX_LEVEL = 10.0
 _RA_ENHANCE = {"Color": ops.RA_COLOR, "Contrast": ops.RA_CONTRAST, "Brightness": ops.RA_BRIGHTNESS, "Sharpness": ops.RA_SHARPNESS}

@@ -12,7 +12,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib
-from ._lib import CropResampleArgs, CropResizeArgs, GemmEpilogue, InputPrepArgs, LnReduce, RandAugArgs, TnProblem, LN_MAX_BATCH, PREP_MAX_BOXES, TN_MAX_GROUP, TN_MAX_GROUP_DET, AutoProgHipError, check, lib
+from ._lib import CropResampleArgs, CropResizeArgs, GemmEpilogue, InputPrepArgs, LabelMapCropArgs, LnReduce, RandAugArgs, TnProblem, LN_MAX_BATCH, PREP_MAX_BOXES, TN_MAX_GROUP, TN_MAX_GROUP_DET, AutoProgHipError, check, lib
 
 BF16 = torch.bfloat16
 
@@ -1241,6 +1241,61 @@ def randaug_u8(u8, records, n_layers, fill, layout="nchw", out=None, scratch=Non
         a.records_host = host_records.data_ptr()
     check(lib.ap_randaug_u8(ctypes.byref(a), _stream()), "ap_randaug_u8")
     return out
+
+
+# ------------------------------------------------------------------------------------- token labels from stored top-k label maps
+LABEL_MAP_BOX_WORDS = 8                           # a record of ap_label_map_crop: x1, y1, x2, y2, flip (fp32), three zero words
+LABEL_MAP_MAX_K = 8                               # pairs kept per bin: the mix-token class row of the loss carries 2 K <= 16
+
+
+def _label_map_view(t, name):
+    """a [B,Kin,Hm,Wm] device tensor whose images are contiguous (any stride between images, e.g. one half of tlt's [B,2,Kin,Hm,Wm])"""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dim() == 4):
+        raise AutoProgHipError("label_map_crop: %s must be a [B,Kin,Hm,Wm] CUDA tensor (the HIP path has no CPU fallback)" % name)
+    _, Kin, Hm, Wm = t.shape
+    if t.shape[0] and tuple(t.stride()[1:]) != (Hm * Wm, Wm, 1):
+        raise AutoProgHipError("label_map_crop: the [Kin,Hm,Wm] block of every image of %s must be contiguous" % name)
+    return t
+
+
+def label_map_crop(scores, classes, labels, boxes, P, K, C, out=None, dropped=None, host_records=None):
+    """stored top-k label maps -> the arrays of a SparseTokenLabelTarget at the token grid P, in one launch (include/autoprog_hip.h,
+    ap_label_map_crop): scores fp16 / fp32 [B,Kin,Hm,Wm], classes the same shape in the scores' dtype or int32 (both may be views with
+    their own stride between images), labels int64 [B], boxes fp32 on the device, B records x1, y1, x2, y2 (map pixel units), flip, 0, 0, 0.
+    Slot 0 of the result is (label, 1), slot 1 the box's pooled top-K, slots 2.. those of the P x P ROI-align bins, flipped with the image.
+    `out`: (idx int32, val fp32), both [B, 2 + P P, K] and contiguous, to write into; `dropped`: fp32 [B, 1 + P P] that receives the
+    score mass of the classes beyond K per bin; `host_records`: a CPU copy of `boxes`, validated before the launch.  -> (idx, val)"""
+    _label_map_view(scores, "scores"); _label_map_view(classes, "classes")
+    _req(labels, torch.int64, "labels"); _req(boxes, torch.float32, "boxes")
+    if scores.dtype not in (torch.float16, torch.float32) or classes.dtype not in (scores.dtype, torch.int32):
+        raise AutoProgHipError("label_map_crop: fp16 or fp32 scores, classes in the same dtype or int32 (got %s, %s)" % (scores.dtype, classes.dtype))
+    B, Kin, Hm, Wm = scores.shape
+    P, K, C = int(P), int(K), int(C)
+    if tuple(classes.shape) != (B, Kin, Hm, Wm) or labels.numel() != B or classes.device != scores.device:
+        raise AutoProgHipError("label_map_crop: scores and classes [B,Kin,Hm,Wm] on one device, labels [B]")
+    words = B * LABEL_MAP_BOX_WORDS
+    if boxes.numel() < words or (host_records is not None and (host_records.is_cuda or host_records.dtype != torch.float32
+                                                               or not host_records.is_contiguous() or host_records.numel() < words)):
+        raise AutoProgHipError("label_map_crop: %d images need %d fp32 words of box records (and the same in a CPU fp32 host copy)" % (B, words))
+    shape = (B, 2 + P * P, K)
+    if out is None:
+        out = (torch.empty(shape, dtype=torch.int32, device=scores.device), torch.empty(shape, dtype=torch.float32, device=scores.device))
+    idx, val = out
+    if tuple(_req(idx, torch.int32, "idx").shape) != shape or tuple(_req(val, torch.float32, "val").shape) != shape:
+        raise AutoProgHipError("label_map_crop: out must be (int32, fp32) tensors of shape %s" % (shape,))
+    a = LabelMapCropArgs()
+    a.scores, a.score_dtype, a.score_stride = scores.data_ptr(), int(scores.dtype == torch.float32), scores.stride(0) if B else 0
+    a.classes, a.class_dtype, a.class_stride = classes.data_ptr(), int(classes.dtype == torch.int32), classes.stride(0) if B else 0
+    a.labels, a.boxes, a.idx, a.val = labels.data_ptr(), boxes.data_ptr(), idx.data_ptr(), val.data_ptr()
+    if host_records is not None:
+        a.boxes_host = host_records.data_ptr()
+    if dropped is not None:
+        if tuple(_req(dropped, torch.float32, "dropped").shape) != (B, 1 + P * P):
+            raise AutoProgHipError("label_map_crop: dropped must be fp32 [%d, %d]" % (B, 1 + P * P))
+        a.dropped = dropped.data_ptr()
+    a.B, a.Kin, a.Hm, a.Wm, a.P, a.K, a.C = B, Kin, Hm, Wm, P, K, C
+    check(lib.ap_label_map_crop(ctypes.byref(a), _stream()), "ap_label_map_crop")
+    return idx, val
 
 
 # ------------------------------------------------------------------------------------- stem 7x7 / stride 2 convolution (3 -> 64)

@@ -21,6 +21,7 @@ import time
 import torch
 
 from . import search as S
+from ..data import StoredLabelMaps
 from .helpers import ActiveLayerMask
 
 
@@ -34,7 +35,7 @@ class AutoProgDriver:
                  search_epochs=2, auto_grow=True, probe_batches=4, time_steps=4, seed=0, log=None, original_batch_splits=1,
                  r_max=None, dist_bn="", use_graphs=False, graph_after=2, clip_grad=None, clip_mode="norm", get_val_batches=None,
                  batch_prep=None, re_list=None, skip_nonfinite=False, teacher=None, crop=None, resize_list=None, *, augment=None,
-                 aa_list=None):
+                 aa_list=None, label_maps=None):
         """model: supernet sized for l_list[-1] (e.g. volo_h12_l18); optimizer: FlatAdamWEma over it; reducer: its
         GradientBucketReducer; r_list / l_list / dp_list / grow_epochs: the stage schedule (prog/progressive.py:4-31);
         get_batch(r): a training batch (images at ANY size -- the stem resizes to r -- and a token-label target for r // 16).
@@ -95,7 +96,25 @@ class AutoProgDriver:
         "rand-m4-mstd0.5-inc1"; the reference rebuilds its loader and worker processes for it, main_prog.py:651-656): augment.set_spec(
         aa_list[stage]) at every stage change, where re_prob and crop.scale are set -- the magnitude becomes an attribute, and "" switches
         the step off for the stage.  A search augments with the spec of the stage it starts from, as it erases and crops.  Both None
-        (default): nothing changes."""
+        (default): nothing changes.
+        label_maps (keyword only): a data.DeviceLabelMapCrop (needs a crop; not beside a teacher).  When get_batch returns
+        (canvases_u8, data.StoredLabelMaps) -- the loader's fixed canvases and the stored top-k label maps of the same images -- the maps
+        become label_maps.target(stored, crop, r) directly after crop.crop(images, r): the SparseTokenLabelTarget of the box and flip just
+        drawn, at the token grid of the stage's or of a search candidate's r (the reference's loader cuts its maps with ROI-align before
+        create_token_label_target, main_prog.py:994-1004).  The launch stays outside captured graphs; the target reaches a graph as a
+        teacher's does.  Token labels are not cut with Mixup / CutMix: a mixing batch_prep is refused here as beside a TeacherLabeler.  The
+        geometric ops of an `augment` move pixels, not labels.  None (default): nothing changes."""
+        if label_maps is not None:
+            if crop is None:
+                raise ValueError("label_maps needs a crop: the maps are cut to the boxes DeviceRandomResizedCrop draws")
+            if teacher is not None:
+                raise ValueError("label_maps and teacher both make the token-label target: give one of them")
+            if batch_prep is not None and getattr(batch_prep, "mix_enabled", False):
+                raise ValueError("a teacher's token labels cannot follow Mixup / CutMix: build the batch_prep with mixup_alpha = cutmix_alpha = 0")
+            lc, mc = getattr(label_maps, "num_classes", None), getattr(model, "num_classes", None)
+            if lc is not None and mc is not None and int(lc) != int(mc):
+                raise ValueError("label_maps labels %d classes, the model has %d" % (lc, mc))
+        self.label_maps = label_maps
         if augment is not None and batch_prep is None:
             raise ValueError("augment needs a batch_prep: the augmented uint8 batch is what DeviceBatchPrep.prep takes")
         if augment is not None and getattr(augment, "layout", None) != getattr(batch_prep, "layout", None):
@@ -157,6 +176,8 @@ class AutoProgDriver:
         if torch.is_tensor(images) and images.dtype == torch.uint8:
             if self.crop is not None:                                      # a[0]: the resolution of the stage or of the search's candidate
                 images = self.crop.crop(images, a[0])
+                if self.label_maps is not None and isinstance(target, StoredLabelMaps):
+                    target = self.label_maps.target(target, self.crop, a[0])       # the labels of the box just drawn, at this r's token grid
             if self.augment is not None:
                 images = self.augment(images)
             images = self.batch_prep.prep(images)

@@ -781,6 +781,55 @@ typedef struct ap_randaug_args {
 } ap_randaug_args;
 int ap_randaug_u8(const ap_randaug_args* args, ap_stream_t stream);
 
+/* ---- token labels from stored top-k label maps, ROI-aligned to each image's crop box and flipped with it, in one launch (additive in ABI
+ * version 7; csrc/labelmap.hip).  The reference's published recipe (`train_autoprog.sh --token-label --token-label-data ...`) trains on
+ * stored NFNet-F6 label maps, a top-5 (score, class) map per image, which its loader cuts to the image's random crop box with
+ * roi_align(aligned=False, sampling_ratio=-1) on the densified maps and flips with the image before tlt's create_token_label_target
+ * (main_prog.py:994-1004).  tlt and torchvision are not at hand: the rule below is this library's restatement of that forward, from
+ * knowledge of those packages, not byte-checked against them; tests/_labelmap_ref.py pins it in fp64.
+ * scores (DEVICE): [B][Kin][Hm][Wm], fp16 (AP_LM_F16) or fp32 (AP_LM_F32) by score_dtype, image b at element b * score_stride; scores are
+ * non-negative.  classes (DEVICE): the same shape at its own class_stride, in the scores' float dtype (AP_LM_CLASS_FLOAT, converted by
+ * truncation) or int32 (AP_LM_CLASS_I32); a class outside [0, C) contributes nothing.  tlt's stored half tensor [B, 2, Kin, Hm, Wm] passes
+ * as two views of one buffer.  labels (DEVICE): int64 [B].  boxes (DEVICE): B records of 8 fp32 words: x1, y1, x2, y2 in map pixel
+ * units, the flip as 0.0 or 1.0, then three zero words.  idx (int32) and val (fp32): [B, 2 + P P, K], contiguous -- the arrays of a
+ * SparseTokenLabelTarget at the token grid P.  dropped (nullable): fp32 [B, 1 + P P].
+ * An output bin of image b is the class slot (the single bin of a 1 x 1 pooling of the box, Pw = Ph = 1) or one of the P x P token bins
+ * (Pw = Ph = P).  In fp64, for the x axis and the same in y:
+ *     roi_w = max(x2 - x1, 1);  bin_w = roi_w / Pw;  gw = ceil(roi_w / Pw)
+ *     sample ix of bin pw:  x = x1 + pw * bin_w + (ix + 0.5) * bin_w / gw
+ *     a sample with x < -1 or x > Wm (or the same in y) counts but adds nothing;  x = max(x, 0);  xl = (int)x;
+ *     if xl >= Wm - 1: xl = xh = Wm - 1, x = xl  else xh = xl + 1;  lx = x - xl, hx = 1 - lx
+ *     dense[c] = (1 / (gh gw)) * sum over the samples, over the 4 corners (weights hy hx, hy lx, ly hx, ly lx), over k < Kin with
+ *                classes[b, k, corner] == c, of weight * scores[b, k, corner]
+ * Slot 0 is (labels[b], 1.0), then fillers (-1, 0.0).  Slot 1 (the class slot) and slots 2.. (the token bins) hold the K classes with
+ * the largest dense[c] > 0, by descending score and equal scores by ascending class (the tie rule of ap_softmax_topk_rows), completed
+ * with fillers.  With flip 1, token slot 2 + ph P + pw holds bin (ph, P - 1 - pw); rows never flip and the class slot is unaffected.
+ * dropped[b][slot - 1]: the sum of dense[c] over the classes that were not kept -- keeping the top K where a bin can see more classes is a
+ * stated deviation from the reference, and this makes it visible.  Raw scores are written: label smoothing is applied where the loss
+ * reads the pairs.  Corners that carry the same class merge into one pair.
+ * The kernel forms the sample positions and a pixel's separable weight wy[y] wx[x] / (gh gw) in fp64, products and sums in fp32, every
+ * bin's sums in a fixed order and without atomics: the output is bit-reproducible.  One launch for all B (1 + P P) bins; the launch
+ * geometry depends on B and P alone, never on the records.  boxes_host (nullable): a host copy of the records, validated before the
+ * launch.  The kernel clamps what it indexes (a bin's pixels into the map, the samples of a pixel's weight to the 16 nearest), so a record
+ * it was not shown on the host cannot make it read or write out of bounds.
+ * AP_ERR_NULL: args or a required pointer NULL.  AP_ERR_SHAPE: K or Kin outside 1..8, P < 1 (or P P beyond 2^30), Hm or Wm < 1, C outside
+ * 1..65536, B < 0, a bad dtype flag, a host record with x2 < x1 or y2 < y1, a non-finite word or a flip other than 0 or 1.
+ * AP_ERR_UNSUPPORTED: Hm Wm Kin > 4096 (the candidates of the class slot's bin, which a workgroup keeps in LDS).  B == 0 succeeds
+ * without a launch.  Every check comes before the launch. */
+enum { AP_LM_F16 = 0, AP_LM_F32 = 1 };                   /* score_dtype */
+enum { AP_LM_CLASS_FLOAT = 0, AP_LM_CLASS_I32 = 1 };     /* class_dtype */
+typedef struct ap_label_map_crop_args {
+    const void* scores; int score_dtype; int64_t score_stride;
+    const void* classes; int class_dtype; int64_t class_stride;
+    const int64_t* labels;           /* DEVICE [B] */
+    const float* boxes;              /* DEVICE [B][8] */
+    const float* boxes_host;         /* nullable host copy, validated */
+    int* idx; float* val;            /* [B][2 + P P][K] */
+    float* dropped;                  /* nullable, [B][1 + P P] */
+    int B, Kin, Hm, Wm, P, K, C;
+} ap_label_map_crop_args;
+int ap_label_map_crop(const ap_label_map_crop_args* args, ap_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
