@@ -36,6 +36,14 @@ __device__ __forceinline__ u32x4 pack8(const float* f) {
 }
 __device__ __forceinline__ u32x4 ld16(const void* p) { return *reinterpret_cast<const u32x4*>(p); }
 __device__ __forceinline__ void st16(void* p, const u32x4& v) { *reinterpret_cast<u32x4*>(p) = v; }
+// the 16 bytes at p + g of a buffer of `total` bytes, nothing read past its last byte: the chunk that crosses the end goes byte by byte
+// (zero beyond the end)
+__device__ __forceinline__ u32x4 ld16_clipped(const unsigned char* p, int64_t g, int64_t total) {
+    if (g + 16 <= total) return ld16(p + g);
+    unsigned q[4] = {0u, 0u, 0u, 0u};
+    for (int e = 0; e < 16; ++e) if (g + e < total) q[e >> 2] |= (unsigned)p[g + e] << ((e & 3) * 8);
+    return u32x4{q[0], q[1], q[2], q[3]};
+}
 // the same for a GLOBAL output that this kernel does not read again: nontemporal (no L2 allocation).  The consumer is the next kernel,
 // behind an L2 write-back either way; on the GEMM epilogues alone this was 13.36 -> 12.96 ms per step (AP_NT_STORES=0 at build time: plain)
 #ifndef AP_NT_STORES

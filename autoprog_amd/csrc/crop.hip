@@ -7,14 +7,15 @@
 // No antialiasing when a box is scaled down: that is what the reference's own 224 -> r F.interpolate does.
 //
 // A workgroup owns `tr` output rows of one image.  The source rows they read are staged in LDS as the bytes they are, with 16-byte loads,
-// row by row and only over the box's column span, each row from its own 16-byte-aligned start.  A lane then produces four consecutive
-// output pixels of a row in all three channels, the coordinates computed once: three dwords, one per channel plane (NCHW) or side by side
-// (NHWC); byte stores where the address is not 4-byte aligned (odd S, an output view) and at a row's tail.  The record is clamped into
-// the image first, so every source coordinate lies in [0, Hi-1] x [0, Wi-1] whatever the record says.
+// row by row and only over the box's column span, each row from its own 16-byte-aligned start (u8_box.h, shared with resample.hip).  A
+// lane then produces four consecutive output pixels of a row in all three channels, the coordinates computed once: three dwords, one per
+// channel plane (NCHW) or side by side (NHWC); byte stores where the address is not 4-byte aligned (odd S, an output view) and at a
+// row's tail.  The record is clamped into the image first, so every source coordinate lies in [0, Hi-1] x [0, Wi-1] whatever the record
+// says.
 //
 // Built with -ffp-contract=off (csrc/Makefile): every operation of the header's arithmetic is rounded on its own, which is the float32
 // restatement of tests/_crop_ref.py operation for operation.
-#include "common.h"
+#include "u8_box.h"
 
 #if defined(__FAST_MATH__)
 #error "crop.hip must be built with -ffp-contract=off and without fast-math (csrc/Makefile)"
@@ -45,10 +46,8 @@ k_crop_resize_u8(ap_crop_resize_args A, CropGeom G) {
     const int Hi = A.Hi, Wi = A.Wi, S = A.S;
 
     // ---- the record, clamped into the image: nothing below can leave it
-    const int* rec = A.records + (int64_t)b * 8;
-    const int h = min(max(rec[2], 1), Hi), w = min(max(rec[3], 1), Wi);
-    const int top = min(max(rec[0], 0), Hi - h), left = min(max(rec[1], 0), Wi - w);
-    const int flip = rec[4] & 1;
+    const BoxRecord R = box_record(A.records + (int64_t)b * 8, Hi, Wi);
+    const int h = R.h, w = R.w, top = R.top, left = R.left, flip = R.flip;
     const float sh = (float)h / (float)S, sw = (float)w / (float)S;
 
     // ---- the tile's output rows and the box rows they read
@@ -59,49 +58,15 @@ k_crop_resize_u8(ap_crop_resize_args A, CropGeom G) {
     const int y_hi = min(y_hl + 1, h - 1);
     const int nrows = min(y_hi - y_lo + 1, G.maxrows);           // (== y_hi - y_lo + 1: maxrows bounds it for every box, crop_geometry)
 
-    // ---- stage rows y_lo .. y_lo + nrows - 1 of the box, columns left .. left + w - 1, per plane: chunk k of a row is the 16 bytes at
-    // (the row's first byte & ~15) + 16 k.  CROP_BATCH loads are issued before the first one is stored; indices past the end repeat the
-    // last chunk (loaded, not stored)
-    const int64_t total = (int64_t)A.B * 3 * Hi * Wi;
-    const int rowbytes = Wi * G.ps;
-    const int cpr = min((w * G.ps + 30) >> 4, G.pitch >> 4);      // chunks per row: covers any misalignment of the row's start
-    const int nchunk = G.nseg * nrows * cpr;
-    const int64_t img0 = (int64_t)b * 3 * Hi * Wi;
-    for (int base = tid; base < nchunk; base += CROP_BATCH * CROP_THREADS) {
-        u32x4 v[CROP_BATCH];
-        int64_t g[CROP_BATCH];
-        int dst[CROP_BATCH];
-#pragma unroll
-        for (int j = 0; j < CROP_BATCH; ++j) {
-            const int idx = min(base + j * CROP_THREADS, nchunk - 1);
-            const int row = idx / cpr, k = idx - row * cpr;
-            const int s = row / nrows, r = row - s * nrows;
-            const int64_t g0 = img0 + ((int64_t)(NHWC ? 0 : s) * Hi + (top + y_lo + r)) * rowbytes + left * G.ps;
-            g[j] = (g0 & ~(int64_t)15) + ((int64_t)k << 4);
-            dst[j] = (s * G.maxrows + r) * G.pitch + (k << 4);
-            v[j] = u32x4{0u, 0u, 0u, 0u};
-            if (total >= 16) v[j] = ld16(A.u8 + (g[j] + 16 <= total ? g[j] : 0));      // (uniform: a batch below 16 bytes goes byte by byte)
-        }
-#pragma unroll
-        for (int j = 0; j < CROP_BATCH; ++j) {
-            if (base + j * CROP_THREADS >= nchunk) break;
-            if (g[j] + 16 > total) {                                // the last chunk of the batch: byte by byte, nothing read past the end
-                unsigned q[4] = {0u, 0u, 0u, 0u};
-                for (int e = 0; e < 16; ++e) if (g[j] + e < total) q[e >> 2] |= (unsigned)A.u8[g[j] + e] << ((e & 3) * 8);
-                v[j][0] = q[0]; v[j][1] = q[1]; v[j][2] = q[2]; v[j][3] = q[3];
-            }
-            st16(stage + dst[j], v[j]);
-        }
-    }
+    // ---- stage rows y_lo .. y_lo + nrows - 1 of the box
+    box_stage<NHWC, CROP_THREADS, CROP_BATCH>(stage, A.u8, A.B, Hi, Wi, b, top + y_lo, left, w, nrows, G.maxrows, G.pitch, G.nseg, G.ps);
     __syncthreads();
 
     // ---- four consecutive output pixels of one row, all three channels, per lane and trip: the coordinates are computed once
     const int Q = (S + 3) >> 2;
     const int rows = oy_last - oy_first + 1;
     const int items = rows * Q;
-    // where staged row r of plane s begins: its slot + ((first byte of plane s, row y_lo) + r rowbytes) & 15
-    const int mis_img = (int)((img0 + (int64_t)(top + y_lo) * rowbytes + left * G.ps) & 15);
-    const int mis_plane = NHWC ? 0 : (int)(((int64_t)Hi * rowbytes) & 15);
+    const BoxStart M = box_start<NHWC>(Hi, Wi, b, top + y_lo, left, G.ps);
     const int64_t plane_out = NHWC ? 1 : (int64_t)S * S;                        // bytes between two channels of an output pixel
     for (int it = tid; it < items; it += CROP_THREADS) {
         const int ry = it / Q, q = it - ry * Q;
@@ -113,13 +78,8 @@ k_crop_resize_u8(ap_crop_resize_args A, CropGeom G) {
         int o0[3], o1[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            if (NHWC) {
-                o0[c] = r0 * G.pitch + ((mis_img + r0 * rowbytes) & 15) + c;
-                o1[c] = r1 * G.pitch + ((mis_img + r1 * rowbytes) & 15) + c;
-            } else {
-                o0[c] = (c * G.maxrows + r0) * G.pitch + ((mis_img + c * mis_plane + r0 * rowbytes) & 15);
-                o1[c] = (c * G.maxrows + r1) * G.pitch + ((mis_img + c * mis_plane + r1 * rowbytes) & 15);
-            }
+            o0[c] = box_pixel<NHWC>(M, G.maxrows, G.pitch, c, r0, 0);
+            o1[c] = box_pixel<NHWC>(M, G.maxrows, G.pitch, c, r1, 0);
         }
         // the lane's 12 output bytes as three dwords in the order they are stored: channel c's four pixels (NCHW: byte 4 c + j) or the four
         // pixels' channels side by side (NHWC: byte 3 j + c)
@@ -151,6 +111,8 @@ k_crop_resize_u8(ap_crop_resize_args A, CropGeom G) {
                 for (int k = 0; k < 12; ++k) if (k < 3 * nvalid) dstp[k] = (unsigned char)(word[k >> 2] >> (8 * (k & 3)));
             }
         } else {
+            // (written out, not box_store4 of u8_box.h: through the helper the compiler tests `j < nvalid` once for the three channels and
+            // issues four of the pixel loop's LDS reads later -- measured 0.1 - 0.4 us per launch slower, profiles/loader_core_refactor.txt)
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 unsigned char* dstp = A.out + ((((int64_t)b * 3 + c) * S + oy) * S + q * 4);
@@ -168,9 +130,7 @@ k_crop_resize_u8(ap_crop_resize_args A, CropGeom G) {
 // height h read box rows floor(f(o)) .. floor(f(o + tr - 1)) + 1 with f(o + tr - 1) - f(o) = (tr - 1) h / S, and floor(a) - floor(b) <
 // a - b + 1: at most ceil((tr - 1) h / S) + 2 rows, largest at h = Hi; one more row covers the rounding of the float expression.
 static int crop_geometry(const ap_crop_resize_args* a, CropGeom* g) {
-    g->nseg = a->layout == AP_PREP_NCHW ? 3 : 1;
-    g->ps = a->layout == AP_PREP_NCHW ? 1 : 3;
-    const int64_t pitch = ((int64_t)a->Wi * g->ps + 15 + 15) / 16 * 16;
+    const int64_t pitch = box_row_geometry(a->layout, a->Wi, &g->nseg, &g->ps);
     for (int tr = 16; tr >= 1; tr >>= 1) {
         int64_t maxrows = ((int64_t)(tr - 1) * a->Hi + a->S - 1) / a->S + 3;
         if (maxrows > a->Hi) maxrows = a->Hi;
@@ -184,21 +144,9 @@ static int crop_geometry(const ap_crop_resize_args* a, CropGeom* g) {
 }
 
 extern "C" int ap_crop_resize_u8(const ap_crop_resize_args* args, ap_stream_t stream) {
-    if (!args) return AP_ERR_NULL;
+    bool empty;
+    if (const int rc = box_check(args, false, &empty); rc != AP_OK || empty) return rc;
     const ap_crop_resize_args& a = *args;
-    if (a.B < 0 || a.Hi <= 0 || a.Wi <= 0 || a.S <= 0) return AP_ERR_SHAPE;
-    if (a.layout != AP_PREP_NCHW && a.layout != AP_PREP_NHWC) return AP_ERR_SHAPE;
-    if (a.B == 0) return AP_OK;
-    if (!a.u8 || !a.out || !a.records) return AP_ERR_NULL;
-    if (reinterpret_cast<uintptr_t>(a.u8) & 15) return AP_ERR_SHAPE;
-    if ((int64_t)a.B * 3 * a.Hi * a.Wi > ((int64_t)1 << 40)) return AP_ERR_SHAPE;
-    if (a.records_host) {
-        for (int64_t i = 0; i < a.B; ++i) {
-            const int* q = a.records_host + i * 8;
-            if (q[2] < 1 || q[3] < 1 || q[0] < 0 || q[1] < 0 || (int64_t)q[0] + q[2] > a.Hi || (int64_t)q[1] + q[3] > a.Wi) return AP_ERR_SHAPE;
-            if (q[4] != 0 && q[4] != 1) return AP_ERR_SHAPE;
-        }
-    }
     CropGeom g;
     const int lds = crop_geometry(&a, &g);
     if (lds < 0) return AP_ERR_UNSUPPORTED;                       // one output row's source rows do not fit the LDS budget

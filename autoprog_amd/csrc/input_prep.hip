@@ -185,17 +185,8 @@ k_input_prep(ap_input_prep_args A, PrepGeom G) {
             const int mis = (int)(g0 - a0);
             const int lbase = (img * G.nseg + s) * G.segcap;
             const int nchunk = min((mis + span + 15) >> 4, cap16);
-            for (int k = tid; k < nchunk; k += PREP_THREADS) {
-                const int64_t g = a0 + ((int64_t)k << 4);
-                u32x4 v;
-                if (g + 16 <= total) v = ld16(A.u8 + g);
-                else {                                              // the last chunk of the batch: byte by byte, nothing read past the end
-                    unsigned w[4] = {0u, 0u, 0u, 0u};
-                    for (int e = 0; e < 16; ++e) if (g + e < total) w[e >> 2] |= (unsigned)A.u8[g + e] << ((e & 3) * 8);
-                    v[0] = w[0]; v[1] = w[1]; v[2] = w[2]; v[3] = w[3];
-                }
-                st16(stage + lbase + (k << 4), v);
-            }
+            for (int k = tid; k < nchunk; k += PREP_THREADS)        // (nothing read past the end of the batch)
+                st16(stage + lbase + (k << 4), ld16_clipped(A.u8, a0 + ((int64_t)k << 4), total));
             if (A.in_layout == AP_PREP_NCHW) { (img ? T.off_b : T.off_a)[s] = lbase + mis; }
             else {
 #pragma unroll

@@ -10,7 +10,8 @@
 // image and
 //   A  builds both coefficient tables in LDS: all S horizontal windows and its own rows' vertical ones, one lane per window walking its
 //      taps in order in fp64 (the order of the sum that normalises them matters);
-//   B  stages box rows ymin(first row) .. ymax(last row) - 1 over the box's column span in LDS with 16-byte loads, as k_crop_resize_u8;
+//   B  stages box rows ymin(first row) .. ymax(last row) - 1 over the box's column span in LDS with 16-byte loads (u8_box.h, shared
+//      with k_crop_resize_u8);
 //   C  runs the horizontal pass into an LDS intermediate of rows x 3 x S uint8 in the OUTPUT's layout, already flipped: one lane per
 //      (row, output column) does the three channels with one read of each coefficient;
 //   D  runs the vertical pass four bytes of an intermediate row at a time (one dword read per tap) and stores dwords, bytes where the
@@ -20,7 +21,7 @@
 // read or written out of bounds.
 //
 // Built with -ffp-contract=off and without fast-math (csrc/Makefile): no fused multiply-add, IEEE double division.
-#include "common.h"
+#include "u8_box.h"
 
 #if defined(__FAST_MATH__)
 #error "resample.hip must be built with -ffp-contract=off and without fast-math (csrc/Makefile)"
@@ -98,9 +99,8 @@ k_crop_resample_u8(ap_crop_resample_args A, ResampleGeom G) {
 
     // ---- the record, clamped into the image, the filter into {1, 2}: nothing below can leave the image or the tables
     const int* rec = A.records + (int64_t)b * 8;
-    const int h = min(max(rec[2], 1), Hi), w = min(max(rec[3], 1), Wi);
-    const int top = min(max(rec[0], 0), Hi - h), left = min(max(rec[1], 0), Wi - w);
-    const int flip = rec[4] & 1;
+    const BoxRecord R = box_record(rec, Hi, Wi);
+    const int h = R.h, w = R.w, flip = R.flip;
     const int bicubic = rec[5] == 2;
 
     const int oy_first = tile * G.tr;
@@ -115,46 +115,12 @@ k_crop_resample_u8(ap_crop_resample_args A, ResampleGeom G) {
     const int y_lo = vb[0];                                       // (first taps and last taps both grow with the output row)
     const int nrows = min(max(vb[2 * (rows - 1)] + vb[2 * (rows - 1) + 1] - y_lo, 1), min(G.maxrows, h - y_lo));
 
-    // ---- B: stage rows y_lo .. y_lo + nrows - 1 of the box, columns left .. left + w - 1, per plane: chunk k of a row is the 16 bytes at
-    // (the row's first byte & ~15) + 16 k.  RS_BATCH loads are issued before the first one is stored; indices past the end repeat the
-    // last chunk (loaded, not stored)
-    const int64_t total = (int64_t)A.B * 3 * Hi * Wi;
-    const int rowbytes = Wi * G.ps;
-    const int cpr = min((w * G.ps + 30) >> 4, G.pitch >> 4);      // chunks per row: covers any misalignment of the row's start
-    const int nchunk = G.nseg * nrows * cpr;
-    const int64_t img0 = (int64_t)b * 3 * Hi * Wi;
-    for (int base = tid; base < nchunk; base += RS_BATCH * RS_THREADS) {
-        u32x4 v[RS_BATCH];
-        int64_t g[RS_BATCH];
-        int dst[RS_BATCH];
-#pragma unroll
-        for (int j = 0; j < RS_BATCH; ++j) {
-            const int idx = min(base + j * RS_THREADS, nchunk - 1);
-            const int row = idx / cpr, k = idx - row * cpr;
-            const int s = row / nrows, r = row - s * nrows;
-            const int64_t g0 = img0 + ((int64_t)(NHWC ? 0 : s) * Hi + (top + y_lo + r)) * rowbytes + left * G.ps;
-            g[j] = (g0 & ~(int64_t)15) + ((int64_t)k << 4);
-            dst[j] = (s * G.maxrows + r) * G.pitch + (k << 4);
-            v[j] = u32x4{0u, 0u, 0u, 0u};
-            if (total >= 16) v[j] = ld16(A.u8 + (g[j] + 16 <= total ? g[j] : 0));      // (uniform: a batch below 16 bytes goes byte by byte)
-        }
-#pragma unroll
-        for (int j = 0; j < RS_BATCH; ++j) {
-            if (base + j * RS_THREADS >= nchunk) break;
-            if (g[j] + 16 > total) {                                // the last chunk of the batch: byte by byte, nothing read past the end
-                unsigned q[4] = {0u, 0u, 0u, 0u};
-                for (int e = 0; e < 16; ++e) if (g[j] + e < total) q[e >> 2] |= (unsigned)A.u8[g[j] + e] << ((e & 3) * 8);
-                v[j][0] = q[0]; v[j][1] = q[1]; v[j][2] = q[2]; v[j][3] = q[3];
-            }
-            st16(stage + dst[j], v[j]);
-        }
-    }
+    // ---- B: stage rows y_lo .. y_lo + nrows - 1 of the box
+    box_stage<NHWC, RS_THREADS, RS_BATCH>(stage, A.u8, A.B, Hi, Wi, b, R.top + y_lo, R.left, w, nrows, G.maxrows, G.pitch, G.nseg, G.ps);
     __syncthreads();
 
-    // ---- C: the horizontal pass, rounded to uint8.  Staged row r of plane s begins at its slot + ((first byte of plane s, row y_lo) +
-    // r rowbytes) & 15.  Window o lands in column S - 1 - o of a flipped image
-    const int mis_img = (int)((img0 + (int64_t)(top + y_lo) * rowbytes + left * G.ps) & 15);
-    const int mis_plane = NHWC ? 0 : (int)(((int64_t)Hi * rowbytes) & 15);
+    // ---- C: the horizontal pass, rounded to uint8.  Window o lands in column S - 1 - o of a flipped image
+    const BoxStart M = box_start<NHWC>(Hi, Wi, b, R.top + y_lo, R.left, G.ps);
     const int ipitch = 3 * G.Sp;
     for (int it = tid; it < nrows * S; it += RS_THREADS) {
         const int r = it / S, o = it - r * S;
@@ -162,9 +128,7 @@ k_crop_resample_u8(ap_crop_resample_args A, ResampleGeom G) {
         const int* K = hk + o * G.ksh;
         int src[3];
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
-            src[c] = NHWC ? r * G.pitch + ((mis_img + r * rowbytes) & 15) + xmin * 3 + c
-                          : (c * G.maxrows + r) * G.pitch + ((mis_img + c * mis_plane + r * rowbytes) & 15) + xmin;
+        for (int c = 0; c < 3; ++c) src[c] = box_pixel<NHWC>(M, G.maxrows, G.pitch, c, r, xmin);
         int acc[3] = {1 << 21, 1 << 21, 1 << 21};
         for (int i = 0; i < cnt; ++i) {
             const int k = K[i];
@@ -204,11 +168,7 @@ k_crop_resample_u8(ap_crop_resample_args A, ResampleGeom G) {
             dstp = A.out + ((((int64_t)b * 3 + c) * S + oy) * S + q * 4);
             nvalid = min(4, S - q * 4);
         }
-        if (nvalid == 4 && !(reinterpret_cast<uintptr_t>(dstp) & 3)) *reinterpret_cast<unsigned*>(dstp) = word;
-        else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) if (j < nvalid) dstp[j] = (unsigned char)(word >> (8 * j));
-        }
+        box_store4(dstp, word, nvalid);
     }
 }
 
@@ -224,9 +184,7 @@ static int64_t align16(int64_t v) { return (v + 15) / 16 * 16; }
 // of a box of height h read box rows from trunc(c(o) - support + 0.5) up to, not including, trunc(c(o + tr - 1) + support + 0.5) with
 // c(o + tr - 1) - c(o) = (tr - 1) h / S: at most (tr - 1) h / S + 2 support + 1 rows, which grows with h; one more row covers the rounding
 static int resample_geometry(const ap_crop_resample_args* a, ResampleGeom* g) {
-    g->nseg = a->layout == AP_PREP_NCHW ? 3 : 1;
-    g->ps = a->layout == AP_PREP_NCHW ? 1 : 3;
-    const int64_t pitch = ((int64_t)a->Wi * g->ps + 15 + 15) / 16 * 16;
+    const int64_t pitch = box_row_geometry(a->layout, a->Wi, &g->nseg, &g->ps);
     const int64_t Sp = ((int64_t)a->S + 3) / 4 * 4;
     const int64_t ksh = rs_ksize(a->Wi, a->S), ksv = rs_ksize(a->Hi, a->S);
     const double scale = (double)a->Hi / (double)a->S, support = 2.0 * (scale < 1.0 ? 1.0 : scale);
@@ -250,22 +208,9 @@ static int resample_geometry(const ap_crop_resample_args* a, ResampleGeom* g) {
 }
 
 extern "C" int ap_crop_resample_u8(const ap_crop_resample_args* args, ap_stream_t stream) {
-    if (!args) return AP_ERR_NULL;
+    bool empty;
+    if (const int rc = box_check(args, true, &empty); rc != AP_OK || empty) return rc;
     const ap_crop_resample_args& a = *args;
-    if (a.B < 0 || a.Hi <= 0 || a.Wi <= 0 || a.S <= 0) return AP_ERR_SHAPE;
-    if (a.layout != AP_PREP_NCHW && a.layout != AP_PREP_NHWC) return AP_ERR_SHAPE;
-    if (a.B == 0) return AP_OK;
-    if (!a.u8 || !a.out || !a.records) return AP_ERR_NULL;
-    if (reinterpret_cast<uintptr_t>(a.u8) & 15) return AP_ERR_SHAPE;
-    if ((int64_t)a.B * 3 * a.Hi * a.Wi > ((int64_t)1 << 40)) return AP_ERR_SHAPE;
-    if (a.records_host) {
-        for (int64_t i = 0; i < a.B; ++i) {
-            const int* q = a.records_host + i * 8;
-            if (q[2] < 1 || q[3] < 1 || q[0] < 0 || q[1] < 0 || (int64_t)q[0] + q[2] > a.Hi || (int64_t)q[1] + q[3] > a.Wi) return AP_ERR_SHAPE;
-            if (q[4] != 0 && q[4] != 1) return AP_ERR_SHAPE;
-            if (q[5] != AP_RESAMPLE_BILINEAR && q[5] != AP_RESAMPLE_BICUBIC) return AP_ERR_SHAPE;
-        }
-    }
     ResampleGeom g;
     const int lds = resample_geometry(&a, &g);
     if (lds < 0) return AP_ERR_UNSUPPORTED;                       // the tables and one output row's box rows do not fit the LDS budget

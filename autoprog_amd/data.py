@@ -38,8 +38,22 @@ import numpy as np
 import torch
 
 from . import ops
+from .ring import PinnedRing
 
 MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2
+
+
+def _layout(layout):
+    if layout not in ("nchw", "nhwc"):
+        raise ValueError("layout must be nchw or nhwc")
+    return layout
+
+
+def _device_batch(u8, layout, who):
+    """-> (B, H, W) of a uint8 [B,3,H,W] / [B,H,W,3] batch on the device"""
+    if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 4 or not u8.is_cuda:
+        raise ValueError("%s: a uint8 [B,3,H,W] / [B,H,W,3] batch on the device" % who)
+    return (u8.shape[0],) + ((u8.shape[2], u8.shape[3]) if layout == "nchw" else (u8.shape[1], u8.shape[2]))
 
 
 def normalisation_table(mean, std):
@@ -129,7 +143,7 @@ class DeviceBatchPrep:
              aspect = exp(uniform(log 0.3, log 1/0.3)), h = int(round(sqrt(target aspect))), w = int(round(sqrt(target / aspect))),
              accepted if w < W and h < H, at top = randint(0, H - h), left = randint(0, W - w) (inclusive)
     re_prob is a plain attribute (AutoProgDriver sets it per stage from the schedule's `re` list)."""
-    SLOTS = 8
+    SLOTS = PinnedRing.SLOTS
 
     def __init__(self, mean, std, mixup_alpha=0.0, cutmix_alpha=0.0, prob=1.0, switch_prob=0.5, mode="batch", label_smoothing=0.1,
                  num_classes=1000, re_prob=0.0, re_mode="pixel", re_count=1, seed=0, layout="nchw", device="cuda"):
@@ -139,39 +153,23 @@ class DeviceBatchPrep:
             raise ValueError("re_mode must be const, rand or pixel")
         if not 1 <= int(re_count) <= ops.PREP_MAX_BOXES:
             raise ValueError("re_count must be 1..%d" % ops.PREP_MAX_BOXES)
-        if layout not in ("nchw", "nhwc"):
-            raise ValueError("layout must be nchw or nhwc")
         self.mixup_alpha, self.cutmix_alpha, self.prob, self.switch_prob = float(mixup_alpha), float(cutmix_alpha), float(prob), float(switch_prob)
         self.label_smoothing, self.num_classes = float(label_smoothing), int(num_classes)
         self.re_prob, self.re_mode, self.re_count = float(re_prob), re_mode, int(re_count)
-        self.seed, self.layout, self.device = int(seed), layout, torch.device(device)
+        self.seed, self.layout, self.device = int(seed), _layout(layout), torch.device(device)
         self.mix_enabled = self.mixup_alpha > 0 or self.cutmix_alpha > 0
         self.table_cpu = normalisation_table(mean, std)
         self._table = None
         self._np = np.random.RandomState(self.seed & 0xffffffff)
         self._py = random.Random(self.seed)
         self.steps = 0
-        self._B = None
+        self._ring = PinnedRing(self.device)
         self.last = None                       # the decisions of the last draw, for logs and tests
 
-    # ---- the block: ops.PREP_PARAM_WORDS words of parameters, then B * re_count records of ops.PREP_BOX_WORDS words
-    def _alloc(self, B):
-        words = ops.PREP_PARAM_WORDS + B * self.re_count * ops.PREP_BOX_WORDS
-        ring = torch.zeros(self.SLOTS, words, dtype=torch.int32)
-        self._ring = ring.pin_memory() if self.device.type == "cuda" and torch.cuda.is_available() else ring
-        self._dev = [None] * self.SLOTS
-        self._events = [None] * self.SLOTS
-        self._slot, self._B = 0, B
-
     def draw(self, B, H, W):
-        """-> the host block (int32 CPU tensor) of the next step"""
-        if self._B != B:
-            self._alloc(B)
-        self._slot = (self._slot + 1) % self.SLOTS
-        ev = self._events[self._slot]
-        if ev is not None:
-            ev.synchronize()                   # the copy that last read this slot has executed (graph.StepScalars)
-        host = self._ring[self._slot]
+        """-> the host block (int32 CPU tensor) of the next step: ops.PREP_PARAM_WORDS words of parameters, then B * re_count records of
+        ops.PREP_BOX_WORDS words"""
+        host = self._ring.next(ops.PREP_PARAM_WORDS + B * self.re_count * ops.PREP_BOX_WORDS)
         a = host.numpy()
         a[:] = 0
         f, u = a.view(np.float32), a.view(np.uint32)
@@ -233,19 +231,8 @@ class DeviceBatchPrep:
 
     def prep(self, u8):
         """uint8 device batch -> PreparedBatch: draws the step and enqueues the one copy of its block"""
-        if u8.dtype != torch.uint8 or u8.dim() != 4 or not u8.is_cuda:
-            raise ValueError("DeviceBatchPrep.prep: a uint8 [B,3,H,W] / [B,H,W,3] batch on the device")
-        B = u8.shape[0]
-        H, W = (u8.shape[2], u8.shape[3]) if self.layout == "nchw" else (u8.shape[1], u8.shape[2])
-        host = self.draw(B, H, W)
-        dev = self._dev[self._slot]
-        if dev is None:
-            dev = self._dev[self._slot] = torch.empty(host.numel(), dtype=torch.int32, device=u8.device)
-        dev.copy_(host, non_blocking=True)
-        ev = self._events[self._slot]
-        if ev is None:
-            ev = self._events[self._slot] = torch.cuda.Event()
-        ev.record()
+        host = self.draw(*_device_batch(u8, self.layout, "DeviceBatchPrep.prep"))
+        dev = self._ring.send(u8.device)
         return PreparedBatch(u8.contiguous(), self.layout, self.table(), dev, host, self.mix_enabled, self.re_count, self.re_mode,
                              self.last["lam"], self)
 
@@ -275,40 +262,26 @@ class DeviceRandomResizedCrop:
     ops.RESAMPLE_BILINEAR / RESAMPLE_BICUBIC.  A fixed filter draws nothing more; "random" is timm 0.4.5's
     `random.choice(self.interpolation)` inside `__call__`, after `get_params` and before the flip transform: per image the draw order
     is box, then choice((bilinear, bicubic)), then flip."""
-    SLOTS = 8
+    SLOTS = PinnedRing.SLOTS
     FILTERS = {"bilinear": ops.RESAMPLE_BILINEAR, "bicubic": ops.RESAMPLE_BICUBIC}
 
     def __init__(self, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), hflip=0.5, size=None, seed=0, layout="nchw", device="cuda",
                  interpolation=None):
-        if layout not in ("nchw", "nhwc"):
-            raise ValueError("layout must be nchw or nhwc")
         self._filter(interpolation, True)
         self.interpolation = interpolation
         self.scale, self.ratio, self.hflip = tuple(scale), tuple(ratio), float(hflip)
-        self.size, self.seed, self.layout, self.device = size, int(seed), layout, torch.device(device)
+        self.size, self.seed, self.layout, self.device = size, int(seed), _layout(layout), torch.device(device)
         self._py = random.Random(self.seed)
-        self._B = None
+        self._ring = PinnedRing(self.device)
         self.last = None
         self.last_extents = None               # the (eh, ew) of every image of the last draw or centre crop (DeviceLabelMapCrop reads both)
 
-    def _alloc(self, B):
-        ring = torch.zeros(self.SLOTS, max(B, 1) * ops.CROP_RECORD_WORDS, dtype=torch.int32)
-        self._ring = ring.pin_memory() if self.device.type == "cuda" and torch.cuda.is_available() else ring
-        self._dev = [None] * self.SLOTS
-        self._events = [None] * self.SLOTS
-        self._slot, self._B = 0, B
-
     def _next(self, B):
-        """-> the next slot's host block as a zeroed [B, 8] int32 array"""
-        if self._B != B:
-            self._alloc(B)
-        self._slot = (self._slot + 1) % self.SLOTS
-        ev = self._events[self._slot]
-        if ev is not None:
-            ev.synchronize()                   # the copy that last read this slot has executed
-        a = self._ring[self._slot].numpy().reshape(max(B, 1), ops.CROP_RECORD_WORDS)
+        """-> the next slot's host block, zeroed, and its view as a [B, 8] int32 array"""
+        host = self._ring.next(max(B, 1) * ops.CROP_RECORD_WORDS)
+        a = host.numpy().reshape(max(B, 1), ops.CROP_RECORD_WORDS)
         a[:] = 0
-        return a
+        return host, a
 
     @staticmethod
     def _extents(B, H, W, extents):
@@ -356,7 +329,7 @@ class DeviceRandomResizedCrop:
         """-> the host block (int32 CPU tensor, B records of 8 words) of the next crop: one box and one flip per image, and with
         interpolation "random" one filter"""
         ext = self.last_extents = self._extents(B, H, W, extents)
-        a = self._next(B)
+        host, a = self._next(B)
         rnd, hflip = self._py.random, self.hflip
         filt = self._filter(self.interpolation, True)
         if filt == 0:
@@ -371,36 +344,24 @@ class DeviceRandomResizedCrop:
             self.last = [self._box(eh, ew) + (int(rnd() < hflip), filt) for eh, ew in ext]
         if B:
             a[:B, :5 + (filt != 0)] = self.last    # (one assignment: a per-image write costs more host time than the draw)
-        return self._ring[self._slot]
+        return host
 
     def center_records(self, B, H, W, crop_pct=0.875, extents=None, interpolation=None):
         """-> the host block of the central square boxes of side int(round(crop_pct * min(eh, ew))), no flip; nothing is drawn.
         interpolation: None (the object's setting), "bilinear" or "bicubic"; "random" is refused, here and as the object's setting"""
         filt = self._filter(self.interpolation if interpolation is None else interpolation, False)
         ext = self.last_extents = self._extents(B, H, W, extents)
-        a = self._next(B)
+        host, a = self._next(B)
         self.last = []
         for eh, ew in ext:
             side = min(max(int(round(crop_pct * min(eh, ew))), 1), min(eh, ew))
             self.last.append(((eh - side) // 2, (ew - side) // 2, side, side, 0) + ((filt,) if filt else ()))
         if B:
             a[:B, :5 + (filt != 0)] = self.last
-        return self._ring[self._slot]
-
-    def _canvas(self, u8):
-        if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 4 or not u8.is_cuda:
-            raise ValueError("DeviceRandomResizedCrop: a uint8 [B,3,H,W] / [B,H,W,3] batch on the device")
-        return (u8.shape[0],) + ((u8.shape[2], u8.shape[3]) if self.layout == "nchw" else (u8.shape[1], u8.shape[2]))
+        return host
 
     def _launch(self, u8, size, host, antialias):
-        dev = self._dev[self._slot]
-        if dev is None:
-            dev = self._dev[self._slot] = torch.empty(host.numel(), dtype=torch.int32, device=u8.device)
-        dev.copy_(host, non_blocking=True)
-        ev = self._events[self._slot]
-        if ev is None:
-            ev = self._events[self._slot] = torch.cuda.Event()
-        ev.record()
+        dev = self._ring.send(u8.device)
         return (ops.crop_resample_u8 if antialias else ops.crop_resize_u8)(u8.contiguous(), size, dev, layout=self.layout, host_records=host)
 
     def _size(self, size):
@@ -413,7 +374,7 @@ class DeviceRandomResizedCrop:
         """uint8 device batch -> uint8 [B,3,S,S] / [B,S,S,3]: draws a box and a flip per image, one copy and one launch.  extents: optional
         integer [B,2] (eh, ew) for images that fill only the top-left part of a padded canvas (default: the whole canvas)"""
         size = self._size(size)
-        B, H, W = self._canvas(u8)
+        B, H, W = _device_batch(u8, self.layout, "DeviceRandomResizedCrop")
         return self._launch(u8, size, self.draw(B, H, W, extents), self.interpolation is not None)
 
     def center(self, u8, size, crop_pct=0.875, extents=None, interpolation=None):
@@ -423,7 +384,7 @@ class DeviceRandomResizedCrop:
         floor(size / crop_pct) and then cuts the central size x size; this cuts the central square of side round(crop_pct * min(eh, ew))
         and resizes it to size x size"""
         size = self._size(size)
-        B, H, W = self._canvas(u8)
+        B, H, W = _device_batch(u8, self.layout, "DeviceRandomResizedCrop")
         host = self.center_records(B, H, W, crop_pct, extents, interpolation)
         return self._launch(u8, size, host, (self.interpolation if interpolation is None else interpolation) is not None)
 
@@ -462,7 +423,7 @@ class DeviceLabelMapCrop:
     into this object's own ring of pinned blocks, as the crop's do.  The target of a (B, r) is kept and refilled in place by the next call
     (as prog.teacher.TeacherLabeler's).  k <= 8: the mix-token class row of the loss carries 2 k pairs.  Scores are written raw; smoothing
     is the target's attribute, applied where the loss reads the pairs.  Mixup / CutMix of token labels is not done."""
-    SLOTS = 8
+    SLOTS = PinnedRing.SLOTS
 
     def __init__(self, k=8, smoothing=0.1, num_classes=1000):
         if not 1 <= int(k) <= ops.LABEL_MAP_MAX_K:
@@ -470,29 +431,17 @@ class DeviceLabelMapCrop:
         if not 1 <= int(num_classes) <= 65536:
             raise ValueError("DeviceLabelMapCrop: num_classes must be 1 .. 65536")
         self.k, self.smoothing, self.num_classes = int(k), float(smoothing), int(num_classes)
-        self._B = None
+        self._ring = PinnedRing("cuda")
         self._targets = {}                     # (B, r) -> the target of that configuration, refilled by every call
         self.last = None                       # the records of the last call: (x1, y1, x2, y2, flip) per image, as fp32 values
 
-    def _alloc(self, B, pinned):
-        ring = torch.zeros(self.SLOTS, max(B, 1) * ops.LABEL_MAP_BOX_WORDS, dtype=torch.float32)
-        self._ring = ring.pin_memory() if pinned else ring
-        self._dev = [None] * self.SLOTS
-        self._events = [None] * self.SLOTS
-        self._slot, self._B = 0, B
-
-    def records(self, crop, B, Hm, Wm, pinned=False):
+    def records(self, crop, B, Hm, Wm):
         """-> the host block (fp32 CPU tensor, B records of 8 words) of the boxes `crop` drew last, in the pixel units of Hm x Wm maps"""
         last, ext = getattr(crop, "last", None), getattr(crop, "last_extents", None)
         if last is None or ext is None or len(last) != B or len(ext) != B:
             raise ValueError("DeviceLabelMapCrop: crop.last does not belong to a batch of %d images (crop the batch first)" % B)
-        if self._B != B:
-            self._alloc(B, pinned)
-        self._slot = (self._slot + 1) % self.SLOTS
-        ev = self._events[self._slot]
-        if ev is not None:
-            ev.synchronize()                   # the copy that last read this slot has executed
-        a = self._ring[self._slot].numpy().reshape(max(B, 1), ops.LABEL_MAP_BOX_WORDS)
+        host = self._ring.next(max(B, 1) * ops.LABEL_MAP_BOX_WORDS, torch.float32)
+        a = host.numpy().reshape(max(B, 1), ops.LABEL_MAP_BOX_WORDS)
         a[:] = 0
         if B:
             box = np.asarray([rec[:5] for rec in last], dtype=np.float64)           # top, left, h, w, flip
@@ -501,7 +450,7 @@ class DeviceLabelMapCrop:
             a[:B, 2], a[:B, 3] = (box[:, 1] + box[:, 3]) * Wm / e[:, 1], (box[:, 0] + box[:, 2]) * Hm / e[:, 0]
             a[:B, 4] = box[:, 4]
         self.last = [tuple(float(v) for v in row[:5]) for row in a[:B]]
-        return self._ring[self._slot]
+        return host
 
     def target(self, stored, crop, r, out=None):
         """stored: the StoredLabelMaps of the batch `crop` cropped last; r: the resolution it was cropped to.  -> the
@@ -516,15 +465,8 @@ class DeviceLabelMapCrop:
         P = int(r) // 16
         if P < 1:
             raise ValueError("DeviceLabelMapCrop.target: r = %d has no token grid (r // 16 < 1)" % int(r))
-        host = self.records(crop, B, Hm, Wm, pinned=True)
-        dev = self._dev[self._slot]
-        if dev is None:
-            dev = self._dev[self._slot] = torch.empty(host.numel(), dtype=torch.float32, device=stored.scores.device)
-        dev.copy_(host, non_blocking=True)
-        ev = self._events[self._slot]
-        if ev is None:
-            ev = self._events[self._slot] = torch.cuda.Event()
-        ev.record()
+        host = self.records(crop, B, Hm, Wm)
+        dev = self._ring.send(stored.scores.device)
         key, shape = (B, int(r)), (B, 2 + P * P, self.k)
         if out is None:
             out = self._targets.get(key)
@@ -611,19 +553,17 @@ class DeviceRandAugment:
     the last draw: per image a list of n_layers tuples (op, filter, int argument, factor, matrix) with op one of ops.RA_*.
     A spec of "" or None disables the object: `aug(u8)` then returns its input and draws nothing.
     Not implemented: op weights (w), mstd = inf (uniform magnitudes), the constant-pixel translate ops, AutoAugment and AugMix policies."""
-    SLOTS = 8
+    SLOTS = PinnedRing.SLOTS
 
     def __init__(self, spec="rand-m9-mstd0.5-inc1", mean=IMAGENET_MEAN, seed=0, layout="nchw", device="cuda"):
-        if layout not in ("nchw", "nhwc"):
-            raise ValueError("layout must be nchw or nhwc")
         self.prob = 0.5
         self.magnitude, self.magnitude_std, self.n_layers, self.increasing = int(_RA_MAX_LEVEL), 0.0, 2, False
         self.set_spec(spec)
         self.fill = tuple(min(255, round(255 * x)) for x in mean)
-        self.seed, self.layout, self.device = int(seed), layout, torch.device(device)
+        self.seed, self.layout, self.device = int(seed), _layout(layout), torch.device(device)
         self._np = np.random.RandomState(self.seed & 0xffffffff)
         self._py = random.Random(self.seed)
-        self._key = None
+        self._ring = PinnedRing(self.device)
         self._buffers = {}
         self.last = None
 
@@ -707,30 +647,17 @@ class DeviceRandAugment:
         flat = [(int(a[i, 0]), int(a[i, 1]), int(a[i, 2]), float(f[i]), tuple(float(v) for v in m[i])) for i in range(B * n_layers)]
         return [flat[b * n_layers:(b + 1) * n_layers] for b in range(B)]
 
-    def _alloc(self, B, n):
-        ring = torch.zeros(self.SLOTS, max(B * n, 1) * ops.RANDAUG_RECORD_WORDS, dtype=torch.int32)
-        self._ring = ring.pin_memory() if self.device.type == "cuda" and torch.cuda.is_available() else ring
-        self._dev = [None] * self.SLOTS
-        self._events = [None] * self.SLOTS
-        self._slot, self._key = 0, (B, n)
-
     def draw(self, B, S):
         """-> the host block (int32 CPU tensor, B x n_layers records of 16 words) of the next call on B images of S x S pixels"""
         n = int(self.n_layers)
         if not 1 <= n <= ops.RANDAUG_MAX_LAYERS:
             raise ValueError("DeviceRandAugment: n_layers must be 1..%d" % ops.RANDAUG_MAX_LAYERS)
-        if self._key != (B, n):
-            self._alloc(B, n)
-        self._slot = (self._slot + 1) % self.SLOTS
-        ev = self._events[self._slot]
-        if ev is not None:
-            ev.synchronize()                   # the copy that last read this slot has executed
+        host = self._ring.next(max(B * n, 1) * ops.RANDAUG_RECORD_WORDS)
         # one call for the batch: RandomState.choice(15, B n) is the stream of B calls of choice(15, n) (32 bits and one rejection test
         # per element either way), without a numpy call per image on the host's critical path
         picks = self._np.choice(len(RANDAUG_OPS), B * n).reshape(B, n).tolist() if B else []
         draw_op = self._draw_op
         self.last = [[draw_op(RANDAUG_OPS[k], S) for k in image] for image in picks]
-        host = self._ring[self._slot]
         self.pack(self.last, host.numpy())
         return host
 
@@ -738,9 +665,7 @@ class DeviceRandAugment:
         """uint8 device batch -> the augmented uint8 batch: draws n_layers ops per image, one copy and n_layers launches"""
         if not self.enabled:
             return u8
-        if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 4 or not u8.is_cuda:
-            raise ValueError("DeviceRandAugment: a uint8 [B,3,S,S] / [B,S,S,3] batch on the device")
-        B, S, W = (u8.shape[0], u8.shape[2], u8.shape[3]) if self.layout == "nchw" else (u8.shape[0], u8.shape[1], u8.shape[2])
+        B, S, W = _device_batch(u8, self.layout, "DeviceRandAugment")
         if S != W:
             raise ValueError("DeviceRandAugment: square images (the crop's output), got %s" % (tuple(u8.shape),))
         key = (tuple(u8.shape), u8.device)
@@ -751,12 +676,5 @@ class DeviceRandAugment:
                                   torch.empty_like(u8, memory_format=torch.contiguous_format))
         out, scratch = self._buffers[key]
         host = self.draw(B, S)
-        dev = self._dev[self._slot]
-        if dev is None:
-            dev = self._dev[self._slot] = torch.empty(host.numel(), dtype=torch.int32, device=u8.device)
-        dev.copy_(host, non_blocking=True)
-        ev = self._events[self._slot]
-        if ev is None:
-            ev = self._events[self._slot] = torch.cuda.Event()
-        ev.record()
+        dev = self._ring.send(u8.device)
         return ops.randaug_u8(u8.contiguous(), dev, self.n_layers, self.fill, layout=self.layout, out=out, scratch=scratch, host_records=host)

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .ring import PinnedRing
 
 
 class StepScalars:
@@ -33,35 +34,31 @@ class StepScalars:
          int32 [0..3]  mix-token box on the token-label grid: bbx1, bbx2, bby1, bby2 (rows [bbx1, bbx2), columns [bby1, bby2))
          fp32  [4]     lam of the loss = 1 - box area / N
          fp32  [5..7]  learning rate, 1 - beta1^t, sqrt(1 - beta2^t)
-       The host side is a RING of pinned 64-byte slots: push() is one asynchronous copy of the slot being prepared, and a pinned
-       copy reads its source when it EXECUTES on the GPU, not when it is enqueued -- with one slot the host, which runs many replays
-       ahead of the GPU (a replay costs it tens of microseconds, the step milliseconds), would overwrite step t's scalars with
-       step t + k's before the copy of step t has run.  begin() takes the next slot and waits for the event recorded
-       behind that slot's last copy, so the host runs at most SLOTS - 1 steps ahead of the copies."""
-    SLOTS = 8
+       The host side is a ring.PinnedRing of 64-byte slots: push() is one asynchronous copy of the slot being prepared into the one
+       device buffer, and begin() takes the next slot, so the host, which runs many replays ahead of the GPU (a replay costs it tens
+       of microseconds, the step milliseconds), never overwrites step t's scalars before the copy of step t has run."""
+    SLOTS = PinnedRing.SLOTS
 
     def __init__(self, device):
-        self.ring = torch.zeros(self.SLOTS, 16, dtype=torch.int32).pin_memory()
-        self.events = [None] * self.SLOTS
-        self.slot = 0
+        self._ring = PinnedRing(device)
         self.dev = torch.zeros(16, dtype=torch.int32, device=device)
-        self._bind()
+        self._take()
         self._hf[4] = 1.0
         self.push()
 
-    def _bind(self):
-        self.host = self.ring[self.slot]
+    def _take(self):
+        self.host = self._ring.next(16)
         self._hf = self.host.view(torch.float32)
+
+    @property
+    def slot(self):
+        return self._ring.slot
 
     def begin(self):
         """start preparing a step: the next slot of the ring, once the copy that last read it has executed; the values of the
         previous step carry over (a caller may set only the box or only the optimizer scalars)"""
         prev = self.host
-        self.slot = (self.slot + 1) % self.SLOTS
-        ev = self.events[self.slot]
-        if ev is not None:
-            ev.synchronize()
-        self._bind()
+        self._take()
         self.host.copy_(prev)
 
     @property
@@ -91,11 +88,7 @@ class StepScalars:
 
     def push(self):
         self.dev.copy_(self.host, non_blocking=True)
-        if self.dev.is_cuda:
-            ev = self.events[self.slot]
-            if ev is None:
-                ev = self.events[self.slot] = torch.cuda.Event()
-            ev.record()
+        self._ring.record()
 
 
 class DeviceBox:

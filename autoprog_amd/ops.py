@@ -1107,6 +1107,23 @@ def conv3x3_c64_wgrad(x, dy, dw, bn_in=None):
 
 
 # ------------------------------------------------------------------------------------- a loader's uint8 batch -> the stem's input
+def _u8_batch(what, u8, layout):
+    """-> (B, H, W) of a uint8 batch in `layout`: [B,3,H,W] ("nchw") or [B,H,W,3] ("nhwc")"""
+    _req(u8, torch.uint8, "u8")
+    if layout not in ("nchw", "nhwc") or u8.dim() != 4 or u8.shape[1 if layout == "nchw" else 3] != 3:
+        raise AutoProgHipError("%s: a uint8 [B,3,H,W] (nchw) or [B,H,W,3] (nhwc) batch, got %s as %s" % (what, tuple(u8.shape), layout))
+    return (u8.shape[0],) + ((u8.shape[2], u8.shape[3]) if layout == "nchw" else (u8.shape[1], u8.shape[2]))
+
+
+def _host_records(what, records, host, words, dtype, name="records"):
+    """`records` (on the device) holds at least `words` words of dtype, and so does `host`, where given: a CPU, contiguous copy of the
+    same dtype -> its address, or None"""
+    _req(records, dtype, name)
+    if records.numel() < words or (host is not None and (host.is_cuda or host.dtype != dtype or not host.is_contiguous() or host.numel() < words)):
+        raise AutoProgHipError("%s: %s must hold %d %s words (and so must a CPU, contiguous host copy of that dtype)" % (what, name, words, dtype))
+    return None if host is None else host.data_ptr()
+
+
 PREP_PARAM_WORDS, PREP_BOX_WORDS = 16, 8          # the device block of ap_input_prep: 16 words of per-step parameters, then 8 per box record
 _PREP_ERASE = {"const": 0, "rand": 1, "pixel": 2}
 
@@ -1118,13 +1135,10 @@ def input_prep(u8, size, out="s2d16", table=None, params=None, layout="nchw", mi
     (include/autoprog_hip.h, ap_input_prep).  `params`: int32 device tensor, PREP_PARAM_WORDS words of per-step parameters followed by
     B * n_boxes box records of PREP_BOX_WORDS words (data.DeviceBatchPrep fills it); None: no mix, no erase.  `mix` False ignores the
     block's mix mode.  `host_block`: a CPU copy of `params` whose records are checked against the image before the launch."""
-    _req(u8, torch.uint8, "u8"); _req(table, torch.float32, "table")
-    if u8.dim() != 4 or u8.shape[1 if layout == "nchw" else 3] != 3 or layout not in ("nchw", "nhwc"):
-        raise AutoProgHipError("input_prep: a uint8 [B,3,H,W] (nchw) or [B,H,W,3] (nhwc) batch, got %s as %s" % (tuple(u8.shape), layout))
+    B, Hi, Wi = _u8_batch("input_prep", u8, layout)
+    _req(table, torch.float32, "table")
     if out not in ("s2d16", "nhwc") or erase_mode not in _PREP_ERASE or tuple(table.shape) != (3, 256):
         raise AutoProgHipError("input_prep: out %r, erase_mode %r, table %s" % (out, erase_mode, tuple(table.shape)))
-    B = u8.shape[0]
-    Hi, Wi = (u8.shape[2], u8.shape[3]) if layout == "nchw" else (u8.shape[1], u8.shape[2])
     a = InputPrepArgs()
     a.u8, a.in_layout, a.B, a.Hi, a.Wi = u8.data_ptr(), int(layout == "nhwc"), B, Hi, Wi
     a.out_layout, a.Ho, a.Wo = int(out == "nhwc"), size, size
@@ -1153,17 +1167,10 @@ CROP_RECORD_WORDS = 8                             # a record of ap_crop_resize_u
 
 
 def _crop_launch(what, args_type, entry, u8, size, records, layout, out, host_records):
-    _req(u8, torch.uint8, "u8"); _req(records, torch.int32, "records")
-    if layout not in ("nchw", "nhwc") or u8.dim() != 4 or u8.shape[1 if layout == "nchw" else 3] != 3:
-        raise AutoProgHipError("%s: a uint8 [B,3,H,W] (nchw) or [B,H,W,3] (nhwc) batch, got %s as %s" % (what, tuple(u8.shape), layout))
-    B, size = u8.shape[0], int(size)
-    Hi, Wi = (u8.shape[2], u8.shape[3]) if layout == "nchw" else (u8.shape[1], u8.shape[2])
+    (B, Hi, Wi), size = _u8_batch(what, u8, layout), int(size)
     if size < 1:
         raise AutoProgHipError("%s: size %d" % (what, size))
-    words = B * CROP_RECORD_WORDS
-    if records.numel() < words or (host_records is not None and (host_records.is_cuda or host_records.dtype != torch.int32
-                                                                 or not host_records.is_contiguous() or host_records.numel() < words)):
-        raise AutoProgHipError("%s: %d images need %d int32 words of records (and the same in a CPU int32 host copy)" % (what, B, words))
+    host = _host_records(what, records, host_records, B * CROP_RECORD_WORDS, torch.int32)
     shape = (B, 3, size, size) if layout == "nchw" else (B, size, size, 3)
     if out is None:
         out = torch.empty(shape, dtype=torch.uint8, device=u8.device)
@@ -1171,9 +1178,7 @@ def _crop_launch(what, args_type, entry, u8, size, records, layout, out, host_re
         raise AutoProgHipError("%s: out must be %s, got %s" % (what, shape, tuple(out.shape)))
     a = args_type()
     a.u8, a.layout, a.B, a.Hi, a.Wi = u8.data_ptr(), int(layout == "nhwc"), B, Hi, Wi
-    a.out, a.S, a.records = out.data_ptr(), size, records.data_ptr()
-    if host_records is not None:
-        a.records_host = host_records.data_ptr()
+    a.out, a.S, a.records, a.records_host = out.data_ptr(), size, records.data_ptr(), host
     check(entry(ctypes.byref(a), _stream()), "ap_" + what)
     return out
 
@@ -1211,18 +1216,13 @@ def randaug_u8(u8, records, n_layers, fill, layout="nchw", out=None, scratch=Non
     (include/autoprog_hip.h, ap_randaug_u8).  `fill`: the (R, G, B) bytes of pixels an affine op maps from outside the image.  The input is
     not modified.  `out` / `scratch`: uint8 device tensors of the input's shape to write into (scratch is only used with n_layers > 1;
     allocated when not given); `host_records`: a CPU copy of `records` whose op and filter codes are checked before the launch."""
-    _req(u8, torch.uint8, "u8"); _req(records, torch.int32, "records")
-    if layout not in ("nchw", "nhwc") or u8.dim() != 4 or u8.shape[1 if layout == "nchw" else 3] != 3 or u8.shape[2] != u8.shape[3 if layout == "nchw" else 1]:
-        raise AutoProgHipError("randaug_u8: a square uint8 [B,3,S,S] (nchw) or [B,S,S,3] (nhwc) batch, got %s as %s" % (tuple(u8.shape), layout))
-    B, S, n_layers = u8.shape[0], u8.shape[2], int(n_layers)
+    (B, S, W), n_layers = _u8_batch("randaug_u8", u8, layout), int(n_layers)
+    if S != W:
+        raise AutoProgHipError("randaug_u8: square images, got %s as %s" % (tuple(u8.shape), layout))
     fill = tuple(int(v) for v in fill)
     if not 1 <= n_layers <= RANDAUG_MAX_LAYERS or len(fill) != 3 or min(fill) < 0 or max(fill) > 255:
         raise AutoProgHipError("randaug_u8: n_layers 1..%d and three fill bytes, got %d and %s" % (RANDAUG_MAX_LAYERS, n_layers, fill))
-    words = B * n_layers * RANDAUG_RECORD_WORDS
-    if records.numel() < words or (host_records is not None and (host_records.is_cuda or host_records.dtype != torch.int32
-                                                                 or not host_records.is_contiguous() or host_records.numel() < words)):
-        raise AutoProgHipError("randaug_u8: %d images x %d layers need %d int32 words of records (and the same in a CPU int32 host copy)"
-                               % (B, n_layers, words))
+    host = _host_records("randaug_u8", records, host_records, B * n_layers * RANDAUG_RECORD_WORDS, torch.int32)
     if out is None:
         out = torch.empty_like(u8)
     elif tuple(_req(out, torch.uint8, "out").shape) != tuple(u8.shape):
@@ -1237,8 +1237,7 @@ def randaug_u8(u8, records, n_layers, fill, layout="nchw", out=None, scratch=Non
     a.u8, a.layout, a.B, a.S = u8.data_ptr(), int(layout == "nhwc"), B, S
     a.out, a.records, a.n_layers = out.data_ptr(), records.data_ptr(), n_layers
     a.fill[0], a.fill[1], a.fill[2] = fill
-    if host_records is not None:
-        a.records_host = host_records.data_ptr()
+    a.records_host = host
     check(lib.ap_randaug_u8(ctypes.byref(a), _stream()), "ap_randaug_u8")
     return out
 
@@ -1266,29 +1265,24 @@ def label_map_crop(scores, classes, labels, boxes, P, K, C, out=None, dropped=No
     `out`: (idx int32, val fp32), both [B, 2 + P P, K] and contiguous, to write into; `dropped`: fp32 [B, 1 + P P] that receives the
     score mass of the classes beyond K per bin; `host_records`: a CPU copy of `boxes`, validated before the launch.  -> (idx, val)"""
     _label_map_view(scores, "scores"); _label_map_view(classes, "classes")
-    _req(labels, torch.int64, "labels"); _req(boxes, torch.float32, "boxes")
+    _req(labels, torch.int64, "labels")
     if scores.dtype not in (torch.float16, torch.float32) or classes.dtype not in (scores.dtype, torch.int32):
         raise AutoProgHipError("label_map_crop: fp16 or fp32 scores, classes in the same dtype or int32 (got %s, %s)" % (scores.dtype, classes.dtype))
     B, Kin, Hm, Wm = scores.shape
     P, K, C = int(P), int(K), int(C)
     if tuple(classes.shape) != (B, Kin, Hm, Wm) or labels.numel() != B or classes.device != scores.device:
         raise AutoProgHipError("label_map_crop: scores and classes [B,Kin,Hm,Wm] on one device, labels [B]")
-    words = B * LABEL_MAP_BOX_WORDS
-    if boxes.numel() < words or (host_records is not None and (host_records.is_cuda or host_records.dtype != torch.float32
-                                                               or not host_records.is_contiguous() or host_records.numel() < words)):
-        raise AutoProgHipError("label_map_crop: %d images need %d fp32 words of box records (and the same in a CPU fp32 host copy)" % (B, words))
+    a = LabelMapCropArgs()
+    a.boxes_host = _host_records("label_map_crop", boxes, host_records, B * LABEL_MAP_BOX_WORDS, torch.float32, "boxes")
     shape = (B, 2 + P * P, K)
     if out is None:
         out = (torch.empty(shape, dtype=torch.int32, device=scores.device), torch.empty(shape, dtype=torch.float32, device=scores.device))
     idx, val = out
     if tuple(_req(idx, torch.int32, "idx").shape) != shape or tuple(_req(val, torch.float32, "val").shape) != shape:
         raise AutoProgHipError("label_map_crop: out must be (int32, fp32) tensors of shape %s" % (shape,))
-    a = LabelMapCropArgs()
     a.scores, a.score_dtype, a.score_stride = scores.data_ptr(), int(scores.dtype == torch.float32), scores.stride(0) if B else 0
     a.classes, a.class_dtype, a.class_stride = classes.data_ptr(), int(classes.dtype == torch.int32), classes.stride(0) if B else 0
     a.labels, a.boxes, a.idx, a.val = labels.data_ptr(), boxes.data_ptr(), idx.data_ptr(), val.data_ptr()
-    if host_records is not None:
-        a.boxes_host = host_records.data_ptr()
     if dropped is not None:
         if tuple(_req(dropped, torch.float32, "dropped").shape) != (B, 1 + P * P):
             raise AutoProgHipError("label_map_crop: dropped must be fp32 [%d, %d]" % (B, 1 + P * P))

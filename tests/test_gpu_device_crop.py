@@ -57,6 +57,13 @@ def test_identity_and_flip_are_the_slice(layout):
     t = torch.from_numpy(u8)
     sl = t[:, :, 7:31, 13:37] if layout == "nchw" else t[:, 7:31, 13:37]
     assert torch.equal(got[0], sl[0]) and torch.equal(got[1], sl[1].flip(2 if layout == "nchw" else 1))
+    # one 5 x 7 image: a batch of 105 bytes, more than 16 and no multiple of 16, and the box ends on its last byte -- the 16-byte load
+    # that would cross the end of the batch is the one that goes byte by byte
+    u8 = _canvas(1, 5, 7, layout, 3)
+    src = _hwc(u8, layout)[0, 2:5, 4:7]
+    for flip in (0, 1):
+        got = _hwc(_run(u8, 3, [(2, 4, 3, 3, flip)], layout), layout)[0]
+        assert np.array_equal(got, src[:, ::-1] if flip else src), flip
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)

@@ -52,6 +52,13 @@ def test_identity_and_flip_are_the_slice(layout, filt):
     got = _hwc(_run(u8, 24, _with([(7, 13, 24, 24, 0), (7, 13, 24, 24, 1)], filt), layout), layout)
     sl = _hwc(u8, layout)[:, 7:31, 13:37]
     assert np.array_equal(got[0], sl[0]) and np.array_equal(got[1], sl[1][:, ::-1])
+    # one 5 x 7 image: a batch of 105 bytes, more than 16 and no multiple of 16, and the box ends on its last byte -- the 16-byte load
+    # that would cross the end of the batch is the one that goes byte by byte
+    u8 = _canvas(1, 5, 7, layout, 3)
+    src = _hwc(u8, layout)[0, 2:5, 4:7]
+    for flip in (0, 1):
+        got = _hwc(_run(u8, 3, [(2, 4, 3, 3, flip, filt)], layout), layout)[0]
+        assert np.array_equal(got, src[:, ::-1] if flip else src), flip
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)

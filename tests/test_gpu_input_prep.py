@@ -43,9 +43,14 @@ def table():
     return ((torch.arange(256, dtype=torch.float32).view(1, 256) - mean.view(3, 1)) / std.view(3, 1)).contiguous()
 
 
+def batch_hw(n, h, w, seed=0):
+    """uint8 NCHW [n,3,h,w]"""
+    return torch.randint(0, 256, (n, 3, h, w), dtype=torch.uint8, generator=torch.Generator().manual_seed(seed + h))
+
+
 def batch(hi, seed=0):
     """uint8 NCHW, every byte value present"""
-    return torch.randint(0, 256, (B, 3, hi, hi), dtype=torch.uint8, generator=torch.Generator().manual_seed(seed + hi))
+    return batch_hw(B, hi, hi, seed)
 
 
 def normalised(u8):
@@ -112,19 +117,24 @@ def run(ops, u8, li, lo, ho, blk=None, **kw):
 
 
 # ------------------------------------------------------------------------------------------ 1. plain
-@pytest.mark.parametrize("li,lo,hi,ho", CASES, ids=IDS)
-def test_plain_is_the_existing_resize_on_the_normalised_tensor(ops, li, lo, hi, ho):
-    u8 = batch(hi)
+# every batch of SIZES is a multiple of 16 bytes.  One 5 x 7 image is 105: more than 16 and no multiple of it, so the last 16-byte chunk
+# the staging reads crosses the end of the batch and goes byte by byte
+PLAIN = [(li, lo, B, hi, hi, ho) for li, lo, hi, ho in CASES] + [(li, lo, 1, 5, 7, 6) for li in ("nchw", "nhwc") for lo in ("s2d16", "nhwc")]
+
+
+@pytest.mark.parametrize("li,lo,n,hi,wi,ho", PLAIN, ids=IDS + ["%s-%s-5x7-6" % c[:2] for c in PLAIN[len(CASES):]])
+def test_plain_is_the_existing_resize_on_the_normalised_tensor(ops, li, lo, n, hi, wi, ho):
+    u8 = batch_hw(n, hi, wi)
     x = normalised(u8)                                          # on the CPU: no GPU division enters the comparison
     y = run(ops, u8, li, lo, ho)
     old = ops.resize_bilinear_s2d16(dev(x), ho) if lo == "s2d16" else ops.resize_bilinear_nhwc(dev(x), ho)
-    assert y.dtype == torch.bfloat16 and tuple(y.shape) == (B, 3, ho, ho)
+    assert y.dtype == torch.bfloat16 and tuple(y.shape) == (n, 3, ho, ho)
     assert torch.equal(y, to_nchw(old, lo)), "a run fed uint8 and a run fed fp32 are not the same run"
     ref = F.interpolate(x, size=(ho, ho), mode="bilinear", align_corners=False)
     r = ratio(y, ref)
-    print("plain %s %s %d->%d: worst err / ulp %.4f" % (li, lo, hi, ho, r))
+    print("plain %s %s %dx%d->%d: worst err / ulp %.4f" % (li, lo, hi, wi, ho, r))
     assert r <= 1.01
-    if hi == ho:
+    if hi == wi == ho:
         assert torch.equal(y, ref.to(torch.bfloat16))
 
 
