@@ -926,6 +926,38 @@ class AddPosFn(torch.autograd.Function):
         return dyc, dpos
 
 
+def ce_rows(x2d):
+    """logits [M, C] as the soft-target CE wrappers of ops take them.  Those wrappers require a CONTIGUOUS tensor and read ld from its shape,
+    so the rows are used as they are only when they are contiguous with ld == C; anything else -- a padded view, as linear() returns it,
+    included -- is copied into a zero-filled [M, round_up(C, 8)] buffer.  (ops.padded_view_rows is the other rule, for the entry points
+    that read a padded view in place.)"""
+    M, C = x2d.shape
+    ld = ops.round_up(C, 8)
+    if ld == C and x2d.is_contiguous():
+        return x2d
+    xp = torch.zeros((M, ld), dtype=BF16, device=x2d.device)
+    xp[:, :C] = x2d
+    return xp
+
+
+def mix_args(lam, B):
+    """lam of a batch of B images mixed with its reverse -> the mix_lam / mix_batches / mix_lam_ptr of its CE launch, whose target is
+    lam * t[b] + (1 - lam) * t[B-1-b].  An object with `lam_ptr` (graph.StepScalars, data.MixedLabelTarget) keeps lam in device memory: no
+    host decision, the kernel always blends (lam = 1 blends nothing: lam t + 0 t' = t exactly).  A host lam of 1 launches unmixed; the
+    kernels read mix_lam only where mix_batches > 0."""
+    if hasattr(lam, "lam_ptr"):
+        return dict(mix_lam=1.0, mix_batches=B, mix_lam_ptr=lam.lam_ptr)
+    return dict(mix_lam=lam, mix_batches=B if lam < 1 else 0, mix_lam_ptr=None)
+
+
+def _scaled_grads(g, C, *saved):
+    """the backward of the loss Functions below: their forward kernels left d(loss)/d(logits) behind, so each saved gradient only takes
+    the incoming scalar (one ops.row_scale) and loses its padding columns"""
+    gs = g.reshape(1).float().contiguous()
+    outs = [ops.row_scale(d, gs, d.shape[0]) for d in saved]
+    return [out if out.shape[1] == C else out[:, :C] for out in outs]
+
+
 class SoftTargetCEFn(torch.autograd.Function):
     """mean over rows of -sum_c t*log_softmax(x) (loss/cross_entropy.py:35-36) with the
     gradient produced in the same pass.  target is addressed through explicit strides so the
@@ -934,69 +966,59 @@ class SoftTargetCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, t_sb, t_sc, t_sn, rows_per_batch):
         M, C = logits.shape
-        ld = ops.round_up(C, 8)
-        if ld != C or not logits.is_contiguous():
-            xp = torch.zeros((M, ld), dtype=BF16, device=logits.device)
-            xp[:, :C] = logits
-        else:
-            xp = logits
-        row_loss, dl = ops.soft_ce_fwd_bwd(xp, C, target, t_sb, t_sc, t_sn, rows_per_batch, 1.0 / M)
+        row_loss, dl = ops.soft_ce_fwd_bwd(ce_rows(logits), C, target, t_sb, t_sc, t_sn, rows_per_batch, 1.0 / M)
         ctx.save_for_backward(dl)
         ctx.C = C
         return row_loss.mean()
 
     @staticmethod
     def backward(ctx, g):
-        (dl,) = ctx.saved_tensors
-        M = dl.shape[0]
-        out = ops.row_scale(dl, g.reshape(1).float().contiguous(), M)
-        return (out if out.shape[1] == ctx.C else out[:, :ctx.C]), None, None, None, None, None
+        return _scaled_grads(g, ctx.C, *ctx.saved_tensors)[0], None, None, None, None, None
 
 
-class TokenLabelCEFn(torch.autograd.Function):
-    """TokenLabelCrossEntropy.forward with a token-label target [B,C,2+N] (loss/cross_entropy.py:136-156) in three launches:
-    dense CE of the aux logits against target[:,:,2:], CE of the class logits against the (mix-token blended) target[:,:,1],
-    and cls_weight * mean + dense_weight * mean.  The reference's version of this is ~20 small tensor ops on the loss path; both
-    gradients come out of the forward kernels and only take the incoming scalar in backward."""
+class _TokenLabelLossFn(torch.autograd.Function):
+    """The token-label losses (loss/cross_entropy.py:136-156) in three launches: CE of the B * N aux rows against the token slots, CE of
+    the B class rows against the (mix-token blended) image-level target, and cls_weight * mean + dense_weight * mean.  The reference's
+    version of this is ~20 small tensor ops on the loss path; both gradients come out of the forward kernels and only take the incoming
+    scalar in backward.  The subclasses differ in the two kernel calls alone."""
 
     @staticmethod
-    def forward(ctx, x_cls, x_aux, target, lam, cls_weight, dense_weight):
+    def run(ctx, x_cls, x_aux, lam, cls_weight, dense_weight, aux_ce, cls_ce):
+        """aux_ce(rows, C, grad_scale) and cls_ce(rows, C, grad_scale, **mix_args) -> (row_loss, dlogits)"""
         B, N, C = x_aux.shape
-        ld = ops.round_up(C, 8)
-
-        def padded(x2d):
-            if ld == C and x2d.is_contiguous():
-                return x2d
-            xp = torch.zeros((x2d.shape[0], ld), dtype=BF16, device=x2d.device)
-            xp[:, :C] = x2d
-            return xp
-        aux2d = padded(x_aux.reshape(B * N, C))
-        cls2d = padded(x_cls.reshape(B, C))
-        sb, sc, sn = target.stride()
-        rl_aux, d_aux = ops.soft_ce_fwd_bwd(aux2d, C, target[:, :, 2:], sb, sc, sn, N, dense_weight / (B * N))
-        if hasattr(lam, "lam_ptr"):           # graph.StepScalars: lam lives in device memory (lam = 1 blends nothing: lam t + 0 t' = t)
-            rl_cls, d_cls = ops.soft_ce_fwd_bwd(cls2d, C, target[:, :, 1], sb, sc, 0, 1, cls_weight / B, mix_lam=1.0, mix_batches=B, mix_lam_ptr=lam.lam_ptr)
-        else:
-            mixed = lam < 1
-            rl_cls, d_cls = ops.soft_ce_fwd_bwd(cls2d, C, target[:, :, 1], sb, sc, 0, 1, cls_weight / B,
-                                                mix_lam=lam if mixed else 1.0, mix_batches=B if mixed else 0)
+        rl_aux, d_aux = aux_ce(ce_rows(x_aux.reshape(B * N, C)), C, dense_weight / (B * N))
+        rl_cls, d_cls = cls_ce(ce_rows(x_cls.reshape(B, C)), C, cls_weight / B, **mix_args(lam, B))
         ctx.save_for_backward(d_cls, d_aux)
         ctx.dims = (B, N, C)
         return ops.loss_combine(rl_cls, cls_weight / B, rl_aux, dense_weight / (B * N))
 
     @staticmethod
     def backward(ctx, g):
-        d_cls, d_aux = ctx.saved_tensors
         B, N, C = ctx.dims
-        gs = g.reshape(1).float().contiguous()
-        dc = ops.row_scale(d_cls, gs, d_cls.shape[0])
-        da = ops.row_scale(d_aux, gs, d_aux.shape[0])
-        dc = dc if dc.shape[1] == C else dc[:, :C]
-        da = da if da.shape[1] == C else da[:, :C]
-        return dc, da.reshape(B, N, C), None, None, None, None
+        dc, da = _scaled_grads(g, C, *ctx.saved_tensors)
+        return (dc, da.reshape(B, N, C)) + (None,) * (len(ctx.needs_input_grad) - 2)
 
 
-class SparseTokenLabelCEFn(torch.autograd.Function):
+def _sparse_aux_ce(idx, val, N, smoothing):
+    """the aux rows of both sparse token-label losses: slots 2.. of every image, in place"""
+    K = idx.shape[-1]
+    return lambda rows, C, gs: ops.soft_ce_sparse_fwd_bwd(rows, C, idx[:, 2:], val[:, 2:], (2 + N) * K, K, N, smoothing, gs)
+
+
+class TokenLabelCEFn(_TokenLabelLossFn):
+    """TokenLabelCrossEntropy.forward with a dense token-label target [B,C,2+N]: the aux logits against target[:,:,2:], the class logits
+    against target[:,:,1], both through the target's own strides."""
+
+    @staticmethod
+    def forward(ctx, x_cls, x_aux, target, lam, cls_weight, dense_weight):
+        N = x_aux.shape[1]
+        sb, sc, sn = target.stride()
+        return _TokenLabelLossFn.run(ctx, x_cls, x_aux, lam, cls_weight, dense_weight,
+                                     lambda rows, C, gs: ops.soft_ce_fwd_bwd(rows, C, target[:, :, 2:], sb, sc, sn, N, gs),
+                                     lambda rows, C, gs, **mix: ops.soft_ce_fwd_bwd(rows, C, target[:, :, 1], sb, sc, 0, 1, gs, **mix))
+
+
+class SparseTokenLabelCEFn(_TokenLabelLossFn):
     """TokenLabelCrossEntropy on the token-label target in its SOURCE form -- top-K (class, score) pairs per slot [B, 2+N, K] and a
     label-smoothing strength -- instead of the dense [B,C,2+N] tensor the reference builds from them on the GPU every step
     (main_prog.py:994-1004; loss/cross_entropy.py:136-156 for the loss itself).  Same three launches as TokenLabelCEFn; the
@@ -1004,44 +1026,16 @@ class SparseTokenLabelCEFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_cls, x_aux, idx, val, smoothing, lam, cls_weight, dense_weight):
-        B, N, C = x_aux.shape
-        K = idx.shape[-1]
-        ld = ops.round_up(C, 8)
-
-        def padded(x2d):
-            if ld == C and x2d.is_contiguous():
-                return x2d
-            xp = torch.zeros((x2d.shape[0], ld), dtype=BF16, device=x2d.device)
-            xp[:, :C] = x2d
-            return xp
+        N, K = x_aux.shape[1], idx.shape[-1]
         idx, val = idx.contiguous(), val.contiguous()
-        rl_aux, d_aux = ops.soft_ce_sparse_fwd_bwd(padded(x_aux.reshape(B * N, C)), C, idx[:, 2:], val[:, 2:], (2 + N) * K, K, N, smoothing,
-                                                   dense_weight / (B * N))
         # the class row: slot 1 of every image, in place (stride (2 + N) K); the mix-token target lam * t[b] + (1 - lam) * t[B-1-b] is
         # formed by the kernel from the two images' pairs
-        if hasattr(lam, "lam_ptr"):           # graph.StepScalars
-            rl_cls, d_cls = ops.soft_ce_sparse_fwd_bwd(padded(x_cls.reshape(B, C)), C, idx[:, 1], val[:, 1], (2 + N) * K, 0, 1, smoothing, cls_weight / B,
-                                                       mix_lam=1.0, mix_batches=B, mix_lam_ptr=lam.lam_ptr)
-        else:
-            rl_cls, d_cls = ops.soft_ce_sparse_fwd_bwd(padded(x_cls.reshape(B, C)), C, idx[:, 1], val[:, 1], (2 + N) * K, 0, 1, smoothing, cls_weight / B,
-                                                       mix_lam=lam, mix_batches=B if lam < 1 else 0)
-        ctx.save_for_backward(d_cls, d_aux)
-        ctx.dims = (B, N, C)
-        return ops.loss_combine(rl_cls, cls_weight / B, rl_aux, dense_weight / (B * N))
-
-    @staticmethod
-    def backward(ctx, g):
-        d_cls, d_aux = ctx.saved_tensors
-        B, N, C = ctx.dims
-        gs = g.reshape(1).float().contiguous()
-        dc = ops.row_scale(d_cls, gs, d_cls.shape[0])
-        da = ops.row_scale(d_aux, gs, d_aux.shape[0])
-        dc = dc if dc.shape[1] == C else dc[:, :C]
-        da = da if da.shape[1] == C else da[:, :C]
-        return dc, da.reshape(B, N, C), None, None, None, None, None, None
+        return _TokenLabelLossFn.run(ctx, x_cls, x_aux, lam, cls_weight, dense_weight, _sparse_aux_ce(idx, val, N, smoothing),
+                                     lambda rows, C, gs, **mix: ops.soft_ce_sparse_fwd_bwd(rows, C, idx[:, 1], val[:, 1], (2 + N) * K, 0, 1,
+                                                                                           smoothing, gs, **mix))
 
 
-class SparseTokenLabelGTCEFn(torch.autograd.Function):
+class SparseTokenLabelGTCEFn(_TokenLabelLossFn):
     """TokenLabelGTCrossEntropy (loss/cross_entropy.py:62-89) on the sparse target [B, 2+N, K], K <= 8: the aux rows on the sparse kernel as
     in SparseTokenLabelCEFn, the B class rows on ops.soft_ce_sparse_gt_fwd_bwd -- the argmaxes of slot 0 and slot 1, the ratio, the blend
     with the ground truth and the mix-token blend with image B-1-b are formed by the kernel from the two images' pairs -- and
@@ -1049,33 +1043,12 @@ class SparseTokenLabelGTCEFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_cls, x_aux, idx, val, smoothing, lam, cls_weight, dense_weight):
-        B, N, C = x_aux.shape
-        K = idx.shape[-1]
-        ld = ops.round_up(C, 8)
-
-        def padded(x2d):
-            if ld == C and x2d.is_contiguous():
-                return x2d
-            xp = torch.zeros((x2d.shape[0], ld), dtype=BF16, device=x2d.device)
-            xp[:, :C] = x2d
-            return xp
+        N, K = x_aux.shape[1], idx.shape[-1]
         idx, val = idx.contiguous(), val.contiguous()
-        rl_aux, d_aux = ops.soft_ce_sparse_fwd_bwd(padded(x_aux.reshape(B * N, C)), C, idx[:, 2:], val[:, 2:], (2 + N) * K, K, N, smoothing,
-                                                   dense_weight / (B * N))
         # the class row: slot 0 (ground truth) at offset 0 and slot 1 (image level) at offset K of every image, in place
-        if hasattr(lam, "lam_ptr"):           # graph.StepScalars
-            rl_cls, d_cls = ops.soft_ce_sparse_gt_fwd_bwd(padded(x_cls.reshape(B, C)), C, idx, val, (2 + N) * K, 0, K, smoothing, cls_weight / B,
-                                                          mix_lam=1.0, mix_batches=B, mix_lam_ptr=lam.lam_ptr)
-        else:
-            rl_cls, d_cls = ops.soft_ce_sparse_gt_fwd_bwd(padded(x_cls.reshape(B, C)), C, idx, val, (2 + N) * K, 0, K, smoothing, cls_weight / B,
-                                                          mix_lam=lam, mix_batches=B if lam < 1 else 0)
-        ctx.save_for_backward(d_cls, d_aux)
-        ctx.dims = (B, N, C)
-        return ops.loss_combine(rl_cls, cls_weight / B, rl_aux, dense_weight / (B * N))
-
-    @staticmethod
-    def backward(ctx, g):
-        return SparseTokenLabelCEFn.backward(ctx, g)          # (the same saved gradients, the same eight inputs)
+        return _TokenLabelLossFn.run(ctx, x_cls, x_aux, lam, cls_weight, dense_weight, _sparse_aux_ce(idx, val, N, smoothing),
+                                     lambda rows, C, gs, **mix: ops.soft_ce_sparse_gt_fwd_bwd(rows, C, idx, val, (2 + N) * K, 0, K,
+                                                                                              smoothing, gs, **mix))
 
 
 class MixedLabelCEFn(torch.autograd.Function):
@@ -1087,26 +1060,15 @@ class MixedLabelCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, ones, smoothing, lam):
         B, C = logits.shape
-        ld = ops.round_up(C, 8)
-        if ld != C or not logits.is_contiguous():
-            xp = torch.zeros((B, ld), dtype=BF16, device=logits.device)
-            xp[:, :C] = logits
-        else:
-            xp = logits
         labels, ones = labels.view(B, 1), ones.view(B, 1)             # K = 1 pair per row
-        if hasattr(lam, "lam_ptr"):
-            row_loss, dl = ops.soft_ce_sparse_fwd_bwd(xp, C, labels, ones, 1, 0, 1, smoothing, 1.0 / B, mix_lam=1.0, mix_batches=B, mix_lam_ptr=lam.lam_ptr)
-        else:
-            row_loss, dl = ops.soft_ce_sparse_fwd_bwd(xp, C, labels, ones, 1, 0, 1, smoothing, 1.0 / B, mix_lam=lam, mix_batches=B if lam < 1 else 0)
+        row_loss, dl = ops.soft_ce_sparse_fwd_bwd(ce_rows(logits), C, labels, ones, 1, 0, 1, smoothing, 1.0 / B, **mix_args(lam, B))
         ctx.save_for_backward(dl)
         ctx.C = C
         return row_loss.mean()
 
     @staticmethod
     def backward(ctx, g):
-        (dl,) = ctx.saved_tensors
-        out = ops.row_scale(dl, g.reshape(1).float().contiguous(), dl.shape[0])
-        return (out if out.shape[1] == ctx.C else out[:, :ctx.C]), None, None, None, None
+        return _scaled_grads(g, ctx.C, *ctx.saved_tensors)[0], None, None, None, None
 
 
 class DistillCEFn(torch.autograd.Function):
@@ -1119,18 +1081,9 @@ class DistillCEFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, student, teacher, mode, inv_temp, weight, base, base_weight):
-        M, C = student.shape
-        ld = ops.round_up(C, 8)
-        if ld != C or not student.is_contiguous():
-            xp = torch.zeros((M, ld), dtype=BF16, device=student.device)
-            xp[:, :C] = student
-        else:
-            xp = student
-        if not (teacher.stride(1) == 1 and teacher.stride(0) % 8 == 0 and teacher.stride(0) >= C and teacher.data_ptr() % 16 == 0):
-            tp = torch.zeros((M, ld), dtype=BF16, device=teacher.device)          # (a padded view, as functional.linear returns it, is taken as it is)
-            tp[:, :C] = teacher
-            teacher = tp[:, :C]
-        row_loss, dl = ops.distill_fwd_bwd(xp, C, teacher, mode, inv_temp, weight)
+        C = student.shape[1]
+        # the student rows by the CE rule; the teacher rows by the other one: a padded view, as linear() returns it, is read in place
+        row_loss, dl = ops.distill_fwd_bwd(ce_rows(student), C, ops.padded_view_rows(teacher), mode, inv_temp, weight)
         ctx.save_for_backward(dl)
         ctx.C, ctx.base_weight = C, float(base_weight)
         if base is None:
@@ -1139,9 +1092,8 @@ class DistillCEFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        (dl,) = ctx.saved_tensors
-        out = ops.row_scale(dl, g.reshape(1).float().contiguous(), dl.shape[0])
-        return (out if out.shape[1] == ctx.C else out[:, :ctx.C]), None, None, None, None, (g * ctx.base_weight if ctx.needs_input_grad[5] else None), None
+        (ds,) = _scaled_grads(g, ctx.C, *ctx.saved_tensors)
+        return ds, None, None, None, None, (g * ctx.base_weight if ctx.needs_input_grad[5] else None), None
 
 
 class OutlookCoreFn(torch.autograd.Function):

@@ -74,29 +74,31 @@ class _TokenLabelBase(nn.Module):
     def forward(self, x, target):
         output, aux_output, bb = x
         dev_box = getattr(bb, "scalars", None)                  # graph.DeviceBox: the step's box / lam live in device memory (graph replay)
-        bbx1, bby1, bbx2, bby2 = (0, 0, 0, 0) if dev_box is not None else bb
         B, N, C = aux_output.shape
+        if dev_box is None:
+            bbx1, bby1, bbx2, bby2 = bb
+            host_lam = 1 - ((bbx2 - bbx1) * (bby2 - bby1) / N)
+            lam = float(host_lam)                               # what the fused paths are given: a host float, or the device box
+        else:
+            lam = dev_box
         if isinstance(target, SparseTokenLabelTarget):
             # the sparse kernel takes up to 16 (class, score) pairs per row -- the mix-token class row carries 2K -- at every class count (a
             # dense [B, C, 2 + N] tensor at 21 843 classes could not exist); more pairs are densified and take the dense kernels
             K = target.idx.shape[-1]
             if (type(self)._adjust_cls is _TokenLabelBase._adjust_cls and target.idx.is_cuda and target.idx.shape[1] == 2 + N
                     and 2 * K <= SPARSE_CE_MAX_PAIRS):
-                lam = dev_box if dev_box is not None else float(1 - ((bbx2 - bbx1) * (bby2 - bby1) / N))
                 return AF.SparseTokenLabelCEFn.apply(output.to(torch.bfloat16), aux_output.to(torch.bfloat16), target.idx, target.val,
                                                      target.smoothing, lam, float(self.cls_weight), float(self.dense_weight))
             # the ground-truth variant's class row carries 4 K pairs (slot 1 and slot 0 of the image and of its mix-token partner) and the
             # kernel takes 32: functional.SparseTokenLabelGTCEFn.  A subclass with an _adjust_cls of its own is densified as before.
             if (type(self)._adjust_cls is TokenLabelGTCrossEntropy._adjust_cls and target.idx.is_cuda and target.idx.shape[1] == 2 + N
                     and K <= SPARSE_GT_MAX_K):
-                lam = dev_box if dev_box is not None else float(1 - ((bbx2 - bbx1) * (bby2 - bby1) / N))
                 return AF.SparseTokenLabelGTCEFn.apply(output.to(torch.bfloat16), aux_output.to(torch.bfloat16), target.idx, target.val,
                                                        target.smoothing, lam, float(self.cls_weight), float(self.dense_weight))
             target = target.dense(C)
         target = target.float()
         if target.dim() == 3 and type(self)._adjust_cls is _TokenLabelBase._adjust_cls and target.is_cuda:
             # the production case (TokenLabelCrossEntropy with token labels): three launches, see functional.TokenLabelCEFn
-            lam = dev_box if dev_box is not None else float(1 - ((bbx2 - bbx1) * (bby2 - bby1) / N))
             return AF.TokenLabelCEFn.apply(output.to(torch.bfloat16), aux_output.to(torch.bfloat16), target, lam,
                                            float(self.cls_weight), float(self.dense_weight))
         # the ground-truth variant on a dense [B, C, 2 + N] target in a graph-mode step takes the route below op for op -- the adjusted class
@@ -119,27 +121,14 @@ class _TokenLabelBase(nn.Module):
             # no host decision: lam = 1 blends nothing (1 * t + 0 * t' = t exactly)
             lam = dev_box.dev.view(torch.float32)[4]            # graph.StepScalars: word 4 is lam
             target_cls = lam * target_cls + (1 - lam) * target_cls.flip(0)
-        else:
-            lam = 1 - ((bbx2 - bbx1) * (bby2 - bby1) / N)
-            if lam < 1:
-                target_cls = lam * target_cls + (1 - lam) * target_cls.flip(0)
+        elif host_lam < 1:
+            target_cls = host_lam * target_cls + (1 - host_lam) * target_cls.flip(0)
         loss_cls = _dense_ce(output.to(torch.bfloat16), target_cls)
         return self.cls_weight * loss_cls + self.dense_weight * loss_aux
 
 
 class TokenLabelCrossEntropy(_TokenLabelBase):
     """reference TokenLabelCrossEntropy (loss/cross_entropy.py:112-156)"""
-
-
-def _chunked_rows(x2d):
-    """logits [M, C] as ops.softmax_topk reads them: bf16, unit column stride, rows of a multiple of 8 columns that start 16-byte aligned --
-    what functional.linear returns is passed as it is; anything else is copied into zero-padded rows"""
-    M, C = x2d.shape
-    if (x2d.dtype == torch.bfloat16 and x2d.stride(1) == 1 and x2d.stride(0) % 8 == 0 and x2d.stride(0) >= C and x2d.data_ptr() % 16 == 0):
-        return x2d
-    xp = torch.zeros((M, (C + 7) // 8 * 8), dtype=torch.bfloat16, device=x2d.device)
-    xp[:, :C] = x2d
-    return xp[:, :C]
 
 
 class SparseTokenLabelTarget:
@@ -187,8 +176,8 @@ class SparseTokenLabelTarget:
         out.val[:, 0, 0].fill_(1.0)
         fi, fv, S = out.idx.view(-1), out.val.view(-1), (2 + N) * k
         inv_temp = 1.0 / float(temperature)
-        ops.softmax_topk(_chunked_rows(aux_logits.reshape(B * N, C)), C, k, inv_temp, fi[2 * k:], fv[2 * k:], S, k, N)
-        ops.softmax_topk(_chunked_rows(cls_logits), C, k, inv_temp, fi[k:], fv[k:], S, 0, 1)
+        ops.softmax_topk(ops.padded_view_rows(aux_logits.reshape(B * N, C)), C, k, inv_temp, fi[2 * k:], fv[2 * k:], S, k, N)
+        ops.softmax_topk(ops.padded_view_rows(cls_logits), C, k, inv_temp, fi[k:], fv[k:], S, 0, 1)
         return out
 
     def dense(self, classes):

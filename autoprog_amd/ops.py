@@ -798,12 +798,8 @@ def softmax_topk(logits, C, K, inv_temp, idx_out, val_out, o_sb, o_sn, rows_per_
     order -- equal logits by ascending class -- at idx_out / val_out (int32 / fp32, any shape) + b * o_sb + n * o_sn elements.  Nothing is
     allocated; the caller's strides must keep every pair inside the two outputs (checked here against their sizes)."""
     _req(idx_out, torch.int32, "idx_out"); _req(val_out, torch.float32, "val_out")
-    if not (torch.is_tensor(logits) and logits.is_cuda):
-        raise AutoProgHipError("logits must be a CUDA tensor (the HIP path has no CPU fallback)")
-    if logits.dtype != BF16 or logits.dim() != 2 or (logits.shape[1] > 1 and logits.stride(1) != 1):
-        raise AutoProgHipError("softmax_topk: logits bf16 [M, >= C] with unit column stride")
+    ld = _padded_rows(logits, 0, "logits", "softmax_topk: logits bf16 [M, >= C] with unit column stride")
     M = logits.shape[0]
-    ld = logits.stride(0)                     # (a row stride that is no multiple of 8 or below C is the library's AP_ERR_SHAPE)
     C, K, rows_per_batch = int(C), int(K), int(rows_per_batch)
     if C > logits.shape[1]:
         raise AutoProgHipError("softmax_topk: C = %d valid columns of %d" % (C, logits.shape[1]))
@@ -815,37 +811,40 @@ def softmax_topk(logits, C, K, inv_temp, idx_out, val_out, o_sb, o_sn, rows_per_
                                    rows_per_batch, M, _stream()), "ap_softmax_topk_rows")
 
 
-def soft_ce_fwd_bwd(logits, C, target, t_sb, t_sc, t_sn, rows_per_batch, grad_scale, mix_lam=1.0, mix_batches=0, mix_lam_ptr=None):
-    """returns (row_loss fp32 [M], dlogits bf16 like logits); mix_batches = B: target of batch b is lam*t[b] + (1-lam)*t[B-1-b].
-    mix_lam_ptr: device address of lam (overrides mix_lam: graph.StepScalars)"""
+def _soft_ce(entry, what, logits, C, target_args, grad_scale, mix_lam, mix_batches, mix_lam_ptr, pairs=None):
+    """what the three soft-target CE wrappers share: the logits -- bf16, CONTIGUOUS [M, ldx], ldx read from the shape: a padded view is not
+    taken here (functional.ce_rows copies it) --, the (idx, val) tensors of a sparse target, the two outputs, and lam.  target_args: what the
+    entry point takes between ldx and row_loss.  mix_lam_ptr: device address of lam (overrides mix_lam: graph.StepScalars).
+    -> (row_loss fp32 [M], dlogits bf16 like logits)"""
     _req(logits, BF16, "logits")
-    if not (target.is_cuda and target.dtype == torch.float32):
-        raise AutoProgHipError("target must be a CUDA fp32 tensor (any strides; pass them explicitly)")
+    if pairs is not None:
+        idx, val = pairs
+        if not (idx.is_cuda and idx.dtype == torch.int32 and val.is_cuda and val.dtype == torch.float32):
+            raise AutoProgHipError("sparse targets: idx must be CUDA int32 and val CUDA fp32")
     M, ldx = logits.shape
     row_loss = torch.empty(M, dtype=torch.float32, device=logits.device)
     dlogits = torch.empty_like(logits)
-    check(lib.ap_soft_ce_fwd_bwd_dev(logits.data_ptr(), ldx, target.data_ptr(), int(t_sb), int(t_sc), int(t_sn), int(rows_per_batch),
-                                     row_loss.data_ptr(), dlogits.data_ptr(), float(grad_scale), M, C, float(mix_lam), int(mix_batches),
-                                     int(mix_lam_ptr) if mix_lam_ptr else None, _stream()),
-          "ap_soft_ce_fwd_bwd_dev")
+    check(entry(logits.data_ptr(), ldx, *target_args, row_loss.data_ptr(), dlogits.data_ptr(), float(grad_scale), M, C, float(mix_lam),
+                int(mix_batches), int(mix_lam_ptr) if mix_lam_ptr else None, _stream()), what)
     return row_loss, dlogits
+
+
+def soft_ce_fwd_bwd(logits, C, target, t_sb, t_sc, t_sn, rows_per_batch, grad_scale, mix_lam=1.0, mix_batches=0, mix_lam_ptr=None):
+    """returns (row_loss fp32 [M], dlogits bf16 like logits); mix_batches = B: target of batch b is lam*t[b] + (1-lam)*t[B-1-b].
+    mix_lam_ptr: device address of lam (overrides mix_lam: graph.StepScalars)"""
+    if not (target.is_cuda and target.dtype == torch.float32):
+        raise AutoProgHipError("target must be a CUDA fp32 tensor (any strides; pass them explicitly)")
+    return _soft_ce(lib.ap_soft_ce_fwd_bwd_dev, "ap_soft_ce_fwd_bwd_dev", logits, C,
+                    (target.data_ptr(), int(t_sb), int(t_sc), int(t_sn), int(rows_per_batch)), grad_scale, mix_lam, mix_batches, mix_lam_ptr)
 
 
 def soft_ce_sparse_fwd_bwd(logits, C, idx, val, p_sb, p_sn, rows_per_batch, smoothing, grad_scale, mix_lam=1.0, mix_batches=0, mix_lam_ptr=None):
     """soft-target CE against top-K (class, score) pairs + label smoothing (the token-label target before it is densified);
     idx int32 / val fp32 with K = idx.shape[-1] pairs per row at b * p_sb + n * p_sn.  Returns (row_loss fp32 [M], dlogits bf16).
     mix_batches = B: the target of row (b, n) is mix_lam * t[b, n] + (1 - mix_lam) * t[B-1-b, n] (the mix-token class target)."""
-    _req(logits, BF16, "logits")
-    if not (idx.is_cuda and idx.dtype == torch.int32 and val.is_cuda and val.dtype == torch.float32):
-        raise AutoProgHipError("sparse targets: idx must be CUDA int32 and val CUDA fp32")
-    M, ldx = logits.shape
-    row_loss = torch.empty(M, dtype=torch.float32, device=logits.device)
-    dlogits = torch.empty_like(logits)
-    check(lib.ap_soft_ce_sparse_fwd_bwd_dev(logits.data_ptr(), ldx, idx.data_ptr(), val.data_ptr(), int(idx.shape[-1]), int(p_sb), int(p_sn),
-                                            int(rows_per_batch), float(smoothing), row_loss.data_ptr(), dlogits.data_ptr(), float(grad_scale), M, C,
-                                            float(mix_lam), int(mix_batches), int(mix_lam_ptr) if mix_lam_ptr else None, _stream()),
-          "ap_soft_ce_sparse_fwd_bwd_dev")
-    return row_loss, dlogits
+    return _soft_ce(lib.ap_soft_ce_sparse_fwd_bwd_dev, "ap_soft_ce_sparse_fwd_bwd_dev", logits, C,
+                    (idx.data_ptr(), val.data_ptr(), int(idx.shape[-1]), int(p_sb), int(p_sn), int(rows_per_batch), float(smoothing)),
+                    grad_scale, mix_lam, mix_batches, mix_lam_ptr, pairs=(idx, val))
 
 
 def soft_ce_sparse_gt_fwd_bwd(logits, C, idx, val, p_sb, p_s0, p_s1, smoothing, grad_scale, mix_lam=1.0, mix_batches=0, mix_lam_ptr=None):
@@ -854,33 +853,40 @@ def soft_ce_sparse_gt_fwd_bwd(logits, C, idx, val, p_sb, p_s0, p_s1, smoothing, 
     image-level slot at b * p_sb + p_s1 (elements of idx int32 / val fp32).  The two argmaxes, ratio = 0.9 - 0.4 * [they agree] and the
     blend ratio * slot 1 + (1 - ratio) * slot 0 are formed on the device, for the row's image and -- mix_batches = B -- for its partner
     B-1-b.  Returns (row_loss fp32 [B], dlogits bf16)."""
-    _req(logits, BF16, "logits")
-    if not (idx.is_cuda and idx.dtype == torch.int32 and val.is_cuda and val.dtype == torch.float32):
-        raise AutoProgHipError("sparse targets: idx must be CUDA int32 and val CUDA fp32")
-    B, ldx = logits.shape
+    B = logits.shape[0]
     K, p_sb, p_s0, p_s1 = int(idx.shape[-1]), int(p_sb), int(p_s0), int(p_s1)
     if B > 0 and (min(p_sb, p_s0, p_s1) < 0 or (B - 1) * p_sb + max(p_s0, p_s1) + K > min(idx.numel(), val.numel())):
         raise AutoProgHipError("soft_ce_sparse_gt_fwd_bwd: the slot offsets reach past the %d elements of the pair arrays" % min(idx.numel(), val.numel()))
-    row_loss = torch.empty(B, dtype=torch.float32, device=logits.device)
-    dlogits = torch.empty_like(logits)
-    check(lib.ap_soft_ce_sparse_gt_fwd_bwd(logits.data_ptr(), ldx, idx.data_ptr(), val.data_ptr(), K, p_sb, p_s0, p_s1, float(smoothing),
-                                           row_loss.data_ptr(), dlogits.data_ptr(), float(grad_scale), B, C, float(mix_lam), int(mix_batches),
-                                           int(mix_lam_ptr) if mix_lam_ptr else None, _stream()),
-          "ap_soft_ce_sparse_gt_fwd_bwd")
-    return row_loss, dlogits
+    return _soft_ce(lib.ap_soft_ce_sparse_gt_fwd_bwd, "ap_soft_ce_sparse_gt_fwd_bwd", logits, C,
+                    (idx.data_ptr(), val.data_ptr(), K, p_sb, p_s0, p_s1, float(smoothing)), grad_scale, mix_lam, mix_batches, mix_lam_ptr,
+                    pairs=(idx, val))
 
 
-def _padded_rows(t, C, name):
+def _padded_rows(t, C, name, shape_error=None):
     """a bf16 CUDA matrix [M, >= C] with unit column stride -> its leading dimension (a padded view is taken as it is; a row stride
-    that is no multiple of 8 or below C, or a misaligned base, is the library's AP_ERR_SHAPE)"""
+    that is no multiple of 8 or below C, or a misaligned base, is the library's AP_ERR_SHAPE).  shape_error: the caller's own text for a
+    matrix of another form."""
     if not (torch.is_tensor(t) and t.is_cuda):
         raise AutoProgHipError("%s must be a CUDA tensor (the HIP path has no CPU fallback)" % name)
     if t.dtype != BF16 or t.dim() != 2 or t.shape[1] < C or (t.shape[1] > 1 and t.stride(1) != 1):
-        raise AutoProgHipError("%s must be bf16 [M, >= %d] with unit column stride" % (name, C))
+        raise AutoProgHipError(shape_error or "%s must be bf16 [M, >= %d] with unit column stride" % (name, C))
     ld = t.stride(0)
     if t.shape[0] <= 1 and (ld < t.shape[1] or ld % 8):         # (the row stride of a single row means nothing)
         ld = t.shape[1]
     return ld
+
+
+def padded_view_rows(x2d):
+    """logits [M, C] for an entry point that takes a padded view (ap_softmax_topk_rows, the teacher of ap_distill_fwd_bwd; _padded_rows is
+    their check): bf16 with unit column stride, a row stride that is a multiple of 8 and at least C, and a 16-byte-aligned base -- what
+    functional.linear returns -- is passed as it is; anything else is copied into zero-padded rows and viewed [:, :C].  The soft-target CE
+    wrappers do not take such views: functional.ce_rows is their rule, and the two differ on purpose."""
+    M, C = x2d.shape
+    if x2d.dtype == BF16 and x2d.stride(1) == 1 and x2d.stride(0) % 8 == 0 and x2d.stride(0) >= C and x2d.data_ptr() % 16 == 0:
+        return x2d
+    xp = torch.zeros((M, round_up(C, 8)), dtype=BF16, device=x2d.device)
+    xp[:, :C] = x2d
+    return xp[:, :C]
 
 
 def distill_fwd_bwd(student, C, teacher, mode, inv_temp, grad_scale):
