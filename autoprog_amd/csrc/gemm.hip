@@ -30,6 +30,7 @@
 #include "gemm_ws.h"
 #include "gemm_tn8p.h"
 #include "gemm_tn_fp8.h"
+#include "tn_plan.h"
 // (the measured-and-rejected kernels of rounds 1 and 2 -- LDS-DMA rings, persistent 256-row tiles, the ring weight-gradient kernel -- and
 // their AP_GEMM_NT_P / _RING / _DMA, AP_GEMM_TN_RING switches live under tools/gemm_lab/rejected/, outside the product library)
 #include <cstdlib>
@@ -438,15 +439,9 @@ struct TnArgs {
 };
 // deterministic mode: partial results are STORED per token split and summed in split order by k_tn_reduce
 struct TnDet { float* slab; float* cs_slab; };
-#define TN_MAX_GROUP 8
 struct TnGroup { TnArgs p[TN_MAX_GROUP]; int count; };
-// Placement of a grouped launch: entry b = (problem << 12 | split * tiles + tile) of workgroup b, TN_MAP_IDLE = none.  Workgroup
-// b runs on XCD b % 8, so the host puts ALL output tiles of one (problem, token split) on one XCD: that split's operand slab is
-// then fetched through ONE L2 instead of the 1.5-2 that a contiguous id range per XCD gives when 5 splits meet 8 XCDs
-// (transformer block: 486 MB of beyond-L2 traffic per launch for 270 MB of operands before).
-#define TN_MAP_MAX 1024
-#define TN_MAP_IDLE 0xFFFFu
-struct TnMap { unsigned short e[TN_MAP_MAX]; };
+static_assert(TM == TN_STEP, "tn_plan.h counts the reduction steps of these kernels");
+// (the placement table TnMap of a grouped launch, entry b = problem << 12 | split * tiles + tile of workgroup b: tn_plan.h)
 
 template <bool BPATCH = false, bool BBN = false>
 __device__ __forceinline__ void tn_tile(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ B, int ldb, float* __restrict__ C, int ldc,
@@ -663,9 +658,7 @@ k_gemm_tn_grouped(TnGroup grp) {
 }
 // LayerNorm dgamma / dbeta reductions riding in the grouped launch (ap_gemm_tn_acc_grouped_ln): the workgroups behind the placement
 // table add the partial rows k_ln_bwd left (column sums of [nblocks][2 C]) -- the block's own reduction launch (5.8 us, 19 per step,
-// nothing but latency) disappears into a launch that has idle workgroup slots anyway.
-struct TnLnItem { const float* partial; float* dgamma; float* dbeta; int nblocks; int C; };
-struct TnLn { TnLnItem it[AP_LN_MAX_BATCH]; int count; int first; };            // first: blockIdx.x of the first reduction workgroup
+// nothing but latency) disappears into a launch that has idle workgroup slots anyway.  (TnLn, the table of these riders: tn_plan.h)
 __device__ __forceinline__ void tn_ln_role(const TnLn& ln, int blk, float* red) {          // red: >= (blockDim.x / 32) * 33 floats of LDS
     int y = 0, b0 = 0;
     for (int i = 0; i + 1 < ln.count; ++i) {                                     // which reduction this workgroup belongs to
@@ -713,10 +706,7 @@ k_gemm_tn_grouped_map(TnGroup grp, TnMap map, TnLn ln) {
 
 // the 192 x 192-tile, LDS-DMA weight-gradient kernel (gemm_tn8p.h) with the same placement table and LayerNorm riders
 // (up to AP_TN_MAX_GROUP = 32 problems -- the Linear layers of six transformer blocks, or of two and four outlooker blocks -- and one work item per CU: its own, smaller
-// placement table, entry = problem << 11 | split * tiles + tile; the three arguments stay under 4 KB)
-#define T8_MAP_MAX 320
-#define T8_MAP_SHIFT 11
-struct T8Map { unsigned short e[T8_MAP_MAX]; };
+// placement table T8Map, entry = problem << 11 | split * tiles + tile (tn_plan.h); the three arguments stay under 4 KB)
 struct T8Group { T8Item p[AP_TN_MAX_GROUP]; int tiles[AP_TN_MAX_GROUP]; };
 static_assert(sizeof(T8Group) + sizeof(T8Map) + sizeof(TnLn) <= 4096, "kernel arguments of k_gemm_tn_8p");
 static_assert(sizeof(TnGroup) + sizeof(TnMap) + sizeof(TnLn) <= 4096, "kernel arguments of k_gemm_tn_grouped_map");
@@ -981,17 +971,29 @@ static int ws_try(const bf16_t* A, int lda, const bf16_t* B, int ldb, bf16_t* C,
     return ap_check_launch();
 }
 
+// the epilogue of a launch without ap_gemm_epilogue: everything off, one row per DropPath scale
+static EpiArgs epi_none() {
+    EpiArgs ep = {};
+    ep.rows_per_scale = 1;
+    return ep;
+}
+// the fields of ap_gemm_epilogue that every entry point takes (what else it takes, and what it refuses, is the entry point's)
+static void epi_common(EpiArgs& ep, const ap_gemm_epilogue& epi) {
+    ep.bias = epi.bias; ep.gelu = epi.gelu; ep.preact = epi.preact_out; ep.dgelu_of = epi.dgelu_of;
+    ep.row_scale = epi.row_scale; ep.rows_per_scale = epi.rows_per_scale > 0 ? epi.rows_per_scale : 1;
+    ep.residual = epi.residual; ep.ldr = epi.ldr;
+}
+
 int ap_gemm_nt(const ap_bf16* A, int lda, const ap_bf16* B, int ldb, ap_bf16* C, int ldc, int M, int N, int K,
                const ap_gemm_epilogue* epi, ap_stream_t stream) {
     if (!A || !B || !C) return AP_ERR_NULL;
     if (M <= 0 || N <= 0 || K <= 0 || M > AP_MAX_ROWS) return AP_ERR_SHAPE;          // (tile counts (M + tile - 1) / tile are formed in int)
     if ((K & 7) || (lda & 7) || (ldb & 7) || lda < K || ldb < K || ldc < N) return AP_ERR_SHAPE;
-    EpiArgs ep = {nullptr, 0, nullptr, nullptr, nullptr, 1, nullptr, 0, 0, nullptr, {0, 0, 0, 0, 0, 0u, 0u}, nullptr, nullptr, nullptr};
+    EpiArgs ep = epi_none();
     { const char* e = getenv("AP_GEMM_DBG"); if (e) ep.dbg = atoi(e); }
     if (epi) {
-        ep.bias = epi->bias; ep.gelu = epi->gelu; ep.preact = epi->preact_out; ep.dgelu_of = epi->dgelu_of; ep.mul_by = epi->mul_by;
-        ep.row_scale = epi->row_scale; ep.rows_per_scale = epi->rows_per_scale > 0 ? epi->rows_per_scale : 1;
-        ep.residual = epi->residual; ep.ldr = epi->ldr; ep.mul8 = epi->mul_by8;
+        epi_common(ep, *epi);
+        ep.mul_by = epi->mul_by; ep.mul8 = epi->mul_by8;
         if (ep.residual && ep.ldr < N) return AP_ERR_SHAPE;
         if ((ep.mul_by != nullptr) + (ep.dgelu_of != nullptr) + (ep.mul8 != nullptr) > 1) return AP_ERR_SHAPE;
         // gelu = 4: the value of mode 3 in `out`, no side store (forward-only launches); preact_out is ignored
@@ -1108,11 +1110,10 @@ int ap_gemm_nt_fp8(const unsigned char* A, int lda, const unsigned char* B, int 
     if (!A || !B || !C || !dq_a || !dq_b) return AP_ERR_NULL;
     if (M <= 0 || N <= 0 || K <= 0 || M > AP_MAX_ROWS) return AP_ERR_SHAPE;          // (tile counts (M + tile - 1) / tile are formed in int)
     if ((K & 15) || (lda & 15) || (ldb & 15) || lda < K || ldb < K || ldc < N) return AP_ERR_SHAPE;       // 16-byte chunks of e4m3
-    EpiArgs ep = {nullptr, 0, nullptr, nullptr, nullptr, 1, nullptr, 0, 0, nullptr, {0, 0, 0, 0, 0, 0u, 0u}, dq_a, dq_b, nullptr};
+    EpiArgs ep = epi_none();
+    ep.dq_a = dq_a; ep.dq_b = dq_b;
     if (epi) {
-        ep.bias = epi->bias; ep.gelu = epi->gelu; ep.preact = epi->preact_out; ep.dgelu_of = epi->dgelu_of;
-        ep.row_scale = epi->row_scale; ep.rows_per_scale = epi->rows_per_scale > 0 ? epi->rows_per_scale : 1;
-        ep.residual = epi->residual; ep.ldr = epi->ldr;
+        epi_common(ep, *epi);
         if (ep.residual && ep.ldr < N) return AP_ERR_SHAPE;
         if (ep.gelu < 0 || ep.gelu > 3 || (ep.gelu >= 2 && !ep.preact)) return AP_ERR_SHAPE;
         ep.q8 = epi->q8_out; ep.q8_scale = epi->q8_scale; ep.q8_amax = epi->q8_amax;
@@ -1152,7 +1153,7 @@ int ap_gemm_nt_patch_bn(const ap_bf16* A, const ap_bn_input* a_bn, const ap_bf16
     if (!A || !B || !C || !map) return AP_ERR_NULL;
     if (a_bn && (side != 1 || !a_bn->mean || !a_bn->rstd || !a_bn->gamma || !a_bn->beta)) return AP_ERR_NULL;
     if (M <= 0 || N <= 0 || K <= 0 || M > AP_MAX_ROWS || (K & 7) || (ldb & 7) || ldb < K) return AP_ERR_SHAPE;
-    EpiArgs ep = {nullptr, 0, nullptr, nullptr, nullptr, 1, nullptr, 0, 0, nullptr, {0, 0, 0, 0, 0, 0u, 0u}, nullptr, nullptr, nullptr};
+    EpiArgs ep = epi_none();
     if (!patch_map_device(map, ep.pm)) return AP_ERR_SHAPE;
     if ((int64_t)M >= (int64_t)(0xFFFFFFFFu / (unsigned)map->group)) return AP_ERR_SHAPE;       // exactness bound of the magic division
     (void)hipGetLastError();
@@ -1170,301 +1171,90 @@ int ap_gemm_nt_patch_bn(const ap_bf16* A, const ap_bn_input* a_bn, const ap_bf16
     return ap_check_launch();
 }
 
+// ---- weight gradients: what is launched and how it is cut and placed is planned by tn_plan.h; here its plans become kernel arguments.
+// The run-time switches and the device's CU count are read here and handed to the planner.
+static int tn_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static int tn_8p_enabled() { static const int v = tn_env("AP_GEMM_TN_8P", 1); return v; }
+static int tn_capacity() {               // resident workgroups of the 128 x 128-tile kernels, two per CU (AP_GEMM_TN_GROUP_BLOCKS forces a number)
+    static const int forced = tn_env("AP_GEMM_TN_GROUP_BLOCKS", 0);
+    return forced > 0 ? forced : 2 * ap_cu_count();
+}
+
 int ap_gemm_tn_acc(const ap_bf16* A, int lda, const ap_bf16* B, int ldb, float* C, int ldc, int M, int N1, int N2,
                    float* colsum_A, ap_stream_t stream) {
     if (!A || !B || !C) return AP_ERR_NULL;
     if (M <= 0 || N1 <= 0 || N2 <= 0 || M > AP_MAX_ROWS) return AP_ERR_SHAPE;
     if ((lda & 7) || (ldb & 7) || lda < N1 || ldb < N2 || ldc < N2) return AP_ERR_SHAPE;
-    const int t1 = (N1 + 127) / 128, t2 = (N2 + 127) / 128;
-    int full_steps = 0;
-    const int done = full_steps * TM;
-    if (done < M) {                                   // token tail (or everything when the ring is disabled)
-        const int Mt = M - done;
-        const int total_steps = (Mt + TM - 1) / TM;
-        static int target_blocks = 0;
-        if (target_blocks == 0) { const char* e = getenv("AP_GEMM_TN_BLOCKS"); target_blocks = e ? atoi(e) : 384; /* measured optimum: atomics vs parallelism */ }
-        int splits = (target_blocks + t1 * t2 - 1) / (t1 * t2);
-        if (splits > total_steps / 4) splits = total_steps / 4;
-        if (splits < 1) splits = 1;
-        const int sps = (total_steps + splits - 1) / splits;
-        splits = (total_steps + sps - 1) / sps;
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(k_gemm_tn, dim3(t1 * t2 * splits), dim3(256), 0, (hipStream_t)stream, A + (int64_t)done * lda, lda, B + (int64_t)done * ldb, ldb,
-                           C, ldc, Mt, N1, N2, sps, colsum_A, t1, t2, t1 * t2 * splits);
-        return ap_check_launch();
-    }
-    return AP_OK;
+    static const int target_blocks = tn_env("AP_GEMM_TN_BLOCKS", 384);            // measured optimum: atomics vs parallelism
+    const TnItemPlan p = tn_single_plan(M, N1, N2, target_blocks);
+    const int blocks = p.t1 * p.t2 * p.splits;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_gemm_tn, dim3(blocks), dim3(256), 0, (hipStream_t)stream, A, lda, B, ldb, C, ldc, M, N1, N2, p.sps, colsum_A, p.t1, p.t2, blocks);
+    return ap_check_launch();
 }
 
-static int tn_grouped_128(const ap_tn_problem* problems, int count, const ap_ln_reduce* ln_items, int ln_count,
-                          void* workspace, size_t ws_bytes, ap_stream_t stream);
-// plan of a grouped launch: token splits per problem such that the launch fills the resident workgroup capacity once
-static int tn_validate(const ap_tn_problem* problems, int count) {
-    if (!problems) return AP_ERR_NULL;
-    if (count <= 0 || count > AP_TN_MAX_GROUP) return AP_ERR_SHAPE;
-    for (int i = 0; i < count; ++i) {
-        const ap_tn_problem& q = problems[i];
-        if (!q.A || !q.B || !q.C) return AP_ERR_NULL;
-        if (q.M <= 0 || q.N1 <= 0 || q.N2 <= 0 || q.M > AP_MAX_ROWS) return AP_ERR_SHAPE;
-        if ((q.lda & 7) || q.lda < q.N1 || q.ldc < q.N2) return AP_ERR_SHAPE;
-        if (!q.b_patch && ((q.ldb & 7) || q.ldb < q.N2)) return AP_ERR_SHAPE;         // patch-addressed B has no leading dimension
-    }
-    return AP_OK;
-}
-static int tn_plan(const ap_tn_problem* problems, int count, TnGroup& grp, int& total_blocks, size_t& slab_floats) {
-    if (!problems) return AP_ERR_NULL;
-    if (count <= 0 || count > TN_MAX_GROUP) return AP_ERR_SHAPE;
-    // Two 256-thread workgroups are resident per CU: the launch should fill that single wave of workgroups as fully as
-    // possible but never spill into a second one (measured on the D1 blocks: 450 workgroups 125 us, 540 -> 175 us).
-    static int forced = -1;
-    if (forced < 0) { const char* e = getenv("AP_GEMM_TN_GROUP_BLOCKS"); forced = e ? atoi(e) : 0; }
-    const int capacity = forced > 0 ? forced : 2 * ap_cu_count();
-    int max_steps = 1;
-    for (int i = 0; i < count; ++i) {
-        const ap_tn_problem& q = problems[i];
-        if (!q.A || !q.B || !q.C) return AP_ERR_NULL;
-        if (q.M <= 0 || q.N1 <= 0 || q.N2 <= 0 || q.M > AP_MAX_ROWS) return AP_ERR_SHAPE;
-        if ((q.lda & 7) || q.lda < q.N1 || q.ldc < q.N2) return AP_ERR_SHAPE;
-        if (!q.b_patch && ((q.ldb & 7) || q.ldb < q.N2)) return AP_ERR_SHAPE;         // patch-addressed B has no leading dimension
-        const int steps = (q.M + TM - 1) / TM;
-        if (steps > max_steps) max_steps = steps;
-    }
-    auto blocks_at = [&](int sps) {
-        int64_t nb = 0;
-        for (int i = 0; i < count; ++i) {
-            const ap_tn_problem& q = problems[i];
-            const int steps = (q.M + TM - 1) / TM;
-            nb += (int64_t)((q.N1 + 127) / 128) * ((q.N2 + 127) / 128) * ((steps + sps - 1) / sps);
-        }
-        return nb;
-    };
-    // smallest steps-per-workgroup (>= 8) whose block count fits the resident capacity (binary search: blocks_at is monotone)
-    int lo = 8, hi = max_steps > 8 ? max_steps : 8;
-    while (lo < hi) {
-        const int mid = (lo + hi) / 2;
-        if (blocks_at(mid) <= capacity) hi = mid; else lo = mid + 1;
-    }
-    const int sps_target = lo;
+// the arguments of the 128 x 128-tile kernels from a plan (slabs of the deterministic mode: the caller's)
+static int tn_group_args(const ap_tn_problem* problems, int count, TnGroupPlan& plan, TnGroup& grp) {
+    if (const int rc = tn128_plan(problems, count, tn_capacity(), plan); rc != AP_OK) return rc;
     grp.count = count;
-    int start = 0;
-    slab_floats = 0;
     for (int i = 0; i < count; ++i) {
         const ap_tn_problem& q = problems[i];
+        const TnItemPlan& p = plan.p[i];
         TnArgs& a = grp.p[i];
-        const int t1 = (q.N1 + 127) / 128, t2 = (q.N2 + 127) / 128, steps = (q.M + TM - 1) / TM;
-        int splits = (steps + sps_target - 1) / sps_target;
-        if (splits < 1) splits = 1;
-        const int sps = (steps + splits - 1) / splits;
-        splits = (steps + sps - 1) / sps;
         a.A = reinterpret_cast<const bf16_t*>(q.A); a.B = reinterpret_cast<const bf16_t*>(q.B); a.C = q.C; a.colsum = q.colsum_A;
         a.lda = q.lda; a.ldb = q.ldb; a.ldc = q.ldc; a.M = q.M; a.N1 = q.N1; a.N2 = q.N2;
-        a.steps_per_split = sps; a.t1 = t1; a.t2 = t2; a.nblocks = t1 * t2 * splits; a.start = start;
+        a.steps_per_split = p.sps; a.t1 = p.t1; a.t2 = p.t2; a.nblocks = p.t1 * p.t2 * p.splits; a.start = p.start;
         a.cs_weight = reinterpret_cast<const bf16_t*>(q.colsum_weight);
-        a.cs_scale = q.colsum_weight ? q.colsum_scale : 1.0f;
-        a.alpha = q.alpha != 0.0f ? q.alpha : 1.0f;
-        a.slab = nullptr; a.splits = splits;
+        a.cs_scale = tn_cs_scale(q.colsum_weight, q.colsum_scale);
+        a.alpha = tn_alpha(q.alpha);
+        a.slab = nullptr; a.splits = p.splits;
         a.pb = PatchMap{0, 0, 0, 0, 0, 0u, 0u};
-        if (q.b_patch) {
-            if (!patch_map_device(q.b_patch, a.pb) || (q.N2 & 7) || (q.b_patch->kseg & 7) || q.N2 % q.b_patch->kseg ||
-                (int64_t)q.M >= (int64_t)(0xFFFFFFFFu / (unsigned)q.b_patch->group)) return AP_ERR_SHAPE;
-        }
-        slab_floats += (size_t)splits * ((size_t)q.N1 * q.N2 + (q.colsum_A ? (size_t)q.N1 : 0));
-        start += a.nblocks;
+        if (q.b_patch) patch_map_device(q.b_patch, a.pb);          // (the plan has checked the map)
     }
     for (int i = count; i < TN_MAX_GROUP; ++i) { grp.p[i] = grp.p[0]; grp.p[i].start = 0x7fffffff; grp.p[i].nblocks = 0; }
-    total_blocks = start;
     return AP_OK;
-}
-
-// One (problem, token split) = one XCD: greedy packing of the groups, largest first, onto the least loaded of the 8 XCDs; the
-// launch is 8 * (largest load) workgroups, the unused ids return at once.  false = does not fit the table or the resident capacity
-// (more than `cap` slots per XCD would start a second round of workgroups): the caller keeps the contiguous-range placement.
-static bool tn_place(const TnGroup& grp, int cap, TnMap& map, int& blocks) {
-    struct G { int p, s, n; };
-    G g[TN_MAP_MAX]; int ng = 0;
-    for (int i = 0; i < grp.count; ++i) {
-        const int tiles = grp.p[i].t1 * grp.p[i].t2;
-        if (tiles * grp.p[i].splits > 0x1000) return false;
-        for (int s = 0; s < grp.p[i].splits; ++s) { if (ng == TN_MAP_MAX) return false; g[ng++] = G{i, s, tiles}; }
-    }
-    for (int i = 1; i < ng; ++i) {                       // insertion sort by size, descending, stable
-        const G v = g[i]; int j = i - 1;
-        while (j >= 0 && g[j].n < v.n) { g[j + 1] = g[j]; --j; }
-        g[j + 1] = v;
-    }
-    int load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < TN_MAP_MAX; ++i) map.e[i] = TN_MAP_IDLE;
-    for (int i = 0; i < ng; ++i) {
-        int x = 0;
-        for (int k = 1; k < 8; ++k) if (load[k] < load[x]) x = k;
-        if (load[x] + g[i].n > cap || (load[x] + g[i].n) * 8 > TN_MAP_MAX) return false;
-        for (int t = 0; t < g[i].n; ++t) map.e[(load[x] + t) * 8 + x] = (unsigned short)((g[i].p << 12) | (g[i].s * g[i].n + t));
-        load[x] += g[i].n;
-    }
-    int mx = 0;
-    for (int k = 0; k < 8; ++k) if (load[k] > mx) mx = load[k];
-    blocks = mx * 8;
-    return true;
-}
-
-// Plan of the 192 x 192-tile kernel: every width a multiple of 192, whole 64-token K-tiles, plain row-major operands.  The token
-// axis is cut into ranges of `ksps` K-tiles, the smallest that leaves at most one work item per CU and fits the per-XCD placement.
-static bool tn8_fits(const ap_tn_problem& q) {
-    static int enabled = -1;
-    if (enabled < 0) { const char* e = getenv("AP_GEMM_TN_8P"); enabled = e ? atoi(e) : 1; }
-    if (!enabled || !q.A || !q.B || !q.C || q.b_patch || q.N1 <= 0 || q.N2 <= 0) return false;
-    if (q.N1 % 192 || q.N2 % 192 || q.M % 64 || q.M < 4096 || (q.lda & 7) || (q.ldb & 7) || q.lda < q.N1 || q.ldb < q.N2 || q.ldc < q.N2) return false;
-    return !(q.colsum_weight && (reinterpret_cast<uintptr_t>(q.colsum_weight) & 3));
-}
-// placement for the 8p kernel: as tn_place, but a (problem, token range) that does not fit the least loaded XCD any more is CUT over
-// XCDs (consecutive tiles share their A column block): with six blocks in a launch the table is nearly full -- 240 of 256 slots
-struct T8Plan { int tiles, splits; };
-static bool t8_place(const T8Plan* pl, int count, int cap, T8Map& map, int& blocks) {
-    struct G { int p, s, n; };
-    G g[T8_MAP_MAX]; int ng = 0;
-    for (int i = 0; i < count; ++i) {
-        if (pl[i].tiles * pl[i].splits > (1 << T8_MAP_SHIFT)) return false;
-        for (int s = 0; s < pl[i].splits; ++s) { if (ng == T8_MAP_MAX) return false; g[ng++] = G{i, s, pl[i].tiles}; }
-    }
-    for (int i = 1; i < ng; ++i) {                       // insertion sort by size, descending, stable
-        const G v = g[i]; int j = i - 1;
-        while (j >= 0 && g[j].n < v.n) { g[j + 1] = g[j]; --j; }
-        g[j + 1] = v;
-    }
-    int load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < T8_MAP_MAX; ++i) map.e[i] = TN_MAP_IDLE;
-    for (int i = 0; i < ng; ++i) {
-        int t = 0;
-        while (t < g[i].n) {
-            int x = 0;
-            for (int k = 1; k < 8; ++k) if (load[k] < load[x]) x = k;
-            int take = g[i].n - t;
-            if (take > cap - load[x]) take = cap - load[x];
-            if (take <= 0 || (load[x] + take) * 8 > T8_MAP_MAX) return false;
-            for (int u = 0; u < take; ++u) map.e[(load[x] + u) * 8 + x] = (unsigned short)((g[i].p << T8_MAP_SHIFT) | (g[i].s * g[i].n + t + u));
-            load[x] += take; t += take;
-        }
-    }
-    int mx = 0;
-    for (int k = 0; k < 8; ++k) if (load[k] > mx) mx = load[k];
-    blocks = mx * 8;
-    return true;
-}
-static bool tn8_plan(const ap_tn_problem* problems, int count, int n_cu, T8Group& g8, T8Map& map, int& mblocks) {
-    if (count <= 0 || count > AP_TN_MAX_GROUP) return false;
-    int64_t work = 0; int max_k = 1;
-    for (int i = 0; i < count; ++i) {
-        const ap_tn_problem& q = problems[i];
-        if (!tn8_fits(q)) return false;
-        work += (int64_t)(q.N1 / 192) * (q.N2 / 192) * (q.M / 64);
-        if (q.M / 64 > max_k) max_k = q.M / 64;
-    }
-    int ksps = (int)((work + n_cu - 1) / n_cu);
-    if (ksps < 8) ksps = 8;
-    T8Plan pl[AP_TN_MAX_GROUP];
-    for (; ksps <= max_k; ++ksps) {
-        int64_t items = 0;
-        for (int i = 0; i < count; ++i) {
-            const ap_tn_problem& q = problems[i];
-            const int ksteps = q.M / 64;
-            pl[i].tiles = (q.N1 / 192) * (q.N2 / 192); pl[i].splits = (ksteps + ksps - 1) / ksps;
-            items += (int64_t)pl[i].tiles * pl[i].splits;
-        }
-        if (items <= n_cu && t8_place(pl, count, n_cu / 8, map, mblocks)) break;
-    }
-    if (ksps > max_k) return false;
-    for (int i = 0; i < count; ++i) {
-        const ap_tn_problem& q = problems[i];
-        T8Item& t = g8.p[i];
-        t.A = reinterpret_cast<const bf16_t*>(q.A); t.B = reinterpret_cast<const bf16_t*>(q.B); t.C = q.C; t.colsum = q.colsum_A;
-        t.cs_weight = reinterpret_cast<const bf16_t*>(q.colsum_weight);
-        t.lda = q.lda; t.ldb = q.ldb; t.ldc = q.ldc; t.M = q.M; t.t2 = q.N2 / 192; t.ksteps = q.M / 64; t.ksps = ksps;
-        t.alpha = q.alpha != 0.0f ? q.alpha : 1.0f; t.cs_scale = q.colsum_weight ? q.colsum_scale : 1.0f;
-        g8.tiles[i] = (q.N1 / 192) * (q.N2 / 192);
-        t.shared_out = 0;
-        for (int j = 0; j < count; ++j)
-            if (j != i && (problems[j].C == q.C || (q.colsum_A && problems[j].colsum_A == q.colsum_A))) t.shared_out = 1;
-    }
-    for (int i = count; i < AP_TN_MAX_GROUP; ++i) { g8.p[i] = g8.p[0]; g8.tiles[i] = 1; }
-    return true;
 }
 
 size_t ap_gemm_tn_grouped_workspace(const ap_tn_problem* problems, int count) {
-    TnGroup grp; int blocks = 0; size_t fl = 0;
-    if (tn_plan(problems, count, grp, blocks, fl) != AP_OK) return 0;
-    return fl * sizeof(float);
+    TnGroupPlan plan; TnGroup grp;
+    return tn_group_args(problems, count, plan, grp) == AP_OK ? plan.slab_floats * sizeof(float) : 0;
 }
 
 int ap_gemm_tn_acc_grouped(const ap_tn_problem* problems, int count, void* workspace, size_t ws_bytes, ap_stream_t stream) {
     return ap_gemm_tn_acc_grouped_ln(problems, count, nullptr, 0, workspace, ws_bytes, stream);
 }
 
-int ap_gemm_tn_acc_grouped_ln(const ap_tn_problem* problems, int count, const ap_ln_reduce* ln_items, int ln_count,
-                              void* workspace, size_t ws_bytes, ap_stream_t stream) {
-    if (ln_count < 0 || ln_count > AP_LN_MAX_BATCH || (ln_count > 0 && !ln_items)) return AP_ERR_SHAPE;
-    for (int i = 0; i < ln_count; ++i) {
-        if (!ln_items[i].partial || !ln_items[i].dgamma || !ln_items[i].dbeta) return AP_ERR_NULL;
-        if (ln_items[i].n_partial <= 0 || ln_items[i].C <= 0) return AP_ERR_SHAPE;
+// the 192 x 192-tile kernel (tn_plan.h: tn8_plan) with the LayerNorm riders behind its table
+static int tn_launch_8p(const ap_tn_problem* problems, int count, const T8Plan& plan, TnLn ln, int lblocks, ap_stream_t stream) {
+    T8Group g8;
+    for (int i = 0; i < count; ++i) {
+        const ap_tn_problem& q = problems[i];
+        T8Item& t = g8.p[i];
+        t.A = reinterpret_cast<const bf16_t*>(q.A); t.B = reinterpret_cast<const bf16_t*>(q.B); t.C = q.C; t.colsum = q.colsum_A;
+        t.cs_weight = reinterpret_cast<const bf16_t*>(q.colsum_weight);
+        t.lda = q.lda; t.ldb = q.ldb; t.ldc = q.ldc; t.M = q.M; t.t2 = q.N2 / 192; t.ksteps = q.M / 64; t.ksps = plan.ksps;
+        t.alpha = tn_alpha(q.alpha); t.cs_scale = tn_cs_scale(q.colsum_weight, q.colsum_scale);
+        t.shared_out = plan.shared_out[i];
+        g8.tiles[i] = plan.pl[i].tiles;
     }
-    {
-        const int rcv = tn_validate(problems, count);
-        if (rcv != AP_OK) return rcv;
-    }
-    if (!workspace) {
-        // the 192 x 192-tile LDS-DMA kernel takes the problems that fit it (with the LayerNorm riders); the rest of the group -- e.g. the
-        // 486-wide attention-weight projection of an outlooker block -- goes on in launches of the 128 x 128-tile kernel, 8 problems each
-        const int n_cu = ap_cu_count();
-        ap_tn_problem fit[AP_TN_MAX_GROUP], rest[AP_TN_MAX_GROUP];
-        int nfit = 0, nrest = 0;
-        for (int i = 0; i < count; ++i) { if (tn8_fits(problems[i])) fit[nfit++] = problems[i]; else rest[nrest++] = problems[i]; }
-        T8Group g8; T8Map map8; int mb8 = 0;
-        bool riders_done = false;
-        if (nfit > 0 && tn8_plan(fit, nfit, n_cu, g8, map8, mb8)) {
-            TnLn ln;
-            int lblocks = 0;
-            for (int i = 0; i < AP_LN_MAX_BATCH; ++i) {
-                if (i < ln_count) {
-                    const ap_ln_reduce& q = ln_items[i];
-                    ln.it[i] = TnLnItem{q.partial, q.dgamma, q.dbeta, q.n_partial, q.C}; lblocks += (2 * q.C + 31) / 32;
-                } else ln.it[i] = TnLnItem{nullptr, nullptr, nullptr, 0, 0};
-            }
-            ln.count = ln_count; ln.first = mb8;
-            if (const int rca = ap_allow_lds<k_gemm_tn_8p>(T8_LDS_BYTES); rca != AP_OK) return rca;
-            (void)hipGetLastError();
-            hipLaunchKernelGGL(k_gemm_tn_8p, dim3(mb8 + lblocks), dim3(512), T8_LDS_BYTES, (hipStream_t)stream, g8, map8, ln);
-            const int rc8 = ap_check_launch();
-            if (rc8 != AP_OK) return rc8;
-            riders_done = true;
-        } else { for (int i = 0; i < nfit; ++i) rest[nrest++] = fit[i]; }
-        if (nrest == 0 && riders_done) return AP_OK;
-        if (nrest > TN_MAX_GROUP || (nrest > 0 && riders_done)) {
-            for (int i0 = 0; i0 < nrest; i0 += TN_MAX_GROUP) {
-                const int n = nrest - i0 < TN_MAX_GROUP ? nrest - i0 : TN_MAX_GROUP;
-                const bool with_ln = !riders_done;
-                const int rcc = tn_grouped_128(rest + i0, n, with_ln ? ln_items : nullptr, with_ln ? ln_count : 0, nullptr, 0, stream);
-                if (rcc != AP_OK) return rcc;
-                riders_done = true;
-            }
-            return AP_OK;
-        }
-    }
-    return tn_grouped_128(problems, count, ln_items, ln_count, workspace, ws_bytes, stream);
+    for (int i = count; i < AP_TN_MAX_GROUP; ++i) { g8.p[i] = g8.p[0]; g8.tiles[i] = 1; }
+    ln.first = plan.blocks;
+    if (const int rc = ap_allow_lds<k_gemm_tn_8p>(T8_LDS_BYTES); rc != AP_OK) return rc;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_gemm_tn_8p, dim3(plan.blocks + lblocks), dim3(512), T8_LDS_BYTES, (hipStream_t)stream, g8, plan.map, ln);
+    return ap_check_launch();
 }
 
 // the 128 x 128-tile kernels: at most TN_MAX_GROUP problems, optional deterministic mode
 static int tn_grouped_128(const ap_tn_problem* problems, int count, const ap_ln_reduce* ln_items, int ln_count,
                           void* workspace, size_t ws_bytes, ap_stream_t stream) {
     bool ln_done = ln_count == 0;
-    TnGroup grp; int blocks = 0; size_t fl = 0;
-    const int rc = tn_plan(problems, count, grp, blocks, fl);
-    if (rc != AP_OK) return rc;
+    TnGroupPlan plan; TnGroup grp;
+    if (const int rc = tn_group_args(problems, count, plan, grp); rc != AP_OK) return rc;
+    const int blocks = plan.blocks;
     if (workspace) {                                  // deterministic: stored partial tiles + ordered reduce instead of fp32 atomics
-        if (ws_bytes < fl * sizeof(float)) return AP_ERR_SHAPE;
-        float* w = reinterpret_cast<float*>(workspace);
-        for (int i = 0; i < count; ++i) {
-            grp.p[i].slab = w;
-            w += (size_t)grp.p[i].splits * ((size_t)grp.p[i].N1 * grp.p[i].N2 + (grp.p[i].colsum ? (size_t)grp.p[i].N1 : 0));
-        }
+        if (ws_bytes < plan.slab_floats * sizeof(float)) return AP_ERR_SHAPE;
+        for (int i = 0; i < count; ++i) grp.p[i].slab = reinterpret_cast<float*>(workspace) + plan.slab_off[i];
     }
     (void)hipGetLastError();
     bool any_patch = false;
@@ -1481,20 +1271,13 @@ static int tn_grouped_128(const ap_tn_problem* problems, int count, const ap_ln_
         if (problems[0].b_bn) hipLaunchKernelGGL(k_gemm_tn_patch<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grp.p[0], bbn);
         else hipLaunchKernelGGL(k_gemm_tn_patch<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grp.p[0], bbn);
     } else {
-        static int place = -1;
-        if (place < 0) { const char* e = getenv("AP_GEMM_TN_PLACE"); place = e ? atoi(e) : 1; }
+        static const int place = tn_env("AP_GEMM_TN_PLACE", 1);
         const int cap = 2 * ap_cu_count() / 8;                                                                  // resident workgroups per XCD
         TnMap map; int mblocks = 0;
-        if (place && tn_place(grp, cap, map, mblocks)) {
-            TnLn ln;
-            int lblocks = 0;
-            for (int i = 0; i < AP_LN_MAX_BATCH; ++i) {
-                if (i < ln_count) {
-                    const ap_ln_reduce& q = ln_items[i];
-                    ln.it[i] = TnLnItem{q.partial, q.dgamma, q.dbeta, q.n_partial, q.C}; lblocks += (2 * q.C + 31) / 32;
-                } else ln.it[i] = TnLnItem{nullptr, nullptr, nullptr, 0, 0};
-            }
-            ln.count = ln_count; ln.first = mblocks;
+        if (place && tn128_place(plan, cap, map, mblocks)) {
+            TnLn ln; int lblocks = 0;
+            tn_ln_table(ln_items, ln_count, ln, lblocks);           // (checked by the entry point)
+            ln.first = mblocks;
             hipLaunchKernelGGL(k_gemm_tn_grouped_map, dim3(mblocks + lblocks), dim3(256), 0, (hipStream_t)stream, grp, map, ln);
             ln_done = true;
         } else hipLaunchKernelGGL(k_gemm_tn_grouped, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grp);
@@ -1507,154 +1290,84 @@ static int tn_grouped_128(const ap_tn_problem* problems, int count, const ap_ln_
     return ap_check_launch();
 }
 
+int ap_gemm_tn_acc_grouped_ln(const ap_tn_problem* problems, int count, const ap_ln_reduce* ln_items, int ln_count,
+                              void* workspace, size_t ws_bytes, ap_stream_t stream) {
+    TnLn ln; int lblocks = 0;
+    if (const int rc = tn_ln_table(ln_items, ln_count, ln, lblocks); rc != AP_OK) return rc;
+    if (const int rc = tn_validate(problems, count, AP_TN_MAX_GROUP); rc != AP_OK) return rc;
+    TnDispatch d;
+    tn_dispatch(problems, count, workspace != nullptr, workspace ? 0 : ap_cu_count(), tn_8p_enabled(), d);
+    for (int k = 0; k < d.n; ++k) {
+        const TnLaunch& l = d.l[k];
+        ap_tn_problem sub[AP_TN_MAX_GROUP];
+        for (int i = 0; i < l.count; ++i) sub[i] = problems[d.order[l.first + i]];
+        const int rc = l.kernel == TN_KERNEL_8P ? tn_launch_8p(sub, l.count, d.p8, ln, lblocks, stream)
+                                                : tn_grouped_128(sub, l.count, l.riders ? ln_items : nullptr, l.riders ? ln_count : 0, workspace, ws_bytes, stream);
+        if (rc != AP_OK) return rc;
+    }
+    return AP_OK;
+}
+
 // ---- fp8 weight gradients (gemm_tn_fp8.h)
-static int tf_plan(const ap_tn8_problem* problems, int count, TfGroup& grp, int& blocks, size_t& slab_floats) {
-    if (!problems) return AP_ERR_NULL;
-    if (count <= 0 || count > AP_TN_MAX_GROUP) return AP_ERR_SHAPE;
-    for (int i = 0; i < count; ++i) {
-        const ap_tn8_problem& q = problems[i];
-        if (!q.A || !q.B || !q.C || !q.dq_a || !q.dq_b) return AP_ERR_NULL;
-        if (q.M <= 0 || q.N1 <= 0 || q.N2 <= 0 || q.M > AP_MAX_ROWS) return AP_ERR_SHAPE;
-        if ((q.lda & 15) || (q.ldb & 15) || q.lda < q.N1 || q.ldb < q.N2 || q.ldc < q.N2) return AP_ERR_SHAPE;
-        if ((reinterpret_cast<uintptr_t>(q.A) & 15) || (reinterpret_cast<uintptr_t>(q.B) & 15)) return AP_ERR_SHAPE;
-        if (q.N1 % 128 || q.N2 % 128 || (q.a_fmt != AP_FP8_E5M2 && q.a_fmt != AP_FP8_E4M3)) return AP_ERR_UNSUPPORTED;
-    }
-    // resident capacity: two 256-thread workgroups per CU (32 KB of LDS each); the smallest K-steps per workgroup (>= 4) that fits it once
-    const int capacity = 2 * ap_cu_count();
-    int max_k = 1;
-    for (int i = 0; i < count; ++i) max_k = std::max(max_k, (problems[i].M + 127) / 128);
-    auto blocks_at = [&](int sps) {
-        int64_t nb = 0;
-        for (int i = 0; i < count; ++i) {
-            const ap_tn8_problem& q = problems[i];
-            nb += (int64_t)(q.N1 / 128) * (q.N2 / 128) * (((q.M + 127) / 128 + sps - 1) / sps);
-        }
-        return nb;
-    };
-    // K-steps per workgroup: the smallest time in rounds of resident workgroups, ceil(blocks / capacity) * (sps + 4) (the 4: a partial tile's
-    // epilogue and its atomics in K-step units) -- a launch with more tiles than resident slots is cut along the tokens too, so its last
-    // round is not a nearly empty second wave of whole-axis workgroups
-    int lo = 4;
-    int64_t best = -1;
-    for (int sps = 4; sps <= std::max(max_k, 4); ++sps) {
-        const int64_t nb = blocks_at(sps), cost = ((nb + capacity - 1) / capacity) * (sps + 4);
-        if (best < 0 || cost < best) { best = cost; lo = sps; }
-    }
+static int tf_group_args(const ap_tn8_problem* problems, int count, TnGroupPlan& plan, TfGroup& grp) {
+    if (const int rc = tf_plan(problems, count, 2 * ap_cu_count(), plan); rc != AP_OK) return rc;       // (validates every problem)
     grp.count = count;
-    int start = 0;
-    slab_floats = 0;
     for (int i = 0; i < count; ++i) {
         const ap_tn8_problem& q = problems[i];
+        const TnItemPlan& p = plan.p[i];
         TfItem& t = grp.p[i];
-        const int ksteps = (q.M + 127) / 128;
-        int splits = (ksteps + lo - 1) / lo;
-        const int sps = (ksteps + splits - 1) / splits;
-        splits = (ksteps + sps - 1) / sps;
         t.A = q.A; t.B = q.B; t.C = q.C; t.slab = nullptr; t.dq_a = q.dq_a; t.dq_b = q.dq_b;
         t.lda = q.lda; t.ldb = q.ldb; t.ldc = q.ldc; t.M = q.M; t.N1 = q.N1; t.N2 = q.N2;
-        t.t2 = q.N2 / 128; t.ksteps = ksteps; t.ksps = sps; t.splits = splits; t.tiles = (q.N1 / 128) * (q.N2 / 128);
-        t.start = start; t.alpha = q.alpha != 0.0f ? q.alpha : 1.0f; t.a_fmt = q.a_fmt;
-        t.shared_out = 0;
-        for (int j = 0; j < count; ++j)
-            if (j != i && problems[j].C == q.C) t.shared_out = 1;
-        slab_floats += (size_t)splits * q.N1 * q.N2;
-        start += t.tiles * splits;
+        t.t2 = p.t2; t.ksteps = p.steps; t.ksps = p.sps; t.splits = p.splits; t.tiles = p.t1 * p.t2;
+        t.start = p.start; t.alpha = tn_alpha(q.alpha); t.a_fmt = q.a_fmt; t.shared_out = p.shared_out;
     }
     for (int i = count; i < AP_TN_MAX_GROUP; ++i) { grp.p[i] = grp.p[0]; grp.p[i].start = 0x7fffffff; }
-    blocks = start;
     return AP_OK;
 }
 
 size_t ap_gemm_tn8_grouped_workspace(const ap_tn8_problem* problems, int count) {
-    TfGroup grp; int blocks = 0; size_t fl = 0;
-    if (tf_plan(problems, count, grp, blocks, fl) != AP_OK) return 0;
-    return fl * sizeof(float);
+    TnGroupPlan plan; TfGroup grp;
+    return tf_group_args(problems, count, plan, grp) == AP_OK ? plan.slab_floats * sizeof(float) : 0;
 }
 
 int ap_gemm_tn8_acc_grouped(const ap_tn8_problem* problems, int count, void* workspace, size_t ws_bytes, ap_stream_t stream) {
     return ap_gemm_tn8_acc_grouped_ln(problems, count, nullptr, 0, workspace, ws_bytes, stream);
 }
 
-// the 8-phase fp8 flavour: widths multiples of 192, whole 128-token K-tiles, M >= 4096, one A format per launch (AP_GEMM_TN_8P=0: off)
-static bool tf8_fits(const ap_tn8_problem& q, int a_fmt) {
-    static int enabled = -1;
-    if (enabled < 0) { const char* e = getenv("AP_GEMM_TN_8P"); enabled = e ? atoi(e) : 1; }
-    return enabled && q.a_fmt == a_fmt && q.N1 % 192 == 0 && q.N2 % 192 == 0 && q.M % 128 == 0 && q.M >= 4096;
-}
-// as tn8_plan: the token axis cut into ranges of ksps 128-token K-tiles, the smallest that leaves at most one item per CU and fits t8_place
-static bool tf8_plan(const ap_tn8_problem* problems, int count, int n_cu, T8GroupF8& g8, T8Map& map, int& mblocks) {
-    int64_t work = 0; int max_k = 1;
-    for (int i = 0; i < count; ++i) {
-        const ap_tn8_problem& q = problems[i];
-        if (!tf8_fits(q, problems[0].a_fmt)) return false;
-        work += (int64_t)(q.N1 / 192) * (q.N2 / 192) * (q.M / 128);
-        max_k = std::max(max_k, q.M / 128);
-    }
-    int ksps = std::max(4, (int)((work + n_cu - 1) / n_cu));
-    T8Plan pl[AP_TN_MAX_GROUP];
-    for (; ksps <= max_k; ++ksps) {
-        int64_t items = 0;
-        for (int i = 0; i < count; ++i) {
-            const int ksteps = problems[i].M / 128;
-            pl[i].tiles = (problems[i].N1 / 192) * (problems[i].N2 / 192); pl[i].splits = (ksteps + ksps - 1) / ksps;
-            items += (int64_t)pl[i].tiles * pl[i].splits;
-        }
-        if (items <= n_cu && t8_place(pl, count, n_cu / 8, map, mblocks)) break;
-    }
-    if (ksps > max_k) return false;
-    for (int i = 0; i < count; ++i) {
-        const ap_tn8_problem& q = problems[i];
-        T8ItemF8& t = g8.p[i];
-        t.A = q.A; t.B = q.B; t.C = q.C; t.dq_a = q.dq_a; t.dq_b = q.dq_b;
-        t.lda = q.lda; t.ldb = q.ldb; t.ldc = q.ldc; t.M = q.M; t.t2 = q.N2 / 192; t.ksteps = q.M / 128; t.ksps = ksps;
-        t.alpha = q.alpha != 0.0f ? q.alpha : 1.0f;
-        g8.tiles[i] = pl[i].tiles;
-        t.shared_out = 0;
-        for (int j = 0; j < count; ++j)
-            if (j != i && problems[j].C == q.C) t.shared_out = 1;
-    }
-    for (int i = count; i < AP_TN_MAX_GROUP; ++i) { g8.p[i] = g8.p[0]; g8.tiles[i] = 1; }
-    return true;
-}
-
 int ap_gemm_tn8_acc_grouped_ln(const ap_tn8_problem* problems, int count, const ap_ln_reduce* ln_items, int ln_count,
                                void* workspace, size_t ws_bytes, ap_stream_t stream) {
-    if (ln_count < 0 || ln_count > AP_LN_MAX_BATCH || (ln_count > 0 && !ln_items)) return AP_ERR_SHAPE;
-    for (int i = 0; i < ln_count; ++i) {
-        if (!ln_items[i].partial || !ln_items[i].dgamma || !ln_items[i].dbeta) return AP_ERR_NULL;
-        if (ln_items[i].n_partial <= 0 || ln_items[i].C <= 0) return AP_ERR_SHAPE;
-    }
-    TfGroup grp; int blocks = 0; size_t fl = 0;
-    const int rc = tf_plan(problems, count, grp, blocks, fl);         // (validates every problem)
-    if (rc != AP_OK) return rc;
-    TnLn ln;
-    int lblocks = 0;
-    for (int i = 0; i < AP_LN_MAX_BATCH; ++i) {
-        if (i < ln_count) {
-            const ap_ln_reduce& q = ln_items[i];
-            ln.it[i] = TnLnItem{q.partial, q.dgamma, q.dbeta, q.n_partial, q.C}; lblocks += (2 * q.C + 31) / 32;
-        } else ln.it[i] = TnLnItem{nullptr, nullptr, nullptr, 0, 0};
-    }
-    ln.count = ln_count;
-    if (!workspace) {                                 // atomic mode: the 8-phase flavour when every problem fits it
-        const int n_cu = ap_cu_count();
-        T8GroupF8 g8; T8Map map8; int mb8 = 0;
-        if (tf8_plan(problems, count, n_cu, g8, map8, mb8)) {
-            ln.first = mb8;
-            const bool e5 = problems[0].a_fmt == AP_FP8_E5M2;
-            if (const int rca = e5 ? ap_allow_lds<k_gemm_tn_8p_fp8<AP_FP8_E5M2>>(T8_LDS_BYTES) : ap_allow_lds<k_gemm_tn_8p_fp8<AP_FP8_E4M3>>(T8_LDS_BYTES); rca != AP_OK) return rca;
-            (void)hipGetLastError();
-            if (e5)
-                hipLaunchKernelGGL(k_gemm_tn_8p_fp8<AP_FP8_E5M2>, dim3(mb8 + lblocks), dim3(512), T8_LDS_BYTES, (hipStream_t)stream, g8, map8, ln);
-            else
-                hipLaunchKernelGGL(k_gemm_tn_8p_fp8<AP_FP8_E4M3>, dim3(mb8 + lblocks), dim3(512), T8_LDS_BYTES, (hipStream_t)stream, g8, map8, ln);
-            return ap_check_launch();
+    TnLn ln; int lblocks = 0;
+    if (const int rc = tn_ln_table(ln_items, ln_count, ln, lblocks); rc != AP_OK) return rc;
+    TnGroupPlan plan; TfGroup grp;
+    if (const int rc = tf_group_args(problems, count, plan, grp); rc != AP_OK) return rc;
+    const int blocks = plan.blocks;
+    T8Plan p8;
+    if (!workspace && tf8_plan(problems, count, ap_cu_count(), tn_8p_enabled(), p8)) {        // atomic mode: the 8-phase flavour when every problem fits it
+        T8GroupF8 g8;
+        for (int i = 0; i < count; ++i) {
+            const ap_tn8_problem& q = problems[i];
+            T8ItemF8& t = g8.p[i];
+            t.A = q.A; t.B = q.B; t.C = q.C; t.dq_a = q.dq_a; t.dq_b = q.dq_b;
+            t.lda = q.lda; t.ldb = q.ldb; t.ldc = q.ldc; t.M = q.M; t.t2 = q.N2 / 192; t.ksteps = q.M / 128; t.ksps = p8.ksps;
+            t.alpha = tn_alpha(q.alpha);
+            t.shared_out = p8.shared_out[i];
+            g8.tiles[i] = p8.pl[i].tiles;
         }
+        for (int i = count; i < AP_TN_MAX_GROUP; ++i) { g8.p[i] = g8.p[0]; g8.tiles[i] = 1; }
+        const int mb8 = p8.blocks;
+        ln.first = mb8;
+        const bool e5 = problems[0].a_fmt == AP_FP8_E5M2;
+        if (const int rca = e5 ? ap_allow_lds<k_gemm_tn_8p_fp8<AP_FP8_E5M2>>(T8_LDS_BYTES) : ap_allow_lds<k_gemm_tn_8p_fp8<AP_FP8_E4M3>>(T8_LDS_BYTES); rca != AP_OK) return rca;
+        (void)hipGetLastError();
+        if (e5)
+            hipLaunchKernelGGL(k_gemm_tn_8p_fp8<AP_FP8_E5M2>, dim3(mb8 + lblocks), dim3(512), T8_LDS_BYTES, (hipStream_t)stream, g8, p8.map, ln);
+        else
+            hipLaunchKernelGGL(k_gemm_tn_8p_fp8<AP_FP8_E4M3>, dim3(mb8 + lblocks), dim3(512), T8_LDS_BYTES, (hipStream_t)stream, g8, p8.map, ln);
+        return ap_check_launch();
     }
     if (workspace) {                                  // deterministic: stored partial tiles + ordered reduce instead of fp32 atomics
-        if (ws_bytes < fl * sizeof(float)) return AP_ERR_SHAPE;
-        float* w = reinterpret_cast<float*>(workspace);
-        for (int i = 0; i < count; ++i) { grp.p[i].slab = w; w += (size_t)grp.p[i].splits * grp.p[i].N1 * grp.p[i].N2; }
+        if (ws_bytes < plan.slab_floats * sizeof(float)) return AP_ERR_SHAPE;
+        for (int i = 0; i < count; ++i) grp.p[i].slab = reinterpret_cast<float*>(workspace) + plan.slab_off[i];
     }
     ln.first = blocks;
     (void)hipGetLastError();
