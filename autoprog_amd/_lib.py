@@ -195,6 +195,9 @@ _SIGNATURES["ap_grad_health"] = (_I, [_P, _L, _P, _I, _P, _P, _P, _F, _F, _P, ct
 _SIGNATURES["ap_adamw_ema_step_guarded"] = (_I, _SIGNATURES["ap_adamw_ema_step"][1][:-1] + [_P, _P])
 # the step that also emits bf16 copies of EMA slabs: (... p_bf16, ema_bf16[4] (host array, null = not this copy), guard_or_null, stream)
 _SIGNATURES["ap_adamw_ema_step_ema16"] = (_I, _SIGNATURES["ap_adamw_ema_step"][1][:-1] + [POINTER(c_void_p), _P, _P])
+# the step with per-group learning rates and decays: wd_mask's place holds group_id (uint8 per element), and in front of the stream
+# (... p_bf16, ema_bf16[4] or null, guard_or_null, group_tab_dev (n_groups x {lr, weight_decay} fp32), n_groups, stream)
+_SIGNATURES["ap_adamw_ema_step_groups"] = (_I, _SIGNATURES["ap_adamw_ema_step_ema16"][1][:-1] + [_P, _I, _P])
 # row-wise softmax + top-K (csrc/topk.hip): ap_softmax_topk_rows(logits, ld, C, K, inv_temp, idx, val, o_sb, o_sn, rows_per_batch, M, stream)
 _SIGNATURES["ap_softmax_topk_rows"] = (_I, [_P, _I, _I, _I, _F, _P, _P, _L, _L, _I, _L, _P])
 # distillation loss (csrc/distill.hip): ap_distill_fwd_bwd(student, ld_s, teacher, ld_t, C, mode, inv_temp, row_loss, dstudent, grad_scale, M, stream)

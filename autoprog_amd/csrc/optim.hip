@@ -31,18 +31,44 @@ template <class Base> struct Ema16Args : Base { bf16_t* ema16[4]; };
 template <class T> struct has_ema16 { static constexpr bool value = false; };
 template <class Base> struct has_ema16<Ema16Args<Base>> { static constexpr bool value = true; };
 
+// Arguments of ap_adamw_ema_step_groups: any set above plus a device table of {lr, weight_decay} per parameter group.  The byte slab the
+// kernel reads per element (`wd_mask` in the other instantiations) then holds the element's GROUP; a.lr and a.wd are not read.  Every
+// workgroup forms the two numbers a group contributes -- the decay factor 1 - lr*wd and the step size lr / bc1 -- once, in LDS, and the
+// inner loop looks both up per element (a float4 may straddle groups: tensors of odd length sit back to back in the slab).  The
+// instantiations without the table declare no LDS and compile to the code they were.
+struct AdamGroupEntry { float lr, wd; };
+template <class Base> struct GroupArgs : Base { const AdamGroupEntry* group_tab; int n_groups; };
+template <class T> struct is_grouped { static constexpr bool value = false; };
+template <class Base> struct is_grouped<GroupArgs<Base>> { static constexpr bool value = true; };
+template <class Base> struct has_ema16<GroupArgs<Base>> { static constexpr bool value = has_ema16<Base>::value; };
+constexpr int ADAM_MAX_GROUPS = 256;                   // one byte per element
+
 template <class Args>
 __global__ void __launch_bounds__(256)
 k_adamw_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
             const unsigned char* __restrict__ wd_mask, int64_t n, Args a, bf16_t* __restrict__ p16) {
     constexpr bool GUARD = __is_base_of(AdamGuardArgs, Args);
     constexpr bool E16 = has_ema16<Args>::value;
+    constexpr bool GROUPED = is_grouped<Args>::value;
     const int64_t nv = n >> 2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    if (a.step_dev) { a.lr = a.step_dev[0]; a.bc1 = a.step_dev[1]; a.bc2_sqrt = a.step_dev[2]; }
+    if constexpr (GROUPED) { if (a.step_dev) { a.bc1 = a.step_dev[1]; a.bc2_sqrt = a.step_dev[2]; } }      // (the rates come from the table)
+    else if (a.step_dev) { a.lr = a.step_dev[0]; a.bc1 = a.step_dev[1]; a.bc2_sqrt = a.step_dev[2]; }
     bool skip = false;
     if constexpr (GUARD) { skip = a.guard->nonfinite != 0; a.bc1 = a.guard->bc1; a.bc2_sqrt = a.guard->bc2_sqrt; }
     const float step_size = a.lr / a.bc1;
+    const float2* tab = nullptr;                       // per group {1 - lr*wd, lr / bc1}
+    if constexpr (GROUPED) {
+        __shared__ float2 s_tab[ADAM_MAX_GROUPS];
+        // the ungrouped kernel's two numbers in the forms its instructions have: the factor is ONE fma (its 1.0f - a.lr * a.wd is
+        // contracted), the step size an IEEE division.  Written out, so that no choice of the compiler's separates the two kernels.
+        for (int gi = threadIdx.x; gi < a.n_groups; gi += blockDim.x) {
+            const AdamGroupEntry t = a.group_tab[gi];
+            s_tab[gi] = make_float2(__builtin_fmaf(-t.lr, t.wd, 1.0f), t.lr / a.bc1);
+        }
+        __syncthreads();
+        tab = s_tab;
+    }
     // gradient clipping folded into the update (prog/scaler.py:60-68 -> timm dispatch_clip_grad, main_prog.py:1019-1027):
     // mode 'norm' = torch.nn.utils.clip_grad_norm_: coef = min(1, max_norm / (||g|| + 1e-6)) with ||g|| the norm of the MEAN gradient
     // (gscale * the norm of the slab, which holds the all-reduced SUM under a deferred mean); mode 'value': clamp every element
@@ -66,11 +92,20 @@ k_adamw_ema(float* __restrict__ p, const float* __restrict__ g, float* __restric
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float x = P[k];
-                if (W[k]) x *= (1.0f - a.lr * a.wd);                         // decoupled weight decay (torch AdamW order)
+                if constexpr (!GROUPED) { if (W[k]) x *= (1.0f - a.lr * a.wd); }    // decoupled weight decay (torch AdamW order)
                 M[k] = a.beta1 * M[k] + (1.0f - a.beta1) * G[k];
                 V[k] = a.beta2 * V[k] + (1.0f - a.beta2) * G[k] * G[k];
                 const float denom = sqrtf(V[k]) / a.bc2_sqrt + a.eps;
-                P[k] = x - step_size * (M[k] / denom);
+                if constexpr (GROUPED) {
+                    // the ungrouped update rounds the decayed weight on its own (a select stands between its product and the
+                    // subtraction) and then takes ONE fma; times 1.0f for an un-decayed group is exact.  The fma is spelled out: left to
+                    // contraction, x * f - s * q could fuse the other product.
+                    const float2 t = tab[W[k]];
+                    x *= t.x;
+                    P[k] = __builtin_fmaf(-t.y, M[k] / denom, x);
+                } else {
+                    P[k] = x - step_size * (M[k] / denom);
+                }
             }
             reinterpret_cast<float4*>(p)[i] = pp;
             if (p16) { u32x2 o; o[0] = pack_bf2(pp.x, pp.y); o[1] = pack_bf2(pp.z, pp.w); reinterpret_cast<u32x2*>(p16)[i] = o; }
@@ -137,13 +172,25 @@ extern "C" int ap_sumsq_f32(const float* x, int64_t n, float* out, void* workspa
     return ap_check_launch();
 }
 
+// the grouped launch of one argument set: the same arguments under one more layer, the byte slab read as group numbers
+template <class Base>
+static void adamw_ema_launch_grouped(const Base& base, const float* group_tab, int n_groups, unsigned grid, hipStream_t stream, float* p,
+                                     const float* g, float* m, float* v, const unsigned char* group_id, int64_t n, bf16_t* p16) {
+    GroupArgs<Base> ga;
+    static_cast<Base&>(ga) = base;
+    ga.group_tab = reinterpret_cast<const AdamGroupEntry*>(group_tab);
+    ga.n_groups = n_groups;
+    hipLaunchKernelGGL(k_adamw_ema<GroupArgs<Base>>, dim3(grid), dim3(256), 0, stream, p, g, m, v, group_id, n, ga, p16);
+}
+
 // the argument checks and the launch all entry points share; `guard` selects the guarded instantiation, `ema16` (an array of 4, entries
-// past n_ema already checked to be null) the ones that emit bf16 copies of EMA slabs
+// past n_ema already checked to be null) the ones that emit bf16 copies of EMA slabs, `group_tab` (n_groups already checked) the ones
+// that read wd_mask as group numbers
 static int adamw_ema_launch(float* p, const float* g, float* m, float* v, const unsigned char* wd_mask, int64_t n,
                             float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
                             const float* gnorm_sq, float max_norm, float clip_value, const float* step_scalars_dev,
                             float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, const ap_guard_state* guard, ap_stream_t stream,
-                            ap_bf16* const* ema16 = nullptr) {
+                            ap_bf16* const* ema16 = nullptr, const float* group_tab = nullptr, int n_groups = 0) {
     if (!p || !g || !m || !v || !wd_mask) return AP_ERR_NULL;
     if (n <= 0 || (n & 3) || n_ema < 0 || n_ema > 4 || step < 1) return AP_ERR_SHAPE;
     if (gnorm_sq && !(max_norm > 0.f)) return AP_ERR_SHAPE;
@@ -160,6 +207,24 @@ static int adamw_ema_launch(float* p, const float* g, float* m, float* v, const 
     int64_t grid = (n / 4 + 255) / 256;
     if (grid > 256 * 16) grid = 256 * 16;
     (void)hipGetLastError();
+    if (group_tab) {                                    // the same four argument sets, grouped
+        hipStream_t s = (hipStream_t)stream;
+        bf16_t* p16 = reinterpret_cast<bf16_t*>(p_bf16);
+        if (ema16 && (ema16[0] || ema16[1] || ema16[2] || ema16[3])) {
+            Ema16Args<AdamGuardArgs> b;
+            static_cast<AdamGuardArgs&>(b) = a;
+            for (int e = 0; e < 4; ++e) b.ema16[e] = reinterpret_cast<bf16_t*>(ema16[e]);
+            if (guard) adamw_ema_launch_grouped(b, group_tab, n_groups, (unsigned)grid, s, p, g, m, v, wd_mask, n, p16);
+            else {
+                Ema16Args<AdamArgs> c;
+                static_cast<AdamArgs&>(c) = a;
+                for (int e = 0; e < 4; ++e) c.ema16[e] = b.ema16[e];
+                adamw_ema_launch_grouped(c, group_tab, n_groups, (unsigned)grid, s, p, g, m, v, wd_mask, n, p16);
+            }
+        } else if (guard) adamw_ema_launch_grouped(a, group_tab, n_groups, (unsigned)grid, s, p, g, m, v, wd_mask, n, p16);
+        else adamw_ema_launch_grouped(static_cast<const AdamArgs&>(a), group_tab, n_groups, (unsigned)grid, s, p, g, m, v, wd_mask, n, p16);
+        return ap_check_launch();
+    }
     // (four null entries: nothing to emit, the launch is the one without the pointers)
     if (ema16 && (ema16[0] || ema16[1] || ema16[2] || ema16[3])) {
         Ema16Args<AdamGuardArgs> b;
@@ -216,6 +281,26 @@ extern "C" int ap_adamw_ema_step_ema16(float* p, const float* g, float* m, float
     }
     return adamw_ema_launch(p, g, m, v, wd_mask, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, gnorm_sq, max_norm, clip_value,
                             step_scalars_dev, ema, ema_decay, n_ema, p_bf16, guard_or_null, stream, ema_bf16);
+}
+
+// the step with one learning rate and one weight decay per parameter group (include/autoprog_hip.h): group_id[n] in the place of wd_mask,
+// group_tab_dev[n_groups] of {lr, weight_decay}.  ema_bf16 is nullable here; the checks of ap_adamw_ema_step_ema16 apply to a given one.
+// A byte >= n_groups is the caller's error (the kernel reads its own 256-entry LDS table, nothing outside it).  Everything is checked
+// before anything is launched.
+extern "C" int ap_adamw_ema_step_groups(float* p, const float* g, float* m, float* v, const unsigned char* group_id, int64_t n,
+                                        float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                                        const float* gnorm_sq, float max_norm, float clip_value, const float* step_scalars_dev,
+                                        float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, ap_bf16* const* ema_bf16,
+                                        const ap_guard_state* guard_or_null, const float* group_tab_dev, int n_groups, ap_stream_t stream) {
+    if (!group_id || !group_tab_dev) return AP_ERR_NULL;
+    if (n_groups < 1 || n_groups > ADAM_MAX_GROUPS || ((uintptr_t)group_tab_dev & 7)) return AP_ERR_SHAPE;
+    if (n_ema < 0 || n_ema > 4) return AP_ERR_SHAPE;
+    for (int e = 0; ema_bf16 && e < 4; ++e) {
+        if (!ema_bf16[e]) continue;
+        if (e >= n_ema || ((uintptr_t)ema_bf16[e] & 7)) return AP_ERR_SHAPE;
+    }
+    return adamw_ema_launch(p, g, m, v, group_id, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, gnorm_sq, max_norm, clip_value,
+                            step_scalars_dev, ema, ema_decay, n_ema, p_bf16, guard_or_null, stream, ema_bf16, group_tab_dev, n_groups);
 }
 
 // ---- gradient health (ap_grad_health): per parameter tensor the sum of squares of the finite elements (fp64) and the number of

@@ -142,8 +142,11 @@ class GraphedStep:
         self.scalars.begin()
         self._draw()
         o = self.opt
-        self.scalars.set_adam(o.param_groups[0]["lr"], o.betas[0], o.betas[1], o.step_count + 1)
+        g0 = o.param_groups[0]
+        self.scalars.set_adam(float(g0["lr"]) * float(g0.get("lr_scale", 1.0)), o.betas[0], o.betas[1], o.step_count + 1)
         self.scalars.push()
+        if getattr(o, "grouped", False):       # per-group rates and decays: the replay reads the table as it stands at THIS step
+            o.push_groups()
 
     def _step_body(self):
         self.reducer.zero_grad()
@@ -162,6 +165,11 @@ class GraphedStep:
             self.opt._guard_workspace(self.images.device)         # (the same rule for the guard's table, outputs, record and workspace)
         if self.clip_grad is not None and float(self.clip_grad) > 0 and self.clip_mode == "norm":
             self.opt._clip_workspace(self.images.device)          # (never first allocated inside the capture: optim.FlatAdamWEma._clip_workspace)
+        # which optimizer launch the graph holds: the one with a parameter-group table or the one without.  Its buffers follow the same
+        # rule as the workspaces above; step() refuses to replay once the optimizer's groups ask for the other launch
+        self._grouped = bool(getattr(self.opt, "grouped", False))
+        if self._grouped:
+            self.opt._group_workspace(self.images.device)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -182,6 +190,9 @@ class GraphedStep:
     def step(self, images=None, target=None):
         if self.graph is None:
             raise RuntimeError("GraphedStep.step() before capture()")
+        if bool(getattr(self.opt, "grouped", False)) != self._grouped:
+            raise RuntimeError("GraphedStep.step(): the optimizer's parameter groups now need the %s launch, the graph holds the other one: "
+                               "recapture" % ("grouped" if not self._grouped else "ungrouped"))
         if images is not None:
             _copy_images(self.images, images)
         if target is not None:

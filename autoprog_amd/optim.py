@@ -5,7 +5,11 @@
 the whole update in one kernel (`ap_adamw_ema_step`).  Semantics = `torch.optim.AdamW` with timm's
 no-weight-decay rule (1-D params, biases and `model.no_weight_decay()` names get wd 0)
 followed by `ModelEmaV2.update` for each decay.  Floating-point BUFFERS (BatchNorm running stats) are
-EMA-averaged with torch foreach ops, as ModelEmaV2 averages the whole state dict."""
+EMA-averaged with torch foreach ops, as ModelEmaV2 averages the whole state dict.
+
+Parameter groups: `FlatAdamWEma(param_groups=[...])` takes torch.optim-style groups with their own "lr", "lr_scale" and "weight_decay"
+(`ap_adamw_ema_step_groups`: the group of every element in the byte the decay mask was, the groups' values in a small device table);
+`layer_decay_param_groups` builds the groups of layer-wise learning-rate decay for the DeiT and VOLO models."""
 import ctypes
 
 import torch
@@ -35,15 +39,165 @@ def grad_segments(reducer, model=None):
     return offsets, out_names
 
 
+MAX_PARAM_GROUPS = 256                   # the update kernel reads a parameter's group from one byte per element
+
+
+def resolve_param_groups(params, groups, lr, weight_decay, betas, eps, names=None):
+    """an explicit `param_groups=` list of FlatAdamWEma against the parameters it must cover.  groups: torch.optim-style dicts -- "params"
+    (required: a list of parameters, or one), "lr" / "weight_decay" (default: the constructor's), "lr_scale" (optional; step() multiplies
+    the group's "lr" by it), any other key carried along untouched.  -> (the optimizer's group dicts, {id(parameter): group index}).
+    ValueError naming the parameter when one of `params` is in no group or in two, or a group holds a parameter that is not among
+    `params`; for more than 256 groups; for betas / eps that differ from the optimizer's (one pair of moments, one kernel).  Needs no
+    device."""
+    names = names or {}
+
+    def label(p):
+        return repr(names[id(p)]) if id(p) in names else "a parameter of shape %s" % (tuple(p.shape),)
+    groups = list(groups)
+    if not 1 <= len(groups) <= MAX_PARAM_GROUPS:
+        raise ValueError("FlatAdamWEma: %d parameter groups, the update kernel takes 1 .. %d" % (len(groups), MAX_PARAM_GROUPS))
+    owned = {id(p) for p in params}
+    group_of, out = {}, []
+    for gi, g in enumerate(groups):
+        if not isinstance(g, dict) or "params" not in g:
+            raise ValueError("FlatAdamWEma: parameter group %d is not a dict with a \"params\" entry" % gi)
+        ps = [g["params"]] if torch.is_tensor(g["params"]) else list(g["params"])
+        for p in ps:
+            if id(p) not in owned:
+                raise ValueError("FlatAdamWEma: parameter group %d holds %s, which is not among the reducer's parameters" % (gi, label(p)))
+            if id(p) in group_of:
+                raise ValueError("FlatAdamWEma: %s is in parameter groups %d and %d" % (label(p), group_of[id(p)], gi))
+            group_of[id(p)] = gi
+        d = {"lr": lr, "weight_decay": weight_decay, "betas": betas, "eps": eps}
+        d.update((k, v) for k, v in g.items() if k != "params")
+        if tuple(d["betas"]) != tuple(betas) or d["eps"] != eps:
+            raise ValueError("FlatAdamWEma: parameter group %d sets its own betas / eps; the flat-slab step has one pair for all groups" % gi)
+        d["params"] = ps
+        out.append(d)
+    missing = [label(p) for p in params if id(p) not in group_of]
+    if missing:
+        raise ValueError("FlatAdamWEma: %d parameter(s) are in no parameter group: %s" % (len(missing), ", ".join(missing[:8])))
+    return out, group_of
+
+
+def _layer_ids(model):
+    """{parameter name: layer id} by the rule layer_decay_param_groups documents"""
+    from .models.deit import VisionTransformer
+    from .models.volo import VOLO, Downsample
+    ids = {}
+    if isinstance(model, VisionTransformer):
+        last = len(model.blocks) + 1
+        for name, _ in model.named_parameters():
+            top = name.split(".")[0]
+            if top in ("cls_token", "dist_token", "pos_embed", "patch_embed"):
+                ids[name] = 0
+            elif top == "blocks":
+                ids[name] = int(name.split(".")[1]) + 1
+            elif top in ("norm", "head", "head_dist"):
+                ids[name] = last
+            else:
+                raise ValueError("layer_decay_param_groups: no layer id for parameter %r of %s" % (name, type(model).__name__))
+        return ids
+    if isinstance(model, VOLO):
+        entry_id, block_id, pending, nxt = {}, {}, [], 1
+        for i, entry in enumerate(model.network):
+            if i == 2:
+                pending.append("pos_embed")                      # (added in front of network[2]: VOLO.forward_tokens)
+            if isinstance(entry, Downsample):
+                pending.append(i)
+            elif isinstance(entry, (torch.nn.Sequential, torch.nn.ModuleList)):
+                for j in range(len(entry)):
+                    if pending:                                  # what stands in front of this block takes its id
+                        for key in pending:
+                            entry_id[key] = nxt
+                        pending = []
+                    block_id[(i, j)] = nxt
+                    nxt += 1
+            else:
+                raise ValueError("layer_decay_param_groups: no layer id for network[%d] (%s)" % (i, type(entry).__name__))
+        last = nxt
+        if len(model.network) <= 2:
+            pending.append("pos_embed")
+        for key in pending:
+            entry_id[key] = last                                 # (nothing behind it but the heads)
+        for name, _ in model.named_parameters():
+            parts = name.split(".")
+            top = parts[0]
+            if top == "patch_embed":
+                ids[name] = 0
+            elif top == "pos_embed":
+                ids[name] = entry_id["pos_embed"]
+            elif top == "network":
+                i = int(parts[1])
+                ids[name] = entry_id[i] if i in entry_id else block_id[(i, int(parts[2]))]
+            elif top in ("post_network", "cls_token", "norm", "head", "aux_head"):
+                ids[name] = last
+            else:
+                raise ValueError("layer_decay_param_groups: no layer id for parameter %r of VOLO" % (name,))
+        return ids
+    raise ValueError("layer_decay_param_groups: layer ids are defined for models.deit.VisionTransformer (and its distilled form) and "
+                     "models.volo.VOLO, not for %s" % type(model).__name__)
+
+
+def layer_decay_param_groups(model, weight_decay, layer_decay, lr=None):
+    """layer-wise learning-rate decay (the ViT / DeiT fine-tuning recipe) as a `param_groups=` list for FlatAdamWEma: one group per
+    (layer id, decayed or not) pair, in ascending id order, the decayed group first; empty groups are left out.  Each group has
+        "lr_scale"      layer_decay ** (L - id), L the largest id: 1 for the heads, smaller towards the stem.  FlatAdamWEma.step()
+                        multiplies the group's "lr" by it, so a scheduler that writes ONE value into every group's "lr" (timm 0.4.5's
+                        do) keeps the groups apart;
+        "weight_decay"  `weight_decay`, or 0 by the no-decay rule of the default groups (1-D parameters, names ending in ".bias",
+                        model.no_weight_decay());
+        "name"          "layer_<id>_decay" / "layer_<id>_no_decay", for logs;
+        "lr"            only when `lr` is given (else the constructor's).
+    Parameters with requires_grad False are left out (the reducer does not own them).  The layer ids are this project's own:
+      models.deit.VisionTransformer / DistilledVisionTransformer (depth d):
+        0       cls_token, dist_token, pos_embed, patch_embed.*
+        i + 1   blocks.i.*
+        d + 1   norm.*, head.*, head_dist.*
+      models.volo.VOLO:
+        0       patch_embed.*
+        1 ..    the blocks of `network`, numbered in forward order across the stages by their index in the SUPERNET: an identity
+                layer of an elastic configuration keeps its number (the map does not follow set_sample_config)
+                a Downsample entry and pos_embed: the id of the first block behind them
+        last block id + 1   post_network.*, cls_token, norm.*, head.*, aux_head.*
+    Any other module: ValueError."""
+    ids = _layer_ids(model)
+    top = max(ids.values())
+    skip = set(model.no_weight_decay()) if hasattr(model, "no_weight_decay") else set()
+    buckets = {}
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        decay = not (p.dim() == 1 or name.endswith(".bias") or name in skip)
+        buckets.setdefault((ids[name], 0 if decay else 1), []).append(p)
+    groups = []
+    for (lid, nodecay), ps in sorted(buckets.items()):
+        g = {"params": ps, "weight_decay": 0.0 if nodecay else weight_decay, "lr_scale": float(layer_decay) ** (top - lid),
+             "name": "layer_%d_%s" % (lid, "no_decay" if nodecay else "decay")}
+        if lr is not None:
+            g["lr"] = lr
+        groups.append(g)
+    return groups
+
+
 class FlatAdamWEma:
-    def __init__(self, model, reducer, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, ema_decays=()):
+    def __init__(self, model, reducer, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, ema_decays=(), param_groups=None):
+        """param_groups: None -- the two groups of timm's create_optimizer (decayed, then un-decayed parameters) -- or an explicit
+        torch.optim-style list (resolve_param_groups; layer_decay_param_groups builds one): every parameter of `reducer.params` in
+        exactly one group, at most 256 groups.  step() reads every group's "lr", "lr_scale" (default 1) and "weight_decay" each call."""
         assert len(ema_decays) <= 4
         self.model, self.reducer = model, reducer
         self.betas, self.eps = betas, eps
         # torch.optim-style groups (timm's create_optimizer layout: decayed, then un-decayed parameters).  step() reads
         # `lr` / `weight_decay` from here every call, so timm LR schedulers that write param_groups[i]["lr"] work unchanged.
-        self.param_groups = [{"lr": lr, "weight_decay": weight_decay, "betas": betas, "eps": eps, "params": []},
-                             {"lr": lr, "weight_decay": 0.0, "betas": betas, "eps": eps, "params": []}]
+        self._explicit_groups = param_groups is not None
+        names = {id(p): n_ for n_, p in model.named_parameters()}
+        if self._explicit_groups:
+            self.param_groups, group_of = resolve_param_groups(reducer.params, param_groups, lr, weight_decay, betas, eps, names)
+        else:
+            self.param_groups = [{"lr": lr, "weight_decay": weight_decay, "betas": betas, "eps": eps, "params": []},
+                                 {"lr": lr, "weight_decay": 0.0, "betas": betas, "eps": eps, "params": []}]
+        self._groups = None                                      # the grouped launch's device buffers (_group_workspace)
         self.ema_decays = list(ema_decays)
         self.step_count = 0
         flat_g = reducer.flat
@@ -52,11 +206,12 @@ class FlatAdamWEma:
         dev = flat_g.device
         self.p = torch.zeros(self.n_pad, dtype=torch.float32, device=dev)
         self.g = flat_g if self.n_pad == n else None
-        self.wd_mask = torch.zeros(self.n_pad, dtype=torch.uint8, device=dev)
+        # (an explicit group list always takes the grouped launch, which reads `group_id` in the mask's place)
+        self.wd_mask = None if self._explicit_groups else torch.zeros(self.n_pad, dtype=torch.uint8, device=dev)
         skip = set(model.no_weight_decay()) if hasattr(model, "no_weight_decay") else set()
-        names = {id(p): n_ for n_, p in model.named_parameters()}
         base = flat_g.data_ptr()
         self._views = []
+        self._group_of = []                                      # per parameter of reducer.params: its group (static: it follows the parameter)
         for p in reducer.params:
             off = (p.grad.data_ptr() - base) // 4
             view = self.p[off:off + p.numel()].view_as(p)
@@ -64,9 +219,13 @@ class FlatAdamWEma:
             p.data = view                                   # parameters now live in the slab
             name = names.get(id(p), "")
             decay = not (p.dim() == 1 or name.endswith(".bias") or name in skip)
-            if decay:
+            if decay and self.wd_mask is not None:
                 self.wd_mask[off:off + p.numel()] = 1
-            self.param_groups[0 if decay else 1]["params"].append(p)
+            if self._explicit_groups:
+                self._group_of.append(group_of[id(p)])
+            else:
+                self.param_groups[0 if decay else 1]["params"].append(p)
+                self._group_of.append(0 if decay else 1)
             self._views.append((name, off, p.shape))
         self.m = torch.zeros_like(self.p)
         self.v = torch.zeros_like(self.p)
@@ -122,6 +281,61 @@ class FlatAdamWEma:
     @property
     def weight_decay(self):
         return self.param_groups[0]["weight_decay"]
+
+    # ------------------------------------------------------------------ per-group learning rates and decays
+    @staticmethod
+    def _lr_eff(group):
+        return float(group["lr"]) * float(group.get("lr_scale", 1.0))
+
+    @property
+    def grouped(self):
+        """which launch the next step() makes: False -- the entry points without a group table, whenever they can express the groups
+        (built with param_groups=None, both groups at one effective learning rate, no decay in group 1) --, True --
+        ap_adamw_ema_step_groups.  An optimizer built with an explicit group list is always grouped, so the choice is fixed for a
+        captured graph; on a default-built one it follows what was last written into param_groups (GraphedStep checks)."""
+        if self._explicit_groups:
+            return True
+        g0, g1 = self.param_groups
+        return not (self._lr_eff(g0) == self._lr_eff(g1) and float(g1["weight_decay"]) == 0.0)
+
+    def _group_workspace(self, device):
+        """the buffers of the grouped launch, allocated once and OUTSIDE any stream capture (see _clip_workspace; GraphedStep.capture()
+        calls this first): `group_id`, one byte per element of the padded slab from the parameters' slab offsets (the tail padding goes
+        to group 0), the device table [G, 2] of {lr * lr_scale, weight_decay} and the pinned ring its host side is written into."""
+        if self._groups is None:
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FlatAdamWEma: the parameter-group buffers must exist before a step is captured (call _group_workspace first)")
+            from .ring import PinnedRing
+            ids = torch.zeros(self.n_pad, dtype=torch.uint8)
+            for gi, (_, off, shape) in zip(self._group_of, self._views):
+                n = 1
+                for d in shape:
+                    n *= d
+                ids[off:off + n] = gi
+            self._groups = {"group_id": ids.to(device), "table": torch.zeros(len(self.param_groups), 2, dtype=torch.float32, device=device),
+                            "ring": PinnedRing(device), "pushed": False}
+        return self._groups
+
+    @property
+    def group_id(self):
+        """the uint8 slab of the grouped launch (None until the grouped path is first used)"""
+        return self._groups["group_id"] if self._groups is not None else None
+
+    def group_table(self):
+        """[G, 2] fp32 on the host: what the next push_groups() sends -- per group lr_eff = float32(lr * lr_scale), float32(weight_decay)"""
+        return torch.tensor([[self._lr_eff(g), float(g["weight_decay"])] for g in self.param_groups], dtype=torch.float64).to(torch.float32)
+
+    def push_groups(self):
+        """the groups' current rates and decays into the ONE device table the grouped launch reads: the host writes the next slot of a
+        ring.PinnedRing and one small asynchronous copy is enqueued (the rule of graph.StepScalars).  An eager step() calls this in front
+        of its launch; a step replayed from a graph does not contain the copy (a captured copy would read a ring slot that has since
+        rotated) -- GraphedStep calls this in front of every replay."""
+        gw = self._group_workspace(self.reducer.flat.device)
+        host = gw["ring"].next(2 * len(self.param_groups), torch.float32)
+        host.copy_(self.group_table().reshape(-1))
+        gw["table"].view(-1).copy_(host, non_blocking=True)
+        gw["ring"].record()
+        gw["pushed"] = True
 
     def _stamp_versions(self):
         for p in self.reducer.params:
@@ -319,7 +533,10 @@ class FlatAdamWEma:
         Adam's step number t (the APPLIED steps, for the bias corrections) stay on the device: nothing is read back, a replayed graph
         skips like an eager step.  `step_count` keeps counting calls; guard_counts() / grad_health() report.  `last_grad_norm` of a
         skipped step is non-finite (it is the norm of the whole slab).  Use the flag for every step of a run or for none: an unguarded
-        step takes t from `step_count`."""
+        step takes t from `step_count`.
+        Parameter groups: every group's "lr" * "lr_scale" (default 1) and "weight_decay" are read at every call.  While the two default
+        groups share one rate and group 1 has no decay the launch is the one it always was; any other setting, and every optimizer built
+        with param_groups=, takes ap_adamw_ema_step_groups (`grouped`).  Clipping and the guard are global, not per group."""
         g = self.reducer.flat
         gd = self._guard_workspace(g.device) if skip_nonfinite else None     # (before the count moves: the record starts at the steps made so far)
         self.step_count += 1
@@ -347,13 +564,23 @@ class FlatAdamWEma:
                 clip_value = float(clip_grad)
             else:
                 raise NotImplementedError("FlatAdamWEma.step: clip_mode %r (the reference's default is 'norm'; 'agc' is not on the flat-slab path)" % (clip_mode,))
-        lr, wd = float(self.param_groups[0]["lr"]), float(self.param_groups[0]["weight_decay"])
-        if float(self.param_groups[1]["lr"]) != lr:
-            raise ValueError("FlatAdamWEma: both parameter groups must share one learning rate (timm schedulers do)")
-        args = (self.p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.wd_mask.data_ptr(),
+        lr, wd = self._lr_eff(self.param_groups[0]), float(self.param_groups[0]["weight_decay"])
+        grouped = self.grouped
+        if grouped:
+            # one rate and one decay per group, from the device table: an eager step sends the table first; a step under `scalars` (a
+            # captured one) does not -- the copy belongs in front of the replay (push_groups; graph.GraphedStep._prepare)
+            if scalars is None:
+                self.push_groups()
+            gw = self._group_workspace(g.device)
+            if not gw["pushed"]:
+                raise RuntimeError("FlatAdamWEma.step(scalars=...): the parameter-group table was never sent (call push_groups() first)")
+        args = (self.p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), (gw["group_id"] if grouped else self.wd_mask).data_ptr(),
                 self.n_pad, lr, self.betas[0], self.betas[1], self.eps, wd, self.step_count, gscale,
                 gnorm_ptr, max_norm, clip_value, scalars.adam_ptr if scalars is not None else None, self._ema_ptrs, self._ema_decay, len(self.ema), self.p16.data_ptr())
-        if self._shadows:                                    # some EMA copy is a network: the same update, and its bf16 copy in the same pass
+        if grouped:                                          # (the four argument sets of the launches below behind one symbol)
+            check(lib.ap_adamw_ema_step_groups(*args, self._ema16_ptrs if self._shadows else None, gd["state"].data_ptr() if skip_nonfinite else None,
+                                               gw["table"].data_ptr(), len(self.param_groups), ops._stream()), "ap_adamw_ema_step_groups")
+        elif self._shadows:                                  # some EMA copy is a network: the same update, and its bf16 copy in the same pass
             check(lib.ap_adamw_ema_step_ema16(*args, self._ema16_ptrs, gd["state"].data_ptr() if skip_nonfinite else None, ops._stream()),
                   "ap_adamw_ema_step_ema16")
         elif skip_nonfinite:
@@ -474,6 +701,8 @@ class FlatAdamWEma:
     def load_state_dict(self, sd):
         offs = {id(p): off for p, (_, off, _) in zip(self.reducer.params, self._views)}
         idx = 0
+        if len(sd["param_groups"]) != len(self.param_groups):
+            raise ValueError("FlatAdamWEma.load_state_dict: the state has %d parameter groups, the optimizer %d" % (len(sd["param_groups"]), len(self.param_groups)))
         with torch.no_grad():
             for g, saved in zip(self.param_groups, sd["param_groups"]):
                 for k, v in saved.items():

@@ -617,6 +617,25 @@ int ap_adamw_ema_step_ema16(float* p, const float* g, float* m, float* v, const 
                             const float* gnorm_sq, float max_norm, float clip_value, const float* step_scalars_dev,
                             float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, ap_bf16* const* ema_bf16,
                             const ap_guard_state* guard_or_null, ap_stream_t stream);
+/* The same step with one learning rate and one weight decay PER PARAMETER GROUP (additive in ABI version 7): torch.optim.AdamW with
+ * param_groups -- layer-wise learning-rate decay, a head trained faster than the body, a frozen group (lr 0).  In the place of wd_mask
+ * the kernel reads group_id[n], one byte per element (the same traffic), and group_tab_dev[n_groups], a DEVICE table of {lr,
+ * weight_decay} fp32 pairs (8-byte aligned, 1 <= n_groups <= 256).  Element i is decayed by 1 - lr*wd and stepped by lr / (1 - beta1^t)
+ * of group group_id[i]; every workgroup forms the two numbers per group once, in LDS.  Groups may change at any element: tensors of odd
+ * length sit back to back in the slab.  A byte group_id[i] >= n_groups is the CALLER's error: the kernel cannot afford to check the
+ * bytes and would read LDS it never wrote (no memory outside the workgroup's own table of 256 entries).
+ * The `lr` and `weight_decay` arguments and step_scalars_dev[0] are NOT read; the bias corrections come from where they come in the
+ * other entry points (the host's `step`, step_scalars_dev[1..2], or the guard record).  Clipping (gnorm_sq / max_norm, clip_value) and
+ * grad_scale are global as before; the guard, the EMA lerps, p_bf16 and ema_bf16 are unchanged.  ema_bf16 is NULLABLE here (NULL or
+ * four NULL entries: nothing is emitted), guard_or_null selects the guarded step.  With a table in which every decayed element's group
+ * is {lr, wd} and every other element's {lr, 0} all outputs are bit for bit those of the entry points above.
+ * Refused before anything is launched: group_id == NULL or group_tab_dev == NULL (AP_ERR_NULL); n_groups < 1 or > 256, a table that is
+ * not 8-byte aligned (AP_ERR_SHAPE); and everything ap_adamw_ema_step_ema16 refuses. */
+int ap_adamw_ema_step_groups(float* p, const float* g, float* m, float* v, const unsigned char* group_id, int64_t n,
+                             float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                             const float* gnorm_sq, float max_norm, float clip_value, const float* step_scalars_dev,
+                             float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, ap_bf16* const* ema_bf16,
+                             const ap_guard_state* guard_or_null, const float* group_tab_dev, int n_groups, ap_stream_t stream);
 /* transpose `count` bf16 matrices of one slab in one launch: desc_dev = device array of
  * {int64 src_off, int64 dst_off, int rows, int cols, int ld_dst, int first_tile} (32x32 tiles, first_tile
  * = running tile prefix); dst[dst_off + c*ld_dst + r] = src[src_off + r*cols + c], pad columns zeroed */
