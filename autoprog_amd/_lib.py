@@ -213,6 +213,10 @@ _SIGNATURES["ap_crop_resample_u8"] = (_I, [POINTER(CropResampleArgs), _P])
 _SIGNATURES["ap_randaug_u8"] = (_I, [POINTER(RandAugArgs), _P])
 # stored top-k label maps -> the pairs of a SparseTokenLabelTarget, ROI-aligned to each image's crop box (csrc/labelmap.hip)
 _SIGNATURES["ap_label_map_crop"] = (_I, [POINTER(LabelMapCropArgs), _P])
+# adaptive gradient clipping on the gradient slab (csrc/agc.hip): ap_agc_clip(g, p, n, unit_off, unit_skip, n_units, clip_factor, eps,
+# grad_scale, unit_factor_or_null, counts_or_null, stream)
+_SIGNATURES["ap_agc_clip"] = (_I, [_P, _P, _L, _P, _P, _I, _F, _F, _F, _P, _P, _P])
+_SIGNATURES["ap_agc_short_max"] = (_I, [])
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 EXPECTED_ABI = 7                     # ap_abi_version() of the library these ctypes Structures mirror (include/autoprog_hip.h)

@@ -29,6 +29,9 @@ from . import ops
 from .ring import PinnedRing
 
 
+CLIP_MODES = ("norm", "value", "agc")        # the reference's --clip-mode (main_prog.py:129-132)
+
+
 class StepScalars:
     """the per-step host scalars of a training step in device memory.  Layout (16 x 4 bytes; include/autoprog_hip.h ap_step_scalars):
          int32 [0..3]  mix-token box on the token-label grid: bbx1, bbx2, bby1, bby2 (rows [bbx1, bbx2), columns [bby1, bby2))
@@ -104,11 +107,16 @@ class DeviceBox:
 class GraphedStep:
     def __init__(self, model, loss_fn, reducer, opt, images, target, clip_grad=None, clip_mode="norm", skip_nonfinite=False):
         """skip_nonfinite: FlatAdamWEma.step's flag.  The guarded launch sequence reads its decision, its counters and Adam's step number
-        from device memory (ap_guard_state), so a replay skips or applies like an eager step and needs no further per-step copy."""
+        from device memory (ap_guard_state), so a replay skips or applies like an eager step and needs no further per-step copy.
+        clip_mode: 'norm' / 'value' go to FlatAdamWEma.step; 'agc' is opt.adaptive_clip_grad(clip_grad) between reducer.finish() and a
+        step() without clip arguments (clip_grad is then timm's clip_factor).  Any other mode is refused here."""
+        if clip_mode not in CLIP_MODES:
+            raise ValueError("GraphedStep: clip_mode %r, expected one of %s" % (clip_mode, ", ".join(repr(m) for m in CLIP_MODES)))
         if getattr(reducer, "world", 1) > 1:
             raise ValueError("GraphedStep: single-rank only (the gradient exchange is not captured)")
         self.model, self.loss_fn, self.reducer, self.opt = model, loss_fn, reducer, opt
         self.clip_grad, self.clip_mode = clip_grad, clip_mode
+        self._agc = clip_mode == "agc" and clip_grad is not None and float(clip_grad) > 0
         self.skip_nonfinite = bool(skip_nonfinite)
         # a data.PreparedBatch in place of the images: a static uint8 buffer and a static copy of the step's parameter block (mix mode, lam,
         # CutMix box, noise key, erase records), refreshed by ONE device copy in front of every replay; the loss reads lam from that block
@@ -153,10 +161,12 @@ class GraphedStep:
         loss = self.loss_fn(self.model(self.images), self.target)
         loss.backward()
         self.reducer.finish()
-        if self.skip_nonfinite:
-            self.opt.step(clip_grad=self.clip_grad, clip_mode=self.clip_mode, scalars=self.scalars, skip_nonfinite=True)
+        kw = {"skip_nonfinite": True} if self.skip_nonfinite else {}
+        if self._agc:                                             # the slab is rewritten in front of the update, which then clips nothing
+            self.opt.adaptive_clip_grad(self.clip_grad)
+            self.opt.step(scalars=self.scalars, **kw)
         else:
-            self.opt.step(clip_grad=self.clip_grad, clip_mode=self.clip_mode, scalars=self.scalars)
+            self.opt.step(clip_grad=self.clip_grad, clip_mode=self.clip_mode, scalars=self.scalars, **kw)
         return loss
 
     def capture(self, warmup=3):
@@ -165,6 +175,8 @@ class GraphedStep:
             self.opt._guard_workspace(self.images.device)         # (the same rule for the guard's table, outputs, record and workspace)
         if self.clip_grad is not None and float(self.clip_grad) > 0 and self.clip_mode == "norm":
             self.opt._clip_workspace(self.images.device)          # (never first allocated inside the capture: optim.FlatAdamWEma._clip_workspace)
+        if self._agc:
+            self.opt._agc_workspace(self.images.device)           # (the same rule for the unit table, the factors and the tallies)
         # which optimizer launch the graph holds: the one with a parameter-group table or the one without.  Its buffers follow the same
         # rule as the workspaces above; step() refuses to replay once the optimizer's groups ask for the other launch
         self._grouped = bool(getattr(self.opt, "grouped", False))

@@ -1392,3 +1392,29 @@ def grad_health(g, seg_off, seg_sumsq, seg_nonfinite, state, workspace, beta1=0.
     check(lib.ap_grad_health(g.data_ptr(), g.numel(), seg_off.data_ptr(), n_seg, seg_sumsq.data_ptr(), seg_nonfinite.data_ptr(), state.data_ptr(),
                              float(beta1), float(beta2), workspace.data_ptr(), workspace.numel() * 8, _stream()), "ap_grad_health")
     return seg_sumsq, seg_nonfinite
+
+
+def agc_short_max():
+    """the longest unit ap_agc_clip reads once, one wave per unit; a longer one takes a workgroup and a second walk"""
+    return int(lib.ap_agc_short_max())
+
+
+def agc_clip(g, p, unit_off, unit_skip, clip_factor, eps=1e-3, grad_scale=1.0, unit_factor=None, counts=None):
+    """ap_agc_clip: adaptive gradient clipping of the fp32 gradient slab `g`, in place, against the parameters `p` (fp32, as long as g,
+    only read) and the device unit table `unit_off` (int64 [n_units + 1], ascending from 0 to g.numel()) / `unit_skip` (uint8 [n_units],
+    non-zero: leave the unit alone).  Per unit: gn = grad_scale * ||g||, bound = max(||p||, eps) * clip_factor, and where gn >= bound
+    the unit is multiplied by bound / max(gn, 1e-6); a unit with a non-finite gradient element is left alone (the rule in full:
+    include/autoprog_hip.h).  unit_factor (fp32 [n_units], optional) receives the factor applied, 1 for a unit left alone; counts (int32
+    [2], optional) {clipped units, non-finite units}.  Every buffer is the caller's: nothing is allocated."""
+    _req(g, torch.float32, "g"); _req(p, torch.float32, "p"); _req(unit_off, torch.int64, "unit_off"); _req(unit_skip, torch.uint8, "unit_skip")
+    n_units = unit_off.numel() - 1
+    if n_units < 1 or unit_skip.numel() != n_units or p.numel() != g.numel():
+        raise AutoProgHipError("agc_clip: p as long as g, a table of n_units + 1 bounds and n_units skip bytes")
+    if unit_factor is not None and _req(unit_factor, torch.float32, "unit_factor").numel() != n_units:
+        raise AutoProgHipError("agc_clip: unit_factor holds one fp32 per unit")
+    if counts is not None and _req(counts, torch.int32, "counts").numel() != 2:
+        raise AutoProgHipError("agc_clip: counts holds two int32")
+    check(lib.ap_agc_clip(g.data_ptr(), p.data_ptr(), g.numel(), unit_off.data_ptr(), unit_skip.data_ptr(), n_units, float(clip_factor), float(eps),
+                          float(grad_scale), unit_factor.data_ptr() if unit_factor is not None else None,
+                          counts.data_ptr() if counts is not None else None, _stream()), "ap_agc_clip")
+    return g

@@ -39,7 +39,56 @@ def grad_segments(reducer, model=None):
     return offsets, out_names
 
 
-MAX_PARAM_GROUPS = 256                   # the update kernel reads a parameter's group from one byte per element
+def agc_units(reducer, model=None, exclude=None):
+    """the unit table of adaptive gradient clipping (ap_agc_clip; the rule: include/autoprog_hip.h) for the reducer's slab, in slab order,
+    read from where each gradient view sits as grad_segments reads its segments.  A parameter tensor with ndim <= 1 is one unit; one with
+    ndim >= 2 has shape[0] units of numel / shape[0] contiguous elements (a Linear [out, in]: `out` rows; a conv [O, I, k, k]: O units;
+    pos_embed [1, g, g, C] and cls_token [1, 1, C]: one unit each).  An excluded tensor is ONE unit with its skip byte set.
+    exclude: None -- the reference's rule, timm's model_parameters(model, exclude_head=True) = list(model.parameters())[:-2]: the LAST TWO
+    parameters of model.parameters() are excluded, whatever they are called.  That is head.weight / head.bias for VOLO and DeiT, and
+    head_dist.weight / head_dist.bias -- not head.* -- for a distilled DeiT; aux_head is never excluded.  (Without a model: nothing.)
+    An iterable of parameter names and / or parameters replaces the rule; () excludes nothing.  An unknown name is a ValueError.
+    -> (offsets, skip, names): offsets has one entry more than there are units, ascending from 0 to the slab's length; skip[u] is 1 for an
+    excluded tensor's unit; names[u] is "blocks.3.mlp.fc1.weight[17]" for row 17 of a tensor cut into rows, the tensor's name for a tensor
+    that is one unit."""
+    flat = reducer.flat
+    base = flat.data_ptr()
+    by_name = dict(model.named_parameters()) if model is not None else {}
+    names = {id(p): n for n, p in by_name.items()}
+    if exclude is None:
+        excluded = {id(p) for p in list(model.parameters())[-2:]} if model is not None else set()
+    else:
+        excluded = set()
+        for item in ([exclude] if isinstance(exclude, str) or torch.is_tensor(exclude) else exclude):
+            if isinstance(item, str):
+                if item not in by_name:
+                    raise ValueError("agc_units: exclude names %r, which is not a parameter of the model" % (item,))
+                excluded.add(id(by_name[item]))
+            else:
+                excluded.add(id(item))
+    items = sorted(((p.grad.data_ptr() - base) // flat.element_size(), i) for i, p in enumerate(reducer.params))
+    offsets, skip, out_names = [0], [], []
+    for off, i in items:
+        p = reducer.params[i]
+        name, n = names.get(id(p), ""), p.numel()
+        if off != offsets[-1]:
+            raise ValueError("agc_units: the gradient of %r starts at %d, the slab is covered up to %d" % (name, off, offsets[-1]))
+        rows = p.shape[0] if p.dim() >= 2 else 1
+        if id(p) in excluded or rows <= 1 or n == 0:
+            offsets.append(off + n)
+            skip.append(1 if id(p) in excluded else 0)
+            out_names.append(name)
+        else:
+            w = n // rows
+            offsets.extend(range(off + w, off + n + 1, w))
+            skip.extend([0] * rows)
+            out_names.extend("%s[%d]" % (name, r) for r in range(rows))
+    if offsets[-1] != flat.numel():
+        raise ValueError("agc_units: the gradients cover %d of the slab's %d elements" % (offsets[-1], flat.numel()))
+    return offsets, skip, out_names
+
+
+MAX_PARAM_GROUPS = 256                  # the update kernel reads a parameter's group from one byte per element
 
 
 def resolve_param_groups(params, groups, lr, weight_decay, betas, eps, names=None):
@@ -262,6 +311,7 @@ class FlatAdamWEma:
         # model.load_state_dict() copies INTO the slab views (pointers unchanged): re-derive the bf16 copies afterwards
         self._load_hook = model.register_load_state_dict_post_hook(lambda module, incompatible: self.resync())
         self._guard = None                                       # the non-finite guard's device buffers (_guard_workspace)
+        self._agc = None                                         # adaptive gradient clipping's unit table and outputs (_agc_workspace)
         # EMA copies as networks (ema_model): the bf16 slab of copy i while its shadow module lives (else None), the shadow modules,
         # and the launch-constant pointer array ap_adamw_ema_step_ema16 reads (a null entry: that copy is not emitted)
         self.ema16 = [None] * len(self.ema)
@@ -515,12 +565,67 @@ class FlatAdamWEma:
         count = host[8 * n_seg:].view(torch.int32).tolist()
         return list(zip(gd["names"], sumsq, count))
 
+    # ------------------------------------------------------------------ adaptive gradient clipping (the reference's --clip-mode agc)
+    def _agc_workspace(self, device, exclude=None):
+        """the buffers of adaptive_clip_grad, allocated once and OUTSIDE any stream capture (see _clip_workspace; GraphedStep.capture()
+        calls this first): the unit table and skip bytes of agc_units, and ONE buffer holding the two tallies (int32) and the per-unit
+        factors (fp32) -- one read-back for agc_report().  exclude: None keeps the table that exists (the default rule of agc_units when
+        there is none yet); anything else builds the table for that exclusion, again only outside a capture."""
+        ws = self._agc
+        if ws is not None and exclude is None:
+            return ws
+        key = None
+        if exclude is not None:
+            key = tuple(exclude) if not (isinstance(exclude, str) or torch.is_tensor(exclude)) else (exclude,)
+            key = tuple(x if isinstance(x, str) else id(x) for x in key)
+            if ws is not None and ws["key"] == key:
+                return ws
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FlatAdamWEma: the AGC unit table and outputs must exist before a step is captured (call _agc_workspace first)")
+        offsets, skip, names = agc_units(self.reducer, self.model, exclude)
+        n_units = len(names)
+        out = torch.zeros(2 + n_units, dtype=torch.float32, device=device)
+        self._agc = {"key": key, "names": names, "n": offsets[-1], "n_units": n_units, "used": False,
+                     "table": torch.tensor(offsets, dtype=torch.int64).to(device), "skip": torch.tensor(skip, dtype=torch.uint8).to(device),
+                     "out": out, "counts": out[:2].view(torch.int32), "factor": out[2:]}
+        return self._agc
+
+    def adaptive_clip_grad(self, clip_factor=0.01, eps=1e-3, exclude=None):
+        """adaptive gradient clipping (timm's adaptive_clip_grad, the reference's `--clip-mode agc`, main_prog.py:129-132, 1019-1027) of
+        the gradient slab, in place, in ONE pass (ap_agc_clip; the rule and its two stated deviations: include/autoprog_hip.h): every
+        output unit -- a row of a Linear, an output channel of a conv, a whole 1-D tensor -- whose MEAN-gradient norm reaches
+        max(||p||, eps) * clip_factor is scaled down to that bound.  Call it between reducer.finish() and step(), as timm's function
+        stands in front of optimizer.step(); step() then runs without clip arguments.  With GradientBucketReducer(defer_mean=True) the
+        slab holds the all-reduced SUM: the pass reads the pending 1/world for its norms and leaves it pending for step().
+        exclude: agc_units' -- None: the table already built, or on the first call the reference's rule (the last two of
+        model.parameters()); names / parameters replace it; () clips everything.  Nothing is read back (agc_report() does that); after the
+        first call nothing is allocated, so the pass can be captured -- call _agc_workspace before the capture."""
+        g = self.reducer.flat
+        ws = self._agc_workspace(g.device, exclude)
+        check(lib.ap_agc_clip(g.data_ptr(), self.p.data_ptr(), ws["n"], ws["table"].data_ptr(), ws["skip"].data_ptr(), ws["n_units"],
+                              float(clip_factor), float(eps), float(self.reducer.grad_scale), ws["factor"].data_ptr(), ws["counts"].data_ptr(),
+                              ops._stream()), "ap_agc_clip")
+        ws["used"] = True
+
+    def agc_report(self):
+        """the last adaptive_clip_grad pass: {"units": units in the table, "clipped": units scaled down, "nonfinite": units left alone
+        for an inf / NaN gradient element, "worst": [(unit name, factor), ...] the three smallest factors}.  ONE read-back."""
+        ws = self._agc
+        if ws is None or not ws["used"]:
+            raise RuntimeError("FlatAdamWEma.agc_report: no adaptive_clip_grad() has run yet")
+        host = ws["out"].cpu()
+        counts = host[:2].view(torch.int32)
+        val, idx = torch.topk(host[2:], min(3, ws["n_units"]), largest=False)
+        return {"units": ws["n_units"], "clipped": int(counts[0]), "nonfinite": int(counts[1]),
+                "worst": [(ws["names"][int(i)], float(v)) for v, i in zip(val, idx)]}
+
     def step(self, clip_grad=None, clip_mode="norm", scalars=None, skip_nonfinite=False):
         """one AdamW + EMA update from the gradient slab.  clip_grad / clip_mode: the reference's `--clip-grad` / `--clip-mode`
         (main_prog.py:129-132; prog/scaler.py:60-68 calls timm's dispatch_clip_grad between backward and optimizer.step()):
           'norm'  -- torch.nn.utils.clip_grad_norm_(parameters, clip_grad): ONE pass over the flat slab for the global norm
                      (ap_sumsq_f32, a device scalar), the factor min(1, clip / (norm + 1e-6)) is applied inside the update kernel;
           'value' -- clip_grad_value_: every gradient element clamped to [-clip, clip] inside the update kernel.
+        ('agc' is not a mode of this kernel and raises NotImplementedError: adaptive_clip_grad() rewrites the slab in front of step().)
         Both act on the MEAN gradient: with GradientBucketReducer(defer_mean=True) the slab still holds the all-reduced SUM and the
         1/world factor is applied first -- clipping the slab from outside before step() would be off by `world`.
         `last_grad_norm` (device scalar, 'norm' mode) is the norm of the mean gradient before clipping.
@@ -563,7 +668,8 @@ class FlatAdamWEma:
             elif clip_mode == "value":
                 clip_value = float(clip_grad)
             else:
-                raise NotImplementedError("FlatAdamWEma.step: clip_mode %r (the reference's default is 'norm'; 'agc' is not on the flat-slab path)" % (clip_mode,))
+                raise NotImplementedError("FlatAdamWEma.step: clip_mode %r is not a mode of the update kernel ('norm' and 'value' are; 'agc' rewrites the "
+                                          "gradient in front of the update: call adaptive_clip_grad(clip_grad), then step() without clip arguments)" % (clip_mode,))
         lr, wd = self._lr_eff(self.param_groups[0]), float(self.param_groups[0]["weight_decay"])
         grouped = self.grouped
         if grouped:

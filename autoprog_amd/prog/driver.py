@@ -35,7 +35,7 @@ class AutoProgDriver:
                  search_epochs=2, auto_grow=True, probe_batches=4, time_steps=4, seed=0, log=None, original_batch_splits=1,
                  r_max=None, dist_bn="", use_graphs=False, graph_after=2, clip_grad=None, clip_mode="norm", get_val_batches=None,
                  batch_prep=None, re_list=None, skip_nonfinite=False, teacher=None, crop=None, resize_list=None, *, augment=None,
-                 aa_list=None, label_maps=None):
+                 aa_list=None, label_maps=None, agc_exclude=None):
         """model: supernet sized for l_list[-1] (e.g. volo_h12_l18); optimizer: FlatAdamWEma over it; reducer: its
         GradientBucketReducer; r_list / l_list / dp_list / grow_epochs: the stage schedule (prog/progressive.py:4-31);
         get_batch(r): a training batch (images at ANY size -- the stem resizes to r -- and a token-label target for r // 16).
@@ -54,7 +54,10 @@ class AutoProgDriver:
         replay one graph per candidate drawn (<= 9 per search), captured on the search supernet's slabs the same way.
         With DropPath off a graphed run is bit-identical to the eager one; with it the masks come from the same generator at replay time.
         clip_grad / clip_mode: the reference's --clip-grad / --clip-mode (main_prog.py:129-132, prog/scaler.py:60-68), applied inside the fused
-        optimizer step (FlatAdamWEma.step) of every update, eager or replayed.
+        optimizer step (FlatAdamWEma.step) of every update, eager or replayed.  clip_mode "agc": adaptive gradient clipping, clip_grad is
+        timm's clip_factor -- FlatAdamWEma.adaptive_clip_grad(clip_grad) rewrites the gradient slab after the last micro-batch's finish(),
+        and step() then runs without clip arguments; agc_exclude (keyword only) is its `exclude` (None: the reference's rule, the last
+        two of model.parameters()).  An unknown clip_mode is refused here.
         get_val_batches(): an iterable of (images, labels) validation batches, called once per pass.  When given, the model and then every
         EMA copy are validated after each training epoch (main_prog.py:889-906, prog/validate.py) and the metrics (loss / top1 / top5, the
         EMA copies' with the suffix _EMA_{decay}) join that epoch's `history` entry; None (default): no validation, `history` as before.
@@ -104,6 +107,10 @@ class AutoProgDriver:
         create_token_label_target, main_prog.py:994-1004).  The launch stays outside captured graphs; the target reaches a graph as a
         teacher's does.  Token labels are not cut with Mixup / CutMix: a mixing batch_prep is refused here as beside a TeacherLabeler.  The
         geometric ops of an `augment` move pixels, not labels.  None (default): nothing changes."""
+        from ..graph import CLIP_MODES
+        if clip_mode not in CLIP_MODES:
+            raise ValueError("AutoProgDriver: clip_mode %r, expected one of %s" % (clip_mode, ", ".join(repr(m) for m in CLIP_MODES)))
+        self.agc_exclude = agc_exclude
         if label_maps is not None:
             if crop is None:
                 raise ValueError("label_maps needs a crop: the maps are cut to the boxes DeviceRandomResizedCrop draws")
@@ -257,6 +264,8 @@ class AutoProgDriver:
         images, target = self.get_batch(r)
         self.reducer.zero_grad()
         self._set_splits(1)
+        if self._agc():                                           # the unit table for THIS driver's exclusion, in front of the capture
+            self.opt._agc_workspace(self.reducer.flat.device, self.agc_exclude)
         gs = GraphedStep(self.model, self.loss_fn, self.reducer, self.opt, images, target, clip_grad=self.clip_grad, clip_mode=self.clip_mode,
                          **self._guard_kw()).capture(warmup=0)
         self._graphs[key] = gs
@@ -284,11 +293,17 @@ class AutoProgDriver:
             (loss if k == 1 else loss / k).backward()
             self.reducer.finish()
             total = loss.detach() if total is None else total + loss.detach()
-        if self.clip_grad is not None:
+        if self._agc():
+            self.opt.adaptive_clip_grad(self.clip_grad, exclude=self.agc_exclude)      # (the slab is rewritten; the update clips nothing)
+            self.opt.step(**self._guard_kw())
+        elif self.clip_grad is not None:
             self.opt.step(clip_grad=self.clip_grad, clip_mode=self.clip_mode, **self._guard_kw())
         else:
             self.opt.step(**self._guard_kw())     # (any optimizer with the plain step() of the reference's loop works when nothing is clipped or guarded)
         return total if k == 1 else total / k
+
+    def _agc(self):
+        return self.clip_mode == "agc" and self.clip_grad is not None and float(self.clip_grad) > 0
 
     def _guard_kw(self):
         return {"skip_nonfinite": True} if self.skip_nonfinite else {}

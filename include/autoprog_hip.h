@@ -636,6 +636,38 @@ int ap_adamw_ema_step_groups(float* p, const float* g, float* m, float* v, const
                              const float* gnorm_sq, float max_norm, float clip_value, const float* step_scalars_dev,
                              float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, ap_bf16* const* ema_bf16,
                              const ap_guard_state* guard_or_null, const float* group_tab_dev, int n_groups, ap_stream_t stream);
+/* ---- adaptive gradient clipping (AGC) on the flat gradient slab (additive in ABI version 7; csrc/agc.hip).  The reference's
+ * `--clip-mode agc` (main_prog.py:129-132, 1019-1027) calls timm 0.4.5's adaptive_clip_grad between backward and optimizer.step().  The
+ * rule below restates that function and its unitwise_norm from knowledge of the code; it is NOT byte-checked against timm (timm is not a
+ * dependency of this project); tests/_agc_ref.py pins it in fp64.
+ *   Units.   A parameter tensor with ndim <= 1 is one unit; a tensor with ndim >= 2 has shape[0] units, each the numel / shape[0]
+ *            contiguous elements of one leading index (a Linear [out, in]: `out` rows; a conv [O, I, k, k]: O units of I k k;
+ *            pos_embed [1, g, g, C] and cls_token [1, 1, C]: one unit each).  The caller describes them by a DEVICE table
+ *            unit_off[n_units + 1] that ascends from 0 to n and covers the slab exactly; a unit may start at any offset mod 4.
+ *   Rule.    Per unit pn = ||p||_2 and gn = grad_scale * ||g||_2 (grad_scale: the pending 1/world of a deferred data-parallel mean --
+ *            the rule acts on the MEAN gradient while the slab holds the SUM; 1 otherwise).  max_norm = max(pn, eps) * clip_factor.
+ *            gn < max_norm: the unit is left as it is.  Otherwise every element of g is multiplied by f = max_norm / max(gn, 1e-6)
+ *            (the slab stays the SUM; the pending scale stays pending).  timm's defaults: clip_factor 0.01, eps 1e-3.
+ *   Skipped. unit_skip[u] != 0 leaves unit u alone (timm's exclude_head: an excluded tensor is ONE skipped unit).
+ *   Deviation 1 (non-finite units).  A unit with an inf or NaN gradient element is left bit for bit as it is and counted; timm would
+ *            multiply it by 0 or NaN, turning an inf into NaN and zeroing its finite neighbours in front of the non-finite guard
+ *            (ap_grad_health), which reports the finite part per tensor.
+ *   Deviation 2 (arithmetic).  Both sums are of exact squares in fp64, the bound and the quotient are formed in fp64, and f is rounded
+ *            to fp32 once; timm computes all of it in the gradient's dtype.  p is expected finite.
+ * p (the fp32 master parameters, the same offsets as g) is only read.  Elements of units that are not clipped are never stored: they keep
+ * their bits, and in a healthy run the pass is close to read-only.  unit_factor_or_null[n_units] receives the factor applied, 1.0 for
+ * every unit left alone; counts_or_null[2] receives {clipped units, non-finite units} (int32; zeroed by a one-wave launch in front of the pass).
+ * Units of up to ap_agc_short_max() elements are read once, one wave per unit, g kept in registers between the norm and the
+ * store; a longer unit takes one workgroup and a second walk over g.  Fixed reduction order, no floating-point atomics: two launches on
+ * the same inputs write the same bits.  No workspace, nothing allocated; runs under stream capture.  A table entry outside [0, n] or
+ * out of order is clamped: nothing outside the slabs is read or written.
+ * Refused before anything is launched: g, p, unit_off or unit_skip NULL (AP_ERR_NULL); n <= 0, n_units <= 0, g or p not 16-byte
+ * aligned, unit_off not 8-byte or an output not 4-byte aligned, clip_factor or grad_scale not positive and finite, eps negative or not
+ * finite (AP_ERR_SHAPE). */
+int ap_agc_clip(float* g, const float* p, int64_t n, const int64_t* unit_off, const uint8_t* unit_skip, int n_units,
+                float clip_factor, float eps, float grad_scale, float* unit_factor_or_null, int32_t* counts_or_null,
+                ap_stream_t stream);
+int ap_agc_short_max(void);
 /* transpose `count` bf16 matrices of one slab in one launch: desc_dev = device array of
  * {int64 src_off, int64 dst_off, int rows, int cols, int ld_dst, int first_tile} (32x32 tiles, first_tile
  * = running tile prefix); dst[dst_off + c*ld_dst + r] = src[src_off + r*cols + c], pad columns zeroed */
