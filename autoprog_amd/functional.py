@@ -744,7 +744,13 @@ class LinearFn(torch.autograd.Function):
         K = x.shape[-1]
         x2 = x.reshape(-1, K).contiguous()
         N = w.shape[0]
-        h = torch.empty((x2.shape[0], ops.round_up(N, 8)), dtype=BF16, device=x.device) if gelu else None
+        h = None
+        if gelu:
+            # the launch writes the N logical columns of its side output only.  At a width that is no multiple of 8 the backward multiplies
+            # the zero padding of dL/da by this padding, and 0 * (whatever the allocator left: a NaN, an inf) is a NaN that the input-gradient
+            # product spreads over every element of dx: the padding is zeroed here.  Whole chunks (every width of the models): as before
+            ld = ops.round_up(N, 8)
+            h = torch.empty((x2.shape[0], ld), dtype=BF16, device=x.device) if ld == N else torch.zeros((x2.shape[0], ld), dtype=BF16, device=x.device)
         y = ops.gemm_nt(x2, bank.get(w), n=N, k=K, bias=b, gelu=gelu, preact_out=h, preact_grad=bool(gelu and STORE_GELU_GRAD))     # (bf16 derivative: multiplied in torch below)
         ctx.save_for_backward(x2, w, b, h)
         ctx.lead = x.shape[:-1]
