@@ -217,6 +217,14 @@ _SIGNATURES["ap_label_map_crop"] = (_I, [POINTER(LabelMapCropArgs), _P])
 # grad_scale, unit_factor_or_null, counts_or_null, stream)
 _SIGNATURES["ap_agc_clip"] = (_I, [_P, _P, _L, _P, _P, _I, _F, _F, _F, _P, _P, _P])
 _SIGNATURES["ap_agc_short_max"] = (_I, [])
+# fused LAMB + EMA step with per-tensor trust ratios (csrc/lamb.hip): ap_lamb_ema_step(p, g, m, v, group_id, n, beta1, beta2, eps, step,
+# grad_scale, gnorm_sq, max_norm, clip_value, step_scalars_dev, ema[], ema_decay[], n_ema, p_bf16, ema_bf16[4] or null, guard_or_null,
+# group_tab_dev, n_groups, chunk_tab_dev, n_chunks, tensor_first_dev, n_tensors, always_adapt, trust_clip, trust_out, workspace, ws_bytes,
+# grid_cap, passes, stream)
+_SIGNATURES["ap_lamb_chunk"] = (_I, [])
+_SIGNATURES["ap_lamb_workspace"] = (ctypes.c_size_t, [_I])
+_SIGNATURES["ap_lamb_ema_step"] = (_I, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _I, _F, _P, _F, _F, _P, POINTER(c_void_p), POINTER(c_float), _I, _P,
+                                        POINTER(c_void_p), _P, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, ctypes.c_size_t, _I, _I, _P])
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 EXPECTED_ABI = 7                     # ap_abi_version() of the library these ctypes Structures mirror (include/autoprog_hip.h)

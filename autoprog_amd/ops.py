@@ -1418,3 +1418,82 @@ def agc_clip(g, p, unit_off, unit_skip, clip_factor, eps=1e-3, grad_scale=1.0, u
                           float(grad_scale), unit_factor.data_ptr() if unit_factor is not None else None,
                           counts.data_ptr() if counts is not None else None, _stream()), "ap_agc_clip")
     return g
+
+
+def lamb_chunk():
+    """the most elements one chunk of ap_lamb_ema_step's work table holds (a multiple of 4)"""
+    return int(lib.ap_lamb_chunk())
+
+
+def lamb_chunk_table(offsets, chunk=None):
+    """the work table of ap_lamb_ema_step for tensors that sit back to back at `offsets` (one entry more than there are tensors, ascending
+    from 0): every tensor cut into chunks of at most `chunk` (default lamb_chunk()) consecutive elements, none crossing a tensor, tensors
+    and chunks ascending.  -> {"start": int64 [n_chunks], "len": int32 [n_chunks], "tensor": int32 [n_chunks], "first": int32 [n_tensors
+    + 1] -- the first chunk of every tensor}, numpy arrays on the host.  An empty tensor has no chunk.  Needs no device."""
+    import numpy as np
+    ch = lamb_chunk() if chunk is None else int(chunk)
+    if ch < 4 or ch % 4:
+        raise ValueError("lamb_chunk_table: a chunk holds a positive multiple of 4 elements, not %d" % ch)
+    off = np.asarray(offsets, dtype=np.int64)
+    if off.ndim != 1 or off.size < 2 or off[0] != 0 or (np.diff(off) < 0).any():
+        raise ValueError("lamb_chunk_table: offsets ascend from 0 and hold one entry more than there are tensors")
+    per = (np.diff(off) + ch - 1) // ch
+    first = np.concatenate([[0], np.cumsum(per)])
+    tensor = np.repeat(np.arange(off.size - 1), per)
+    within = np.arange(int(first[-1])) - first[tensor]
+    start = off[tensor] + within * ch
+    length = np.minimum(ch, off[tensor + 1] - start)
+    return {"start": start.astype(np.int64), "len": length.astype(np.int32), "tensor": tensor.astype(np.int32), "first": first.astype(np.int32)}
+
+
+def lamb_pack_chunks(table):
+    """a lamb_chunk_table as the two HOST tensors the kernel's tables are copied from: the 16-byte {int64 start, int32 length, int32 tensor}
+    records as uint8 [n_chunks * 16], and `first` as int32"""
+    import numpy as np
+    rec = np.zeros(table["start"].size, dtype=np.dtype([("start", "<i8"), ("len", "<i4"), ("tensor", "<i4")]))
+    rec["start"], rec["len"], rec["tensor"] = table["start"], table["len"], table["tensor"]
+    return torch.from_numpy(rec.view(np.uint8).copy()), torch.from_numpy(np.ascontiguousarray(table["first"], dtype=np.int32))
+
+
+def lamb_ema_step(p, g, m, v, group_id, group_tab, chunks, first, trust, workspace, step, beta1=0.9, beta2=0.999, eps=1e-6, grad_scale=1.0,
+                  gnorm_sq=None, max_norm=0.0, clip_value=0.0, scalars_ptr=None, ema=(), ema_decay=(), p16=None, ema16=None, guard=None,
+                  always_adapt=False, trust_clip=False, grid_cap=0, passes=0):
+    """ap_lamb_ema_step: one LAMB + EMA update of the fp32 slabs p, m, v from the gradient slab g (only read), one trust ratio per tensor
+    (the rule in full: include/autoprog_hip.h).  group_id: uint8 per element; group_tab: fp32 [G, 2] of {lr * lr_scale, weight_decay};
+    chunks / first: the device copies of lamb_pack_chunks(lamb_chunk_table(offsets)); trust: fp32 [3, n_tensors], receives wn, un, phi of
+    an applied step; workspace: fp64 [2 * n_chunks], its contents do not matter.  ema / ema_decay: up to four fp32 slabs and their decays;
+    p16: the bf16 weight slab or None; ema16: None or a list as long as `ema` of bf16 slabs / None; guard: the int32 [8] ap_guard_state
+    record of ops.grad_health, or None.  scalars_ptr: the device address of {lr, 1 - beta1^t, sqrt(1 - beta2^t)} (graph.StepScalars.adam_ptr)
+    in the place of `step`.  grid_cap: workgroups of the two sweeping launches (0: the default); passes: bit 0 the norms, bit 1 the trust
+    ratios, bit 2 the update (0: all).  Every buffer is the caller's: nothing is allocated."""
+    for t, name in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (group_tab, "group_tab"), (trust, "trust")):
+        _req(t, torch.float32, name)
+    _req(group_id, torch.uint8, "group_id"); _req(chunks, torch.uint8, "chunks"); _req(first, torch.int32, "first"); _req(workspace, torch.float64, "workspace")
+    n, n_chunks, n_tensors = p.numel(), chunks.numel() // 16, first.numel() - 1
+    if not (g.numel() >= n and m.numel() == n and v.numel() == n and group_id.numel() >= n):
+        raise AutoProgHipError("lamb_ema_step: g, m, v and group_id as long as p")
+    if n_chunks < 1 or chunks.numel() != 16 * n_chunks or n_tensors < 1 or trust.numel() != 3 * n_tensors or workspace.numel() < 2 * n_chunks:
+        raise AutoProgHipError("lamb_ema_step: 16 bytes per chunk, n_tensors + 1 first chunks, trust [3, n_tensors], two fp64 of workspace per chunk")
+    if group_tab.dim() != 2 or group_tab.shape[1] != 2:
+        raise AutoProgHipError("lamb_ema_step: group_tab is [G, 2]")
+    ema, ema_decay = list(ema), list(ema_decay)
+    if len(ema) > 4 or len(ema) != len(ema_decay) or any(_req(e, torch.float32, "ema").numel() != n for e in ema):
+        raise AutoProgHipError("lamb_ema_step: up to four EMA slabs as long as p, one decay each")
+    ema_ptrs = (ctypes.c_void_p * 4)(*[e.data_ptr() for e in ema])
+    decays = (ctypes.c_float * 4)(*ema_decay)
+    e16 = None
+    if ema16 is not None:
+        if len(ema16) != len(ema) or any(e is not None and _req(e, BF16, "ema16").numel() != n for e in ema16):
+            raise AutoProgHipError("lamb_ema_step: ema16 holds one bf16 slab as long as p, or None, per EMA copy")
+        e16 = (ctypes.c_void_p * 4)(*[e.data_ptr() if e is not None else None for e in ema16])
+    if p16 is not None and _req(p16, BF16, "p16").numel() != n:
+        raise AutoProgHipError("lamb_ema_step: p16 as long as p")
+    if guard is not None and _req(guard, torch.int32, "guard").numel() != 8:
+        raise AutoProgHipError("lamb_ema_step: the guard record holds 8 words")
+    check(lib.ap_lamb_ema_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), group_id.data_ptr(), n, float(beta1), float(beta2), float(eps),
+                               int(step), float(grad_scale), gnorm_sq.data_ptr() if gnorm_sq is not None else None, float(max_norm), float(clip_value),
+                               scalars_ptr, ema_ptrs, decays, len(ema), p16.data_ptr() if p16 is not None else None, e16,
+                               guard.data_ptr() if guard is not None else None, group_tab.data_ptr(), group_tab.shape[0], chunks.data_ptr(), n_chunks,
+                               first.data_ptr(), n_tensors, int(bool(always_adapt)), int(bool(trust_clip)), trust.data_ptr(), workspace.data_ptr(),
+                               workspace.numel() * 8, int(grid_cap), int(passes), _stream()), "ap_lamb_ema_step")
+    return trust

@@ -9,7 +9,10 @@ EMA-averaged with torch foreach ops, as ModelEmaV2 averages the whole state dict
 
 Parameter groups: `FlatAdamWEma(param_groups=[...])` takes torch.optim-style groups with their own "lr", "lr_scale" and "weight_decay"
 (`ap_adamw_ema_step_groups`: the group of every element in the byte the decay mask was, the groups' values in a small device table);
-`layer_decay_param_groups` builds the groups of layer-wise learning-rate decay for the DeiT and VOLO models."""
+`layer_decay_param_groups` builds the groups of layer-wise learning-rate decay for the DeiT and VOLO models.
+
+`FlatLambEma` is the same optimizer under LAMB's rule, one trust ratio per parameter tensor (`ap_lamb_ema_step`); `make_flat_optimizer`
+maps the reference's `--opt` names onto the two."""
 import ctypes
 
 import torch
@@ -88,7 +91,17 @@ def agc_units(reducer, model=None, exclude=None):
     return offsets, skip, out_names
 
 
-MAX_PARAM_GROUPS = 256                  # the update kernel reads a parameter's group from one byte per element
+def lamb_chunks(reducer, model=None):
+    """the work table of the fused LAMB step (ap_lamb_ema_step; the rule: include/autoprog_hip.h) for the reducer's slab: every parameter
+    tensor -- LAMB's trust unit is the whole tensor, the segments of grad_segments -- cut into chunks of at most ops.lamb_chunk()
+    consecutive elements, read from where each gradient view sits.  -> (table, names): table is ops.lamb_chunk_table's dict of host
+    arrays ("start", "len", "tensor" per chunk, "first" per tensor), names[t] the name of tensor t.  The chunks cover the slab exactly
+    once, none crosses a tensor, tensor numbers ascend.  Needs no device."""
+    offsets, names = grad_segments(reducer, model)
+    return ops.lamb_chunk_table(offsets), names
+
+
+MAX_PARAM_GROUPS = 256             # the update kernel reads a parameter's group from one byte per element
 
 
 def resolve_param_groups(params, groups, lr, weight_decay, betas, eps, names=None):
@@ -642,6 +655,31 @@ class FlatAdamWEma:
         Parameter groups: every group's "lr" * "lr_scale" (default 1) and "weight_decay" are read at every call.  While the two default
         groups share one rate and group 1 has no decay the launch is the one it always was; any other setting, and every optimizer built
         with param_groups=, takes ap_adamw_ema_step_groups (`grouped`).  Clipping and the guard are global, not per group."""
+        g, gd, gscale, gnorm_ptr, max_norm, clip_value = self._step_front(clip_grad, clip_mode, skip_nonfinite)
+        lr, wd = self._lr_eff(self.param_groups[0]), float(self.param_groups[0]["weight_decay"])
+        grouped = self.grouped
+        if grouped:
+            gw = self._pushed_groups(g.device, scalars)
+        args = (self.p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), (gw["group_id"] if grouped else self.wd_mask).data_ptr(),
+                self.n_pad, lr, self.betas[0], self.betas[1], self.eps, wd, self.step_count, gscale,
+                gnorm_ptr, max_norm, clip_value, scalars.adam_ptr if scalars is not None else None, self._ema_ptrs, self._ema_decay, len(self.ema), self.p16.data_ptr())
+        if grouped:                                          # (the four argument sets of the launches below behind one symbol)
+            check(lib.ap_adamw_ema_step_groups(*args, self._ema16_ptrs if self._shadows else None, gd["state"].data_ptr() if skip_nonfinite else None,
+                                               gw["table"].data_ptr(), len(self.param_groups), ops._stream()), "ap_adamw_ema_step_groups")
+        elif self._shadows:                                  # some EMA copy is a network: the same update, and its bf16 copy in the same pass
+            check(lib.ap_adamw_ema_step_ema16(*args, self._ema16_ptrs, gd["state"].data_ptr() if skip_nonfinite else None, ops._stream()),
+                  "ap_adamw_ema_step_ema16")
+        elif skip_nonfinite:
+            check(lib.ap_adamw_ema_step_guarded(*args, gd["state"].data_ptr(), ops._stream()), "ap_adamw_ema_step_guarded")
+        else:
+            check(lib.ap_adamw_ema_step(*args, ops._stream()), "ap_adamw_ema_step")
+        self._step_back()
+
+    def _step_front(self, clip_grad, clip_mode, skip_nonfinite, pad=True):
+        """what every update rule does in front of its launch (step() states the contracts): the call is counted, the guard's health pass
+        runs, the pending 1/world is taken, and 'norm' mode measures the slab.  pad: a slab whose length is no multiple of 4 goes into
+        a padded copy (the AdamW kernel sweeps whole float4).  -> (the gradient slab to read, the guard's buffers or None, the gradient
+        scale, the device address of the slab's sum of squares or None, the norm bound, the value bound)"""
         g = self.reducer.flat
         gd = self._guard_workspace(g.device) if skip_nonfinite else None     # (before the count moves: the record starts at the steps made so far)
         self.step_count += 1
@@ -650,7 +688,7 @@ class FlatAdamWEma:
                                      gd["state"].data_ptr(), self.betas[0], self.betas[1], gd["ws"].data_ptr(), gd["ws_bytes"], ops._stream()),
                   "ap_grad_health")
             gd["used"] = True
-        if self.g is None:                                   # slab length not a multiple of 4: padded copy
+        if pad and self.g is None:                           # slab length not a multiple of 4: padded copy
             gp = torch.zeros(self.n_pad, dtype=torch.float32, device=g.device)
             gp[:g.numel()] = g
             g = gp
@@ -670,29 +708,21 @@ class FlatAdamWEma:
             else:
                 raise NotImplementedError("FlatAdamWEma.step: clip_mode %r is not a mode of the update kernel ('norm' and 'value' are; 'agc' rewrites the "
                                           "gradient in front of the update: call adaptive_clip_grad(clip_grad), then step() without clip arguments)" % (clip_mode,))
-        lr, wd = self._lr_eff(self.param_groups[0]), float(self.param_groups[0]["weight_decay"])
-        grouped = self.grouped
-        if grouped:
-            # one rate and one decay per group, from the device table: an eager step sends the table first; a step under `scalars` (a
-            # captured one) does not -- the copy belongs in front of the replay (push_groups; graph.GraphedStep._prepare)
-            if scalars is None:
-                self.push_groups()
-            gw = self._group_workspace(g.device)
-            if not gw["pushed"]:
-                raise RuntimeError("FlatAdamWEma.step(scalars=...): the parameter-group table was never sent (call push_groups() first)")
-        args = (self.p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), (gw["group_id"] if grouped else self.wd_mask).data_ptr(),
-                self.n_pad, lr, self.betas[0], self.betas[1], self.eps, wd, self.step_count, gscale,
-                gnorm_ptr, max_norm, clip_value, scalars.adam_ptr if scalars is not None else None, self._ema_ptrs, self._ema_decay, len(self.ema), self.p16.data_ptr())
-        if grouped:                                          # (the four argument sets of the launches below behind one symbol)
-            check(lib.ap_adamw_ema_step_groups(*args, self._ema16_ptrs if self._shadows else None, gd["state"].data_ptr() if skip_nonfinite else None,
-                                               gw["table"].data_ptr(), len(self.param_groups), ops._stream()), "ap_adamw_ema_step_groups")
-        elif self._shadows:                                  # some EMA copy is a network: the same update, and its bf16 copy in the same pass
-            check(lib.ap_adamw_ema_step_ema16(*args, self._ema16_ptrs, gd["state"].data_ptr() if skip_nonfinite else None, ops._stream()),
-                  "ap_adamw_ema_step_ema16")
-        elif skip_nonfinite:
-            check(lib.ap_adamw_ema_step_guarded(*args, gd["state"].data_ptr(), ops._stream()), "ap_adamw_ema_step_guarded")
-        else:
-            check(lib.ap_adamw_ema_step(*args, ops._stream()), "ap_adamw_ema_step")
+        return g, gd, gscale, gnorm_ptr, max_norm, clip_value
+
+    def _pushed_groups(self, device, scalars):
+        """the grouped launch's buffers with the table sent: one rate and one decay per group, from the device table.  An eager step
+        sends the table first; a step under `scalars` (a captured one) does not -- the copy belongs in front of the replay (push_groups;
+        graph.GraphedStep._prepare)"""
+        if scalars is None:
+            self.push_groups()
+        gw = self._group_workspace(device)
+        if not gw["pushed"]:
+            raise RuntimeError("FlatAdamWEma.step(scalars=...): the parameter-group table was never sent (call push_groups() first)")
+        return gw
+
+    def _step_back(self):
+        """what every update rule does behind its launch: the transposed bf16 copies and the BatchNorm buffer averages"""
         self._refresh_transposes()
         from . import functional
         functional._WeightBank.generation += 1             # the kernel wrote the parameters behind autograd's back
@@ -836,3 +866,104 @@ class FlatAdamWEma:
             self._refresh_ema16()
             from . import functional
             functional._WeightBank.generation += 1
+
+
+class FlatLambEma(FlatAdamWEma):
+    """LAMB on the slabs of FlatAdamWEma: the moments of Adam, and per parameter TENSOR a trust ratio phi = ||p|| / ||update|| that scales
+    the tensor's step (ap_lamb_ema_step, csrc/lamb.hip; the rule and its deviations from apex's FusedLAMB and timm's Lamb:
+    include/autoprog_hip.h) -- the update rule of large-batch recipes (`--opt lamb` / `fusedlamb`).  Everything around the rule is the
+    parent's: the EMA copies in the same pass, the bf16 weight slab and the bf16 EMA shadows (ema_model), parameter groups
+    (param_groups=, layer_decay_param_groups), the pending 1/world, clip_grad in 'norm' and 'value' mode, adaptive_clip_grad() in front,
+    skip_nonfinite, graph replay (graph.GraphedStep), grow / resync, state_dict / load_state_dict.
+    Weight decay is LAMB's: wd * p is part of the update that the trust ratio scales, not AdamW's decoupled factor.
+    always_adapt: False -- a tensor of a group without weight decay takes phi = 1 (apex without use_nvlamb); True: every tensor adapts.
+    trust_clip: phi is capped at 1 (timm's flag).  apex's max_grad_norm = 1.0 pre-normalisation is step(clip_grad=1.0, clip_mode="norm")."""
+
+    def __init__(self, model, reducer, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.05, ema_decays=(), param_groups=None,
+                 always_adapt=False, trust_clip=False):
+        super().__init__(model, reducer, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, ema_decays=ema_decays, param_groups=param_groups)
+        self.always_adapt, self.trust_clip = bool(always_adapt), bool(trust_clip)
+        self._lamb = None                                        # the chunk table, the trust outputs and the partials (_lamb_workspace)
+
+    @property
+    def grouped(self):
+        """always True: the LAMB launch reads every element's rate and decay from the group table, so graph.GraphedStep sends the table in
+        front of every replay"""
+        return True
+
+    def _lamb_workspace(self, device):
+        """ALL device buffers the LAMB launch adds, allocated once and OUTSIDE any stream capture (see _clip_workspace): the chunk table
+        of lamb_chunks and every tensor's first chunk, ONE buffer [3, n_tensors] of wn, un, phi -- one read-back for trust_report() --
+        and two fp64 partials per chunk."""
+        if self._lamb is None:
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FlatLambEma: the chunk table and the trust outputs must exist before a step is captured (call _lamb_workspace first)")
+            table, names = lamb_chunks(self.reducer, self.model)
+            chunks, first = ops.lamb_pack_chunks(table)
+            n_chunks, n_tensors = int(table["start"].size), len(names)
+            self._lamb = {"names": names, "n_chunks": n_chunks, "n_tensors": n_tensors, "used": False, "chunks": chunks.to(device), "first": first.to(device),
+                          "trust": torch.zeros(3, n_tensors, dtype=torch.float32, device=device),
+                          "ws": torch.zeros(int(lib.ap_lamb_workspace(n_chunks)) // 8, dtype=torch.float64, device=device)}
+        return self._lamb
+
+    def _group_workspace(self, device):
+        """the parent's buffers, and the LAMB launch's own with them: graph.GraphedStep.capture() asks for these in front of a capture"""
+        gw = super()._group_workspace(device)
+        self._lamb_workspace(device)
+        return gw
+
+    def trust_report(self):
+        """[(parameter name, wn = ||p||, un = ||update||, phi)] per parameter tensor in slab order, as the last APPLIED step measured them
+        (fp32; phi is 1 for a tensor that does not adapt, and what trust_clip left of it).  A step that skip_nonfinite skipped measures
+        nothing and writes nothing here: the report then still holds the last applied step's values -- all zeros when no step has been
+        applied yet.  ONE read-back."""
+        lw = self._lamb
+        if lw is None or not lw["used"]:
+            raise RuntimeError("FlatLambEma.trust_report: no step() has run yet")
+        host = lw["trust"].cpu()
+        return list(zip(lw["names"], host[0].tolist(), host[1].tolist(), host[2].tolist()))
+
+    def state_dict(self):
+        """the parent's layout plus "lamb": {"always_adapt", "trust_clip"} -- the two flags are part of the rule a run continues under"""
+        sd = super().state_dict()
+        sd["lamb"] = {"always_adapt": self.always_adapt, "trust_clip": self.trust_clip}
+        return sd
+
+    def load_state_dict(self, sd):
+        """the parent's, and the two flags of the saved rule (a state without them -- a FlatAdamWEma's -- leaves the constructor's)"""
+        super().load_state_dict(sd)
+        flags = sd.get("lamb", {})
+        self.always_adapt = bool(flags.get("always_adapt", self.always_adapt))
+        self.trust_clip = bool(flags.get("trust_clip", self.trust_clip))
+
+    def step(self, clip_grad=None, clip_mode="norm", scalars=None, skip_nonfinite=False):
+        """one LAMB + EMA update from the gradient slab: FlatAdamWEma.step's arguments and contracts (clip_grad / clip_mode act on the MEAN
+        gradient in front of the moments, 'agc' raises, `last_grad_norm`, `scalars` for a replayed step, skip_nonfinite: a skipped step
+        writes neither the parameters, the moments nor the bf16 weights, still moves the EMA copies and does not advance t).  Three
+        launches: the two norms of every tensor (read-only), the trust ratios, the update.  The launch is given the gradient slab's own
+        length, the one the chunks cover: the pad of the other slabs lies behind it and is never touched, so g needs no padded copy.
+        (A graph captured with one pair of flags keeps them: always_adapt / trust_clip are arguments of the captured launch.)"""
+        g, gd, gscale, gnorm_ptr, max_norm, clip_value = self._step_front(clip_grad, clip_mode, skip_nonfinite, pad=False)
+        gw = self._pushed_groups(g.device, scalars)
+        lw = self._lamb_workspace(g.device)
+        check(lib.ap_lamb_ema_step(self.p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), gw["group_id"].data_ptr(), g.numel(),
+                                   self.betas[0], self.betas[1], self.eps, self.step_count, gscale, gnorm_ptr, max_norm, clip_value,
+                                   scalars.adam_ptr if scalars is not None else None, self._ema_ptrs, self._ema_decay, len(self.ema), self.p16.data_ptr(),
+                                   self._ema16_ptrs if self._shadows else None, gd["state"].data_ptr() if skip_nonfinite else None,
+                                   gw["table"].data_ptr(), len(self.param_groups), lw["chunks"].data_ptr(), lw["n_chunks"], lw["first"].data_ptr(),
+                                   lw["n_tensors"], int(self.always_adapt), int(self.trust_clip), lw["trust"].data_ptr(), lw["ws"].data_ptr(),
+                                   lw["ws"].numel() * 8, 0, 0, ops._stream()), "ap_lamb_ema_step")
+        lw["used"] = True
+        self._step_back()
+
+
+FLAT_OPTIMIZERS = {"adamw": FlatAdamWEma, "fusedadamw": FlatAdamWEma, "lamb": FlatLambEma, "fusedlamb": FlatLambEma}
+
+
+def make_flat_optimizer(name, model, reducer, **kw):
+    """the flat-slab optimizer for the reference's `--opt` (main_prog.py:119, timm's create_optimizer): 'adamw' / 'fusedadamw' ->
+    FlatAdamWEma, 'lamb' / 'fusedlamb' -> FlatLambEma (case-insensitive); `kw` goes to the constructor.  Any other name: ValueError."""
+    cls = FLAT_OPTIMIZERS.get(str(name).lower())
+    if cls is None:
+        raise ValueError("make_flat_optimizer: no flat-slab optimizer %r (there are: %s)" % (name, ", ".join(sorted(FLAT_OPTIMIZERS))))
+    return cls(model, reducer, **kw)

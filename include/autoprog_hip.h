@@ -668,6 +668,55 @@ int ap_agc_clip(float* g, const float* p, int64_t n, const int64_t* unit_off, co
                 float clip_factor, float eps, float grad_scale, float* unit_factor_or_null, int32_t* counts_or_null,
                 ap_stream_t stream);
 int ap_agc_short_max(void);
+/* ---- fused LAMB + EMA step on the flat slabs, one trust ratio per parameter tensor (additive in ABI version 7; csrc/lamb.hip).  The
+ * reference takes its optimizer from `--opt` (main_prog.py:119, timm's create_optimizer); `fusedlamb` / `lamb` there are apex's FusedLAMB
+ * and timm's Lamb.  The rule below restates those two from knowledge of their code; it is NOT byte-checked against either (neither is a
+ * dependency of this project); tests/_lamb_ref.py pins it in fp64.
+ *   Per element, with t, bc1 = 1 - beta1^t and sqrt(bc2) = sqrt(1 - beta2^t) as ap_adamw_ema_step gets them (the host's `step`,
+ *   step_scalars_dev[1..2], or the guard record) and wd, lr_eff of the element's group (group_tab_dev, as ap_adamw_ema_step_groups):
+ *     gh = the AdamW kernel's gradient: grad_scale * g, times min(1, max_norm / (norm + 1e-6)) with gnorm_sq, or clamped to +-clip_value
+ *     m' = beta1 m + (1 - beta1) gh          v' = beta2 v + (1 - beta2) gh^2
+ *     r  = m' / (sqrt(v') / sqrt(bc2) + eps)
+ *     u  = r / bc1 + wd * p
+ *   Per parameter tensor T (the WHOLE tensor: LAMB's unit, not AGC's rows):
+ *     wn = sqrt(sum p^2), un = sqrt(sum u^2)     fp64 sums of the exact squares of the fp32 values, in a fixed order
+ *     phi_T = wn / un  if adapt and wn > 0 and un > 0, else 1       adapt = always_adapt or wd != 0 (wd: the group of the tensor's first element)
+ *     phi_T = min(phi_T, 1) if trust_clip         phi_T is formed in fp64 and rounded to fp32 once
+ *     p' = p - (lr_eff * phi_T) * u
+ *   then every EMA copy e' = d e + (1 - d) p', p_bf16 and the emitted ema_bf16 copies, the bf16 roundings of the stored fp32 values.
+ *   `adapt` is apex's rule without use_nvlamb; always_adapt is timm's name for switching it off; trust_clip is timm's flag.
+ *   Deviation 1 (pre-normalisation).  apex divides the gradient by max(global norm / max_grad_norm, 1) by default (max_grad_norm 1.0).
+ *            Here that is gnorm_sq / max_norm = 1 -- clip_grad_norm_'s coefficient min(1, c / (norm + 1e-6)); apex has no 1e-6 -- and
+ *            it is off unless asked for.
+ *   Deviation 2 (arithmetic).  Both libraries form the two norms in fp32 and the ratio in fp32; here the sums are exact squares in
+ *            fp64, the ratio is fp64 and rounded once.  m', v' and u take fused multiply-adds where csrc/lamb.hip spells them out.
+ *   Non-finite inputs follow the formula (comparisons with NaN are false: such a tensor takes phi = 1); the guard is the remedy.
+ * Work is cut into chunks the HOST describes once: chunk_tab_dev[n_chunks] of {int64 start, int32 length, int32 tensor} (16 bytes each,
+ * 16-byte aligned), every chunk at most ap_lamb_chunk() consecutive elements of ONE tensor, tensors ascending, the chunks of a tensor
+ * consecutive; tensor_first_dev[n_tensors + 1] (int32) holds every tensor's first chunk.  Entries are clamped into [0, n): a malformed
+ * table reads and writes nothing outside the slabs.  Elements no chunk covers (the slab's pad) are never written in any slab.
+ * Three launches: the norms (reads p, g, m, v, group_id; two fp64 partials per chunk into `workspace`, ap_lamb_workspace(n_chunks) bytes,
+ * 8-byte aligned, no initial contents assumed), the trust ratios (partials added in ascending chunk order; trust_out[3][n_tensors] =
+ * wn, un, phi as fp32), the update.  g is only read.  No floating-point atomics: two calls on the same inputs write the same bits.
+ * guard_or_null says non-finite: p, m, v, p_bf16 and trust_out are not written, the EMA copies take their lerp towards the unchanged p.
+ * n is the number of elements the chunks may cover (any n > 0): every slab holds at least n elements, and one padded to a multiple of 4
+ * may be longer than g; all fp32 slabs 16-byte, the bf16 slabs 8-byte, group_id 4-byte aligned at the same offsets.
+ * ema_bf16 is nullable (an array of 4, NULL entries: not emitted).  grid_cap > 0 caps the workgroups of the two sweeping launches (0: the
+ * default, 2048); `passes` selects launches for measurements (bit 0 norms, bit 1 trust ratios, bit 2 update; 0: all three).
+ * Nothing is allocated; runs under stream capture.  Refused before anything is launched: a NULL slab, table, output or workspace
+ * (AP_ERR_NULL); n, n_chunks or n_tensors < 1, n_ema outside 0..4, n_groups outside 1..256, step < 1, gnorm_sq without max_norm > 0, a
+ * workspace that is too small, a misaligned pointer, an ema_bf16 entry at an index >= n_ema, grid_cap < 0, passes outside 0..7
+ * (AP_ERR_SHAPE). */
+int ap_lamb_chunk(void);
+size_t ap_lamb_workspace(int n_chunks);
+int ap_lamb_ema_step(float* p, const float* g, float* m, float* v, const uint8_t* group_id, int64_t n,
+                     float beta1, float beta2, float eps, int step, float grad_scale,
+                     const float* gnorm_sq, float max_norm, float clip_value, const float* step_scalars_dev,
+                     float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, ap_bf16* const* ema_bf16_or_null,
+                     const ap_guard_state* guard_or_null, const float* group_tab_dev, int n_groups,
+                     const void* chunk_tab_dev, int n_chunks, const int32_t* tensor_first_dev, int n_tensors,
+                     int always_adapt, int trust_clip, float* trust_out, void* workspace, size_t ws_bytes,
+                     int grid_cap, int passes, ap_stream_t stream);
 /* transpose `count` bf16 matrices of one slab in one launch: desc_dev = device array of
  * {int64 src_off, int64 dst_off, int rows, int cols, int ld_dst, int first_tile} (32x32 tiles, first_tile
  * = running tile prefix); dst[dst_off + c*ld_dst + r] = src[src_off + r*cols + c], pad columns zeroed */
