@@ -11,9 +11,9 @@
 //                                           a second one over g when it clips.  A unit is never split across workgroups.
 // A unit may start at any offset mod 4 (tensors of odd length sit back to back): up to 3 head elements and up to 3 tail elements go as
 // scalars, everything between as 16-byte accesses (both slabs are 16-byte aligned at the same offsets).
-// Sums are of exact squares in fp64 (x * x of an fp32 is exact in fp64; gh_add of optim.hip), added in a fixed order: per lane in sweep
-// order, a butterfly over the wave, the four waves in order.  No floating-point atomics: two launches write the same bits.  The two
-// tallies are integers.
+// Sums are of exact squares in fp64 (sq_add, sq_add_finite, wave_sum and the split: slab_math.h), added in a fixed order: per lane in
+// sweep order, a butterfly over the wave, the four waves in order.  No floating-point atomics: two launches write the same bits.  The
+// two tallies are integers.
 //
 // Loads in flight.  The pass is bound by memory latency, not by arithmetic, so every load of a unit is issued before the first one is
 // used.  Two forms that read naturally defeat that with hipcc; together they ran at 82 us where this file runs at 59 us (VOLO-D1's
@@ -25,24 +25,13 @@
 //   five scalar loads of table entries, each clamped before the next address is formed, cost five round trips in a row.  The table
 //                           goes through one vector load per wave and readlane (agc_ask_group / agc_take_group).
 #include "common.h"
+#include "slab_math.h"
 
 constexpr int AGC_K = 8;                            // float4 per lane a short unit keeps in registers
 constexpr int AGC_SHORT_MAX = 64 * 4 * AGC_K;       // 2048: at most 512 aligned float4 (64 lanes x AGC_K) whatever the head and tail
 constexpr int AGC_MAX_GRID = 4096;                  // workgroups; each sweep of the grid covers 4 x this many units
 constexpr int AGC_P_CHUNK = 4;                      // float4 of p per lane a short unit has in flight at a time
 constexpr int AGC_LONG_UNROLL = 4;                  // float4 of g and of p a thread of the long walk has in flight
-
-__device__ __forceinline__ void agc_add_g(float x, double& s, int& bad) {
-    const bool nf = (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u;            // exponent all ones: +-inf, NaN
-    const double d = nf ? 0.0 : (double)x;
-    s = fma(d, d, s);
-    bad += nf ? 1 : 0;
-}
-__device__ __forceinline__ void agc_add_p(float x, double& s) { const double d = (double)x; s = fma(d, d, s); }
-
-__device__ __forceinline__ void agc_wave_reduce(double& sg, double& sp, int& bad) {
-    for (int o = 32; o > 0; o >>= 1) { sg += __shfl_xor(sg, o, 64); sp += __shfl_xor(sp, o, 64); bad += __shfl_xor(bad, o, 64); }
-}
 
 // the rule, from the two sums of squares: -> the factor to multiply the unit by, `clipped` set when it is to be applied.  A unit with a
 // non-finite gradient element is left alone (factor 1).
@@ -69,15 +58,6 @@ __device__ __forceinline__ float agc_ld1(const float* __restrict__ v, int64_t i,
     return mine ? r : 0.f;
 }
 
-// how a unit [b, e) splits: `head` scalars up to the first 16-byte boundary, nv float4, `tail` scalars
-__device__ __forceinline__ void agc_split(int64_t b, int64_t e, int& head, int64_t& nv, int& tail) {
-    const int64_t len = e - b;
-    head = (int)((4 - (b & 3)) & 3);
-    if (head > len) head = (int)len;
-    nv = (len - head) >> 2;
-    tail = (int)(len - head - (nv << 2));
-}
-
 // Short units are read through buffer descriptors (hardware bounds check: a lane past the end gets zeros, without a branch and without
 // an address of its own): one over the unit for its head and tail scalars, one over its aligned body for the float4.  Descriptors are
 // built from wave-uniform values only.
@@ -97,7 +77,7 @@ __device__ __forceinline__ float agc_short_unit(float* __restrict__ g, const flo
                                                 float clip_factor, float eps, float grad_scale, int& n_clip, int& n_bad) {
     int head, tail;
     int64_t nv64;
-    agc_split(b, e, head, nv64, tail);
+    slab_split(b, e - b, head, nv64, tail);
     const int nv = (int)nv64, len = (int)(e - b);
     float* g_body = g + b + head;                                                  // (b + head is a multiple of 4, or the body is empty)
     const auto g_unit = __builtin_amdgcn_make_buffer_rsrc(g + b, 0, len * 4, AGC_RSRC_FLAGS);
@@ -122,14 +102,14 @@ __device__ __forceinline__ float agc_short_unit(float* __restrict__ g, const flo
 #pragma unroll
         for (int k = 0; k < YS; ++k) y[k] = agc_buf4(p_vec, (unsigned)lane * 16u + 1024u * (h + k));
 #pragma unroll
-        for (int k = 0; k < YS; ++k) { agc_add_p(y[k].x, p0); agc_add_p(y[k].y, p1); agc_add_p(y[k].z, p0); agc_add_p(y[k].w, p1); }
+        for (int k = 0; k < YS; ++k) { sq_add(y[k].x, p0); sq_add(y[k].y, p1); sq_add(y[k].z, p0); sq_add(y[k].w, p1); }
     }
 #pragma unroll
-    for (int k = 0; k < KS; ++k) { agc_add_g(x[k].x, g0, bad); agc_add_g(x[k].y, g1, bad); agc_add_g(x[k].z, g0, bad); agc_add_g(x[k].w, g1, bad); }
+    for (int k = 0; k < KS; ++k) { sq_add_finite(x[k].x, g0, bad); sq_add_finite(x[k].y, g1, bad); sq_add_finite(x[k].z, g0, bad); sq_add_finite(x[k].w, g1, bad); }
     double sg = g0 + g1, sp = p0 + p1;
-    agc_add_g(xh, sg, bad); agc_add_g(xt, sg, bad);
-    agc_add_p(yh, sp); agc_add_p(yt, sp);
-    agc_wave_reduce(sg, sp, bad);
+    sq_add_finite(xh, sg, bad); sq_add_finite(xt, sg, bad);
+    sq_add(yh, sp); sq_add(yt, sp);
+    wave_sum(sg, sp, bad);
     bool clipped;
     const float f = agc_factor(sg, sp, bad, clip_factor, eps, grad_scale, clipped);
     if (clipped) {                                                                 // (wave-uniform: every lane holds the same sums)
@@ -202,7 +182,7 @@ k_agc_clip(float* __restrict__ g, const float* __restrict__ p, int64_t n, const 
                 if (!skip && e > b) {
                     int head, tail;
                     int64_t nv;
-                    agc_split(b, e, head, nv, tail);                               // (wave-uniform: the body's length picks the code)
+                    slab_split(b, e - b, head, nv, tail);                          // (wave-uniform: the body's length picks the code)
                     if (nv <= 128) f = agc_short_unit<2>(g, p, b, e, lane, clip_factor, eps, grad_scale, n_clip, n_bad);
                     else f = agc_short_unit<AGC_K>(g, p, b, e, lane, clip_factor, eps, grad_scale, n_clip, n_bad);
                 }
@@ -219,7 +199,7 @@ k_agc_clip(float* __restrict__ g, const float* __restrict__ p, int64_t n, const 
             if (e - b <= AGC_SHORT_MAX || (j == 0 ? cur.skip[0] : j == 1 ? cur.skip[1] : j == 2 ? cur.skip[2] : cur.skip[3]) != 0) continue;
             int head, tail;
             int64_t nv;
-            agc_split(b, e, head, nv, tail);                                       // (nv > 0)
+            slab_split(b, e - b, head, nv, tail);                                  // (nv > 0)
             float* g_body = g + b + head;
             const float* p_body = p + b + head;
             const float4* gv = reinterpret_cast<const float4*>(g_body);
@@ -237,14 +217,14 @@ k_agc_clip(float* __restrict__ g, const float* __restrict__ p, int64_t n, const 
                 for (int k = 0; k < AGC_LONG_UNROLL; ++k) y[k] = agc_ld4(pv, i0 + 256 * k, nv);
 #pragma unroll
                 for (int k = 0; k < AGC_LONG_UNROLL; ++k) {
-                    agc_add_g(x[k].x, g0, bad); agc_add_g(x[k].y, g1, bad); agc_add_g(x[k].z, g2, bad); agc_add_g(x[k].w, g3, bad);
-                    agc_add_p(y[k].x, p0); agc_add_p(y[k].y, p1); agc_add_p(y[k].z, p2); agc_add_p(y[k].w, p3);
+                    sq_add_finite(x[k].x, g0, bad); sq_add_finite(x[k].y, g1, bad); sq_add_finite(x[k].z, g2, bad); sq_add_finite(x[k].w, g3, bad);
+                    sq_add(y[k].x, p0); sq_add(y[k].y, p1); sq_add(y[k].z, p2); sq_add(y[k].w, p3);
                 }
             }
             double sg = (g0 + g1) + (g2 + g3), sp = (p0 + p1) + (p2 + p3);
-            agc_add_g(xh, sg, bad); agc_add_g(xt, sg, bad);
-            agc_add_p(yh, sp); agc_add_p(yt, sp);
-            agc_wave_reduce(sg, sp, bad);
+            sq_add_finite(xh, sg, bad); sq_add_finite(xt, sg, bad);
+            sq_add(yh, sp); sq_add(yt, sp);
+            wave_sum(sg, sp, bad);
             if (lane == 0) { red_g[wave] = sg; red_p[wave] = sp; red_c[wave] = bad; }
             __syncthreads();
             sg = ((red_g[0] + red_g[1]) + red_g[2]) + red_g[3];

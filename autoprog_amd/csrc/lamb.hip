@@ -28,7 +28,7 @@
 //
 // Table entries are clamped into the slab: a malformed table reads and writes nothing outside [0, n) of any slab.
 #include "common.h"
-#include <math.h>
+#include "slab_math.h"
 
 constexpr int LAMB_CH = 4096;               // 256 lanes x 4 float4
 constexpr int LAMB_MAX_GRID = 2048;         // 8 workgroups on each of 256 CUs
@@ -68,11 +68,7 @@ __device__ __forceinline__ LambK lamb_consts(const LambArgs& a) {
     if (a.step_dev) { const volatile float* s = a.step_dev; k.bc1 = s[1]; k.bc2_sqrt = s[2]; }
     if (a.guard) { const volatile float* s = &a.guard->bc1; k.bc1 = s[0]; k.bc2_sqrt = s[1]; }
     // the AdamW kernel's gradient: the pending mean, times clip_grad_norm_'s coefficient on the MEAN gradient; then clip_grad_value_
-    k.gs = a.gscale;
-    if (a.gnorm_sq) {
-        const float total = sqrtf(a.gnorm_sq[0]) * a.gscale;
-        k.gs *= fminf(1.0f, a.max_norm / (total + 1e-6f));
-    }
+    k.gs = clip_gscale(a.gscale, a.gnorm_sq, a.max_norm);
     k.cv = a.clip_value;
     return k;
 }
@@ -99,6 +95,8 @@ __device__ __forceinline__ LambGeo lamb_geo(const LambArgs& a, int c) {
     q.start = ch.start < 0 ? 0 : (ch.start > a.n ? a.n : ch.start);
     int64_t len = ch.len < 0 ? 0 : (ch.len > LAMB_CH ? LAMB_CH : ch.len);
     if (len > a.n - q.start) len = a.n - q.start;
+    // (slab_split's arithmetic, restated: called through the function, hipcc gives k_lamb_norms two more SGPRs and k_lamb_apply another
+    // schedule -- profiles/optim_core_refactor.txt)
     q.head = (int)((4 - (q.start & 3)) & 3);
     if (q.head > len) q.head = (int)len;
     q.nv = (int)((len - q.head) >> 2);
@@ -119,8 +117,6 @@ __device__ __forceinline__ void lamb_load_groups(const LambArgs& a, float2* s_ta
         s_tab[gi] = gi < a.n_groups ? make_float2(a.group_tab[2 * gi], a.group_tab[2 * gi + 1]) : make_float2(0.f, 0.f);
     __syncthreads();
 }
-
-__device__ __forceinline__ void lamb_sq(float x, double& s) { const double d = (double)x; s = fma(d, d, s); }
 
 // ---- pass 1: two fp64 partials per chunk.  Reads only.
 __global__ void __launch_bounds__(256)
@@ -148,18 +144,18 @@ k_lamb_norms(const float* __restrict__ p, const float* __restrict__ g, const flo
             for (int e = 0; e < 4; ++e) {
                 float mn, vn;                                                      // (pass 1 stores no moments)
                 const float u = lamb_u(P[e], G[e], M[e], V[e], s_tab[W[e]].y, k, mn, vn);
-                lamb_sq(P[e], sp);
-                lamb_sq(u, su);
+                sq_add(P[e], sp);
+                sq_add(u, su);
             }
         }
         const int64_t j = lamb_scalar_index(q, tid);
         if (j >= 0) {
             float mn, vn;
             const float u = lamb_u(p[j], g[j], m[j], v[j], s_tab[group_id[j]].y, k, mn, vn);
-            lamb_sq(p[j], sp);
-            lamb_sq(u, su);
+            sq_add(p[j], sp);
+            sq_add(u, su);
         }
-        for (int o = 32; o > 0; o >>= 1) { sp += __shfl_xor(sp, o, 64); su += __shfl_xor(su, o, 64); }
+        wave_sum(sp, su);
         if (lane == 0) { red_p[wave] = sp; red_u[wave] = su; }
         __syncthreads();
         if (tid == 0) {
@@ -308,9 +304,7 @@ extern "C" int ap_lamb_ema_step(float* p, const float* g, float* m, float* v, co
         return AP_ERR_SHAPE;
     LambArgs a;
     a.beta1 = beta1; a.omb1 = 1.0f - beta1; a.beta2 = beta2; a.omb2 = 1.0f - beta2; a.eps = eps;
-    // (as ap_adamw_ema_step forms them: in double from the float arguments, rounded once -- graph.StepScalars.set_adam's numbers)
-    a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-    a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+    adam_bias_corrections(beta1, beta2, step, a.bc1, a.bc2_sqrt);                   // (ap_adamw_ema_step's)
     a.gscale = grad_scale; a.max_norm = max_norm; a.clip_value = clip_value > 0.f ? clip_value : 0.f;
     a.gnorm_sq = gnorm_sq; a.step_dev = step_scalars_dev; a.guard = guard_or_null;
     a.group_tab = group_tab_dev; a.n_groups = n_groups;
@@ -318,13 +312,7 @@ extern "C" int ap_lamb_ema_step(float* p, const float* g, float* m, float* v, co
     a.tensor_first = tensor_first_dev; a.n_tensors = n_tensors;
     a.always_adapt = always_adapt != 0; a.trust_clip = trust_clip != 0;
     a.n_ema = n_ema;
-    for (int e = 0; e < 4; ++e) {
-        a.ema[e] = (e < n_ema) ? ema[e] : nullptr;
-        a.decay[e] = (e < n_ema) ? ema_decay[e] : 0.f;
-        a.ema16[e] = ema_bf16 ? reinterpret_cast<bf16_t*>(ema_bf16[e]) : nullptr;
-        if (e < n_ema && (!ema[e] || ((uintptr_t)ema[e] & 15))) return ema[e] ? AP_ERR_SHAPE : AP_ERR_NULL;
-        if (a.ema16[e] && (e >= n_ema || ((uintptr_t)a.ema16[e] & 7))) return AP_ERR_SHAPE;
-    }
+    if (const int rc = slab_ema_args(ema, ema_decay, n_ema, ema_bf16, 15, a.ema, a.decay, a.ema16)) return rc;     // (an EMA slab off 16 bytes is refused here)
     a.trust = trust_out; a.partial = static_cast<double*>(workspace); a.n = n;
     const int cap = grid_cap > 0 ? grid_cap : LAMB_MAX_GRID;
     const unsigned grid = (unsigned)(n_chunks < cap ? n_chunks : cap);

@@ -4,7 +4,23 @@
 // One pass: reads p,g,m,v,ema_0..3 and a 1-byte weight-decay mask, writes p,m,v,ema_0..3 (60 B per
 // parameter instead of ~100 B and ~70 launches for foreach AdamW + 4 foreach lerps).  HBM-bound.
 #include "common.h"
+#include "slab_math.h"
 
+// The arguments of all eight instantiations of k_adamw_ema<GUARD, E16, GROUPED>; an instantiation reads the fields of its flags and
+// compiles to the code it would have without the others (`if constexpr` around every use).  The order of the fields is part of the
+// code: hipcc's register allocation follows it (profiles/optim_core_refactor.txt).
+//   GUARD (ap_adamw_ema_step_guarded): the bias corrections and the skip decision come from the ap_guard_state that ap_grad_health
+//     committed for this step.  A skipped step (a non-finite gradient element) reads neither g, m nor v and writes neither p, m, v nor
+//     p16; the EMA copies still take their lerp towards the unchanged parameters (the reference updates its ModelEma list whether or not
+//     apex skipped the step, main_prog.py:1030-1033).
+//   E16 (ap_adamw_ema_step_ema16): one bf16 slab per EMA copy (nullptr: that copy is not emitted).  An emitted copy is the rounding of
+//     the fp32 lerp that is stored beside it (pack_bf2, as p16), from the registers that hold it: 2 bytes per parameter and copy more, no
+//     second pass.  A skipped guarded step moves the EMA copies and so writes their bf16 copies as well.
+//   GROUPED (ap_adamw_ema_step_groups): a device table of {lr, weight_decay} per parameter group.  The byte slab the kernel reads per
+//     element (`wd_mask` otherwise) then holds the element's GROUP; lr and wd are not read.  Every workgroup forms the two numbers a
+//     group contributes -- the decay factor 1 - lr*wd and the step size lr / bc1 -- once, in LDS, and the inner loop looks both up per
+//     element (a float4 may straddle groups: tensors of odd length sit back to back in the slab).
+struct AdamGroupEntry { float lr, wd; };
 struct AdamArgs {
     float lr, beta1, beta2, eps, wd, bc1, bc2_sqrt;   // bc1 = 1-beta1^t, bc2_sqrt = sqrt(1-beta2^t)
     float gscale;                                      // gradient pre-scale (1/world_size: the data-parallel mean)
@@ -15,41 +31,17 @@ struct AdamArgs {
     int n_ema;
     float decay[4];
     float* ema[4];
+    const ap_guard_state* guard;                       // GUARD
+    const AdamGroupEntry* group_tab;                   // GROUPED
+    int n_groups;
+    bf16_t* ema16[4];                                  // E16
 };
-
-// Guarded arguments (ap_adamw_ema_step_guarded): the bias corrections and the skip decision come from the ap_guard_state that
-// ap_grad_health committed for this step.  A skipped step (a non-finite gradient element) reads neither g, m nor v and writes neither
-// p, m, v nor p16; the EMA copies still take their lerp towards the unchanged parameters (the reference updates its ModelEma list whether
-// or not apex skipped the step, main_prog.py:1030-1033).  With plain AdamArgs `skip` is a constant and the kernel is the one it was.
-struct AdamGuardArgs : AdamArgs { const ap_guard_state* guard; };
-
-// Arguments of ap_adamw_ema_step_ema16: either set above plus one bf16 slab per EMA copy (nullptr: that copy is not emitted).  An emitted
-// copy is the rounding of the fp32 lerp that is stored beside it (pack_bf2, as p16), from the registers that hold it: 2 bytes per
-// parameter and copy more, no second pass.  A skipped guarded step moves the EMA copies and so writes their bf16 copies as well.  The
-// two instantiations without these pointers compile to the code they were: the store below is discarded for them.
-template <class Base> struct Ema16Args : Base { bf16_t* ema16[4]; };
-template <class T> struct has_ema16 { static constexpr bool value = false; };
-template <class Base> struct has_ema16<Ema16Args<Base>> { static constexpr bool value = true; };
-
-// Arguments of ap_adamw_ema_step_groups: any set above plus a device table of {lr, weight_decay} per parameter group.  The byte slab the
-// kernel reads per element (`wd_mask` in the other instantiations) then holds the element's GROUP; a.lr and a.wd are not read.  Every
-// workgroup forms the two numbers a group contributes -- the decay factor 1 - lr*wd and the step size lr / bc1 -- once, in LDS, and the
-// inner loop looks both up per element (a float4 may straddle groups: tensors of odd length sit back to back in the slab).  The
-// instantiations without the table declare no LDS and compile to the code they were.
-struct AdamGroupEntry { float lr, wd; };
-template <class Base> struct GroupArgs : Base { const AdamGroupEntry* group_tab; int n_groups; };
-template <class T> struct is_grouped { static constexpr bool value = false; };
-template <class Base> struct is_grouped<GroupArgs<Base>> { static constexpr bool value = true; };
-template <class Base> struct has_ema16<GroupArgs<Base>> { static constexpr bool value = has_ema16<Base>::value; };
 constexpr int ADAM_MAX_GROUPS = 256;                   // one byte per element
 
-template <class Args>
+template <bool GUARD, bool E16, bool GROUPED>
 __global__ void __launch_bounds__(256)
 k_adamw_ema(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-            const unsigned char* __restrict__ wd_mask, int64_t n, Args a, bf16_t* __restrict__ p16) {
-    constexpr bool GUARD = __is_base_of(AdamGuardArgs, Args);
-    constexpr bool E16 = has_ema16<Args>::value;
-    constexpr bool GROUPED = is_grouped<Args>::value;
+            const unsigned char* __restrict__ wd_mask, int64_t n, AdamArgs a, bf16_t* __restrict__ p16) {
     const int64_t nv = n >> 2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     if constexpr (GROUPED) { if (a.step_dev) { a.bc1 = a.step_dev[1]; a.bc2_sqrt = a.step_dev[2]; } }      // (the rates come from the table)
@@ -72,11 +64,7 @@ k_adamw_ema(float* __restrict__ p, const float* __restrict__ g, float* __restric
     // gradient clipping folded into the update (prog/scaler.py:60-68 -> timm dispatch_clip_grad, main_prog.py:1019-1027):
     // mode 'norm' = torch.nn.utils.clip_grad_norm_: coef = min(1, max_norm / (||g|| + 1e-6)) with ||g|| the norm of the MEAN gradient
     // (gscale * the norm of the slab, which holds the all-reduced SUM under a deferred mean); mode 'value': clamp every element
-    float gs = a.gscale;
-    if (a.gnorm_sq) {
-        const float total = sqrtf(a.gnorm_sq[0]) * a.gscale;
-        gs *= fminf(1.0f, a.max_norm / (total + 1e-6f));
-    }
+    const float gs = clip_gscale(a.gscale, a.gnorm_sq, a.max_norm);
     const float cv = a.clip_value;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
         float4 pp = reinterpret_cast<float4*>(p)[i];
@@ -142,7 +130,7 @@ k_sumsq_partial(const float* __restrict__ x, int64_t n, double* __restrict__ par
     }
     double s = (double)s0 + (double)s1 + (double)s2 + (double)s3;
     if (blockIdx.x == 0 && threadIdx.x == 0) for (int64_t i = nv << 2; i < n; ++i) s += (double)x[i] * (double)x[i];     // (n % 4 tail)
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
@@ -172,75 +160,39 @@ extern "C" int ap_sumsq_f32(const float* x, int64_t n, float* out, void* workspa
     return ap_check_launch();
 }
 
-// the grouped launch of one argument set: the same arguments under one more layer, the byte slab read as group numbers
-template <class Base>
-static void adamw_ema_launch_grouped(const Base& base, const float* group_tab, int n_groups, unsigned grid, hipStream_t stream, float* p,
-                                     const float* g, float* m, float* v, const unsigned char* group_id, int64_t n, bf16_t* p16) {
-    GroupArgs<Base> ga;
-    static_cast<Base&>(ga) = base;
-    ga.group_tab = reinterpret_cast<const AdamGroupEntry*>(group_tab);
-    ga.n_groups = n_groups;
-    hipLaunchKernelGGL(k_adamw_ema<GroupArgs<Base>>, dim3(grid), dim3(256), 0, stream, p, g, m, v, group_id, n, ga, p16);
-}
-
-// the argument checks and the launch all entry points share; `guard` selects the guarded instantiation, `ema16` (an array of 4, entries
-// past n_ema already checked to be null) the ones that emit bf16 copies of EMA slabs, `group_tab` (n_groups already checked) the ones
-// that read wd_mask as group numbers
+// the argument checks and the launch all entry points share.  `guard` selects the guarded instantiations, `ema16` (an array of 4) the ones
+// that emit bf16 copies of EMA slabs, `group_tab` (n_groups already checked) the ones that read wd_mask as group numbers
 static int adamw_ema_launch(float* p, const float* g, float* m, float* v, const unsigned char* wd_mask, int64_t n,
                             float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
                             const float* gnorm_sq, float max_norm, float clip_value, const float* step_scalars_dev,
                             float* const* ema, const float* ema_decay, int n_ema, ap_bf16* p_bf16, const ap_guard_state* guard, ap_stream_t stream,
                             ap_bf16* const* ema16 = nullptr, const float* group_tab = nullptr, int n_groups = 0) {
+    using Kernel = void (*)(float*, const float*, float*, float*, const unsigned char*, int64_t, AdamArgs, bf16_t*);
+    static const Kernel kernels[8] = {                  // [guard | e16 << 1 | grouped << 2]
+        k_adamw_ema<false, false, false>, k_adamw_ema<true, false, false>, k_adamw_ema<false, true, false>, k_adamw_ema<true, true, false>,
+        k_adamw_ema<false, false, true>,  k_adamw_ema<true, false, true>,  k_adamw_ema<false, true, true>,  k_adamw_ema<true, true, true>};
+    // a refused bf16 copy comes before a null slab, the entry points' order of checks; slab_ema_args below makes the same check again per
+    // copy (it is ap_lamb_ema_step's one) and can no longer fail on it here
+    for (int e = 0; ema16 && e < 4; ++e) if (ema16_refused(ema16[e], e, n_ema)) return AP_ERR_SHAPE;
     if (!p || !g || !m || !v || !wd_mask) return AP_ERR_NULL;
     if (n <= 0 || (n & 3) || n_ema < 0 || n_ema > 4 || step < 1) return AP_ERR_SHAPE;
     if (gnorm_sq && !(max_norm > 0.f)) return AP_ERR_SHAPE;
-    AdamGuardArgs a;
+    AdamArgs a;
     a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay; a.gscale = grad_scale;
     a.gnorm_sq = gnorm_sq; a.max_norm = max_norm; a.clip_value = clip_value > 0.f ? clip_value : 0.f; a.step_dev = step_scalars_dev;
-    // (in double from the float arguments, rounded once: graph.StepScalars.set_adam forms the SAME two numbers on the host, so a step
-    // replayed from a graph -- which reads them from device memory -- is bit-identical to the eager step)
-    a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-    a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+    adam_bias_corrections(beta1, beta2, step, a.bc1, a.bc2_sqrt);
     a.n_ema = n_ema;
-    for (int e = 0; e < 4; ++e) { a.ema[e] = (e < n_ema) ? ema[e] : nullptr; a.decay[e] = (e < n_ema) ? ema_decay[e] : 0.f; if (e < n_ema && !ema[e]) return AP_ERR_NULL; }
+    if (const int rc = slab_ema_args(ema, ema_decay, n_ema, ema16, 0, a.ema, a.decay, a.ema16)) return rc;
     a.guard = guard;
+    a.group_tab = reinterpret_cast<const AdamGroupEntry*>(group_tab);
+    a.n_groups = n_groups;
+    // (four null entries: nothing to emit, the launch is the one without the pointers)
+    const bool e16 = a.ema16[0] || a.ema16[1] || a.ema16[2] || a.ema16[3];
     int64_t grid = (n / 4 + 255) / 256;
     if (grid > 256 * 16) grid = 256 * 16;
     (void)hipGetLastError();
-    if (group_tab) {                                    // the same four argument sets, grouped
-        hipStream_t s = (hipStream_t)stream;
-        bf16_t* p16 = reinterpret_cast<bf16_t*>(p_bf16);
-        if (ema16 && (ema16[0] || ema16[1] || ema16[2] || ema16[3])) {
-            Ema16Args<AdamGuardArgs> b;
-            static_cast<AdamGuardArgs&>(b) = a;
-            for (int e = 0; e < 4; ++e) b.ema16[e] = reinterpret_cast<bf16_t*>(ema16[e]);
-            if (guard) adamw_ema_launch_grouped(b, group_tab, n_groups, (unsigned)grid, s, p, g, m, v, wd_mask, n, p16);
-            else {
-                Ema16Args<AdamArgs> c;
-                static_cast<AdamArgs&>(c) = a;
-                for (int e = 0; e < 4; ++e) c.ema16[e] = b.ema16[e];
-                adamw_ema_launch_grouped(c, group_tab, n_groups, (unsigned)grid, s, p, g, m, v, wd_mask, n, p16);
-            }
-        } else if (guard) adamw_ema_launch_grouped(a, group_tab, n_groups, (unsigned)grid, s, p, g, m, v, wd_mask, n, p16);
-        else adamw_ema_launch_grouped(static_cast<const AdamArgs&>(a), group_tab, n_groups, (unsigned)grid, s, p, g, m, v, wd_mask, n, p16);
-        return ap_check_launch();
-    }
-    // (four null entries: nothing to emit, the launch is the one without the pointers)
-    if (ema16 && (ema16[0] || ema16[1] || ema16[2] || ema16[3])) {
-        Ema16Args<AdamGuardArgs> b;
-        static_cast<AdamGuardArgs&>(b) = a;
-        for (int e = 0; e < 4; ++e) b.ema16[e] = reinterpret_cast<bf16_t*>(ema16[e]);
-        if (guard) hipLaunchKernelGGL(k_adamw_ema<Ema16Args<AdamGuardArgs>>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, wd_mask, n, b, p_bf16);
-        else {
-            Ema16Args<AdamArgs> c;
-            static_cast<AdamArgs&>(c) = a;
-            for (int e = 0; e < 4; ++e) c.ema16[e] = b.ema16[e];
-            hipLaunchKernelGGL(k_adamw_ema<Ema16Args<AdamArgs>>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, wd_mask, n, c, p_bf16);
-        }
-        return ap_check_launch();
-    }
-    if (guard) hipLaunchKernelGGL(k_adamw_ema<AdamGuardArgs>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, wd_mask, n, a, p_bf16);
-    else hipLaunchKernelGGL(k_adamw_ema<AdamArgs>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, wd_mask, n, static_cast<const AdamArgs&>(a), p_bf16);
+    hipLaunchKernelGGL(kernels[(guard ? 1 : 0) | (e16 ? 2 : 0) | (group_tab ? 4 : 0)], dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream,
+                       p, g, m, v, wd_mask, n, a, reinterpret_cast<bf16_t*>(p_bf16));
     return ap_check_launch();
 }
 
@@ -275,10 +227,6 @@ extern "C" int ap_adamw_ema_step_ema16(float* p, const float* g, float* m, float
                                        const ap_guard_state* guard_or_null, ap_stream_t stream) {
     if (!ema_bf16) return AP_ERR_NULL;
     if (n_ema < 0 || n_ema > 4) return AP_ERR_SHAPE;
-    for (int e = 0; e < 4; ++e) {
-        if (!ema_bf16[e]) continue;
-        if (e >= n_ema || ((uintptr_t)ema_bf16[e] & 7)) return AP_ERR_SHAPE;
-    }
     return adamw_ema_launch(p, g, m, v, wd_mask, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, gnorm_sq, max_norm, clip_value,
                             step_scalars_dev, ema, ema_decay, n_ema, p_bf16, guard_or_null, stream, ema_bf16);
 }
@@ -295,10 +243,6 @@ extern "C" int ap_adamw_ema_step_groups(float* p, const float* g, float* m, floa
     if (!group_id || !group_tab_dev) return AP_ERR_NULL;
     if (n_groups < 1 || n_groups > ADAM_MAX_GROUPS || ((uintptr_t)group_tab_dev & 7)) return AP_ERR_SHAPE;
     if (n_ema < 0 || n_ema > 4) return AP_ERR_SHAPE;
-    for (int e = 0; ema_bf16 && e < 4; ++e) {
-        if (!ema_bf16[e]) continue;
-        if (e >= n_ema || ((uintptr_t)ema_bf16[e] & 7)) return AP_ERR_SHAPE;
-    }
     return adamw_ema_launch(p, g, m, v, group_id, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, gnorm_sq, max_norm, clip_value,
                             step_scalars_dev, ema, ema_decay, n_ema, p_bf16, guard_or_null, stream, ema_bf16, group_tab_dev, n_groups);
 }
@@ -315,17 +259,6 @@ extern "C" int ap_adamw_ema_step_groups(float* p, const float* g, float* m, floa
 // the second kernel add theirs with integer atomics and the one that draws the last ticket commits the step.
 constexpr int GH_CHUNK = 8192;          // 256 lanes x 8 float4
 constexpr int GH_MAX_GRID = 2048;       // 8 workgroups on each of 256 CUs
-
-__device__ __forceinline__ void gh_add(float x, double& s, int& c) {
-    const bool bad = (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u;          // exponent all ones: +-inf, NaN
-    const double d = bad ? 0.0 : (double)x;
-    s = fma(d, d, s);
-    c += bad ? 1 : 0;
-}
-
-__device__ __forceinline__ void gh_wave_reduce(double& s, int& c) {
-    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o, 64); c += __shfl_xor(c, o, 64); }
-}
 
 __global__ void __launch_bounds__(256)
 k_grad_health(const float* __restrict__ g, int64_t n, const int64_t* __restrict__ seg_off, int n_seg, int64_t n_chunks, int per_wg,
@@ -352,10 +285,10 @@ k_grad_health(const float* __restrict__ g, int64_t n, const int64_t* __restrict_
             double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
             int cnt = 0;
 #pragma unroll
-            for (int k = 0; k < 8; ++k) { gh_add(x[k].x, a0, cnt); gh_add(x[k].y, a1, cnt); gh_add(x[k].z, a2, cnt); gh_add(x[k].w, a3, cnt); }
+            for (int k = 0; k < 8; ++k) { sq_add_finite(x[k].x, a0, cnt); sq_add_finite(x[k].y, a1, cnt); sq_add_finite(x[k].z, a2, cnt); sq_add_finite(x[k].w, a3, cnt); }
             double s = (a0 + a1) + (a2 + a3);
-            if ((int)threadIdx.x < (len & 3)) gh_add(g[c0 + (nv << 2) + threadIdx.x], s, cnt);      // (the slab's n % 4 tail)
-            gh_wave_reduce(s, cnt);
+            if ((int)threadIdx.x < (len & 3)) sq_add_finite(g[c0 + (nv << 2) + threadIdx.x], s, cnt);      // (the slab's n % 4 tail)
+            wave_sum(s, cnt);
             if (lane == 0) { red_s[wave] = s; red_c[wave] = cnt; }
             __syncthreads();
             if (threadIdx.x == 0) {
@@ -373,8 +306,8 @@ k_grad_health(const float* __restrict__ g, int64_t n, const int64_t* __restrict_
                 double acc = 0.0;
                 int cnt = 0;
 #pragma unroll 4
-                for (int64_t i = from + lane; i < to; i += 64) gh_add(g[i], acc, cnt);
-                gh_wave_reduce(acc, cnt);
+                for (int64_t i = from + lane; i < to; i += 64) sq_add_finite(g[i], acc, cnt);
+                wave_sum(acc, cnt);
                 if (lane == 0) { part_s[c + s] = acc; part_c[c + s] = cnt; }
             }
         }
@@ -400,7 +333,7 @@ k_grad_health_final(const double* __restrict__ part_s, const int* __restrict__ p
             if (ch > n_chunks - 1) ch = n_chunks - 1;
             for (int64_t c = cl + lane; c <= ch; c += 64) { acc += part_s[c + s]; cnt += part_c[c + s]; }
         }
-        gh_wave_reduce(acc, cnt);
+        wave_sum(acc, cnt);
         if (lane == 0) { seg_sumsq[s] = acc; seg_nonfinite[s] = cnt; }
     }
     if (lane == 0) tot[wave] = cnt;

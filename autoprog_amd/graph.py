@@ -171,17 +171,12 @@ class GraphedStep:
 
     def capture(self, warmup=3):
         self.model.step_scalars = self.scalars
-        if self.skip_nonfinite:
-            self.opt._guard_workspace(self.images.device)         # (the same rule for the guard's table, outputs, record and workspace)
-        if self.clip_grad is not None and float(self.clip_grad) > 0 and self.clip_mode == "norm":
-            self.opt._clip_workspace(self.images.device)          # (never first allocated inside the capture: optim.FlatAdamWEma._clip_workspace)
-        if self._agc:
-            self.opt._agc_workspace(self.images.device)           # (the same rule for the unit table, the factors and the tallies)
-        # which optimizer launch the graph holds: the one with a parameter-group table or the one without.  Its buffers follow the same
-        # rule as the workspaces above; step() refuses to replay once the optimizer's groups ask for the other launch
+        # whatever this step's optimizer calls allocate on first use is never first allocated inside the capture (optim._outside_capture)
+        self.opt.prepare_capture(self.images.device, clip_grad=self.clip_grad, clip_mode=self.clip_mode, skip_nonfinite=self.skip_nonfinite,
+                                 agc=self._agc)
+        # which optimizer launch the graph holds: the one with a parameter-group table or the one without; step() refuses to replay once
+        # the optimizer's groups ask for the other launch
         self._grouped = bool(getattr(self.opt, "grouped", False))
-        if self._grouped:
-            self.opt._group_workspace(self.images.device)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):

@@ -13,6 +13,7 @@ Parameter groups: `FlatAdamWEma(param_groups=[...])` takes torch.optim-style gro
 
 `FlatLambEma` is the same optimizer under LAMB's rule, one trust ratio per parameter tensor (`ap_lamb_ema_step`); `make_flat_optimizer`
 maps the reference's `--opt` names onto the two."""
+import collections
 import ctypes
 
 import torch
@@ -21,30 +22,42 @@ from ._lib import check, lib
 from . import ops
 
 
+SlabTensor = collections.namedtuple("SlabTensor", "name offset numel shape param")
+
+
+def slab_layout(reducer, model=None, who="slab_layout"):
+    """THE layout of the reducer's slab: one SlabTensor (name, offset, numel, shape, param) per parameter tensor in slab order -- the
+    reversed parameter order (dist.GradientBucketReducer) --, read from where each gradient view sits, not from an assumed order.  name is
+    the one `model.named_parameters()` gives the tensor (a shared parameter appears once, under its first name; "" without a model).
+    Every table of the flat-slab optimizers (grad_segments, agc_units, lamb_chunks, FlatAdamWEma's views) is cut from this list.
+    Raises ValueError, `who` in front, when the gradient views do not tile the slab exactly once.  Needs no device."""
+    flat = reducer.flat
+    base, size = flat.data_ptr(), flat.element_size()
+    names = {id(p): n for n, p in model.named_parameters()} if model is not None else {}
+    out, end = [], 0
+    for off, i in sorted(((p.grad.data_ptr() - base) // size, i) for i, p in enumerate(reducer.params)):
+        p = reducer.params[i]
+        name = names.get(id(p), "")
+        if off != end:
+            raise ValueError("%s: the gradient of %r starts at %d, the slab is covered up to %d" % (who, name, off, end))
+        out.append(SlabTensor(name, off, p.numel(), p.shape, p))
+        end = off + p.numel()
+    if end != flat.numel():
+        raise ValueError("%s: the gradients cover %d of the slab's %d elements" % (who, end, flat.numel()))
+    return out
+
+
 def grad_segments(reducer, model=None):
     """the segment table of the gradient health pass (ap_grad_health): one segment per parameter tensor of the reducer's slab, in slab
-    order -- the reversed parameter order (dist.GradientBucketReducer) -- read from where each gradient view sits, not from an assumed
-    order.  -> (offsets, names): offsets has one entry more than there are tensors, ascending from 0 to the slab's length; names[i] is the
-    name `model.named_parameters()` gives tensor i (a shared parameter appears once, under its first name; "" without a model).
-    Raises ValueError when the gradient views do not tile the slab exactly once."""
-    flat = reducer.flat
-    base, total = flat.data_ptr(), flat.numel()
-    names = {id(p): n for n, p in model.named_parameters()} if model is not None else {}
-    items = sorted(((p.grad.data_ptr() - base) // flat.element_size(), p.numel(), names.get(id(p), "")) for p in reducer.params)
-    offsets, out_names = [0], []
-    for off, n, name in items:
-        if off != offsets[-1]:
-            raise ValueError("grad_segments: the gradient of %r starts at %d, the slab is covered up to %d" % (name, off, offsets[-1]))
-        offsets.append(off + n)
-        out_names.append(name)
-    if offsets[-1] != total:
-        raise ValueError("grad_segments: the gradients cover %d of the slab's %d elements" % (offsets[-1], total))
-    return offsets, out_names
+    order (slab_layout).  -> (offsets, names): offsets has one entry more than there are tensors, ascending from 0 to the slab's length;
+    names[i] is the name of tensor i.  Raises ValueError when the gradient views do not tile the slab exactly once."""
+    layout = slab_layout(reducer, model, "grad_segments")
+    return [0] + [t.offset + t.numel for t in layout], [t.name for t in layout]
 
 
 def agc_units(reducer, model=None, exclude=None):
     """the unit table of adaptive gradient clipping (ap_agc_clip; the rule: include/autoprog_hip.h) for the reducer's slab, in slab order,
-    read from where each gradient view sits as grad_segments reads its segments.  A parameter tensor with ndim <= 1 is one unit; one with
+    read from where each gradient view sits (slab_layout).  A parameter tensor with ndim <= 1 is one unit; one with
     ndim >= 2 has shape[0] units of numel / shape[0] contiguous elements (a Linear [out, in]: `out` rows; a conv [O, I, k, k]: O units;
     pos_embed [1, g, g, C] and cls_token [1, 1, C]: one unit each).  An excluded tensor is ONE unit with its skip byte set.
     exclude: None -- the reference's rule, timm's model_parameters(model, exclude_head=True) = list(model.parameters())[:-2]: the LAST TWO
@@ -54,10 +67,7 @@ def agc_units(reducer, model=None, exclude=None):
     -> (offsets, skip, names): offsets has one entry more than there are units, ascending from 0 to the slab's length; skip[u] is 1 for an
     excluded tensor's unit; names[u] is "blocks.3.mlp.fc1.weight[17]" for row 17 of a tensor cut into rows, the tensor's name for a tensor
     that is one unit."""
-    flat = reducer.flat
-    base = flat.data_ptr()
     by_name = dict(model.named_parameters()) if model is not None else {}
-    names = {id(p): n for n, p in by_name.items()}
     if exclude is None:
         excluded = {id(p) for p in list(model.parameters())[-2:]} if model is not None else set()
     else:
@@ -69,14 +79,9 @@ def agc_units(reducer, model=None, exclude=None):
                 excluded.add(id(by_name[item]))
             else:
                 excluded.add(id(item))
-    items = sorted(((p.grad.data_ptr() - base) // flat.element_size(), i) for i, p in enumerate(reducer.params))
     offsets, skip, out_names = [0], [], []
-    for off, i in items:
-        p = reducer.params[i]
-        name, n = names.get(id(p), ""), p.numel()
-        if off != offsets[-1]:
-            raise ValueError("agc_units: the gradient of %r starts at %d, the slab is covered up to %d" % (name, off, offsets[-1]))
-        rows = p.shape[0] if p.dim() >= 2 else 1
+    for name, off, n, shape, p in slab_layout(reducer, model, "agc_units"):
+        rows = shape[0] if len(shape) >= 2 else 1
         if id(p) in excluded or rows <= 1 or n == 0:
             offsets.append(off + n)
             skip.append(1 if id(p) in excluded else 0)
@@ -86,8 +91,6 @@ def agc_units(reducer, model=None, exclude=None):
             offsets.extend(range(off + w, off + n + 1, w))
             skip.extend([0] * rows)
             out_names.extend("%s[%d]" % (name, r) for r in range(rows))
-    if offsets[-1] != flat.numel():
-        raise ValueError("agc_units: the gradients cover %d of the slab's %d elements" % (offsets[-1], flat.numel()))
     return offsets, skip, out_names
 
 
@@ -99,6 +102,14 @@ def lamb_chunks(reducer, model=None):
     once, none crosses a tensor, tensor numbers ascend.  Needs no device."""
     offsets, names = grad_segments(reducer, model)
     return ops.lamb_chunk_table(offsets), names
+
+
+def _outside_capture(message):
+    """the one rule of every buffer the optimizers allocate on first use: never while a stream is being captured.  A tensor first
+    allocated inside a capture would come from that graph's private pool and then be shared with eager steps and other graphs through
+    the optimizer's cache -- prepare_capture() allocates in front of the capture.  RuntimeError(message) otherwise."""
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(message)
 
 
 MAX_PARAM_GROUPS = 256             # the update kernel reads a parameter's group from one byte per element
@@ -253,8 +264,11 @@ class FlatAdamWEma:
         # torch.optim-style groups (timm's create_optimizer layout: decayed, then un-decayed parameters).  step() reads
         # `lr` / `weight_decay` from here every call, so timm LR schedulers that write param_groups[i]["lr"] work unchanged.
         self._explicit_groups = param_groups is not None
-        names = {id(p): n_ for n_, p in model.named_parameters()}
+        # one record per parameter (slab_layout), kept in reducer.params order: where it sits in every slab of this optimizer
+        self._slot = {id(t.param): t for t in slab_layout(reducer, model, "FlatAdamWEma")}
+        self._layout = [self._slot[id(p)] for p in reducer.params]
         if self._explicit_groups:
+            names = {id(p): n_ for n_, p in model.named_parameters()}
             self.param_groups, group_of = resolve_param_groups(reducer.params, param_groups, lr, weight_decay, betas, eps, names)
         else:
             self.param_groups = [{"lr": lr, "weight_decay": weight_decay, "betas": betas, "eps": eps, "params": []},
@@ -271,15 +285,12 @@ class FlatAdamWEma:
         # (an explicit group list always takes the grouped launch, which reads `group_id` in the mask's place)
         self.wd_mask = None if self._explicit_groups else torch.zeros(self.n_pad, dtype=torch.uint8, device=dev)
         skip = set(model.no_weight_decay()) if hasattr(model, "no_weight_decay") else set()
-        base = flat_g.data_ptr()
-        self._views = []
+        self._views = [(t.name, t.offset, t.shape) for t in self._layout]
         self._group_of = []                                      # per parameter of reducer.params: its group (static: it follows the parameter)
-        for p in reducer.params:
-            off = (p.grad.data_ptr() - base) // 4
+        for name, off, _, _, p in self._layout:
             view = self.p[off:off + p.numel()].view_as(p)
             view.copy_(p.data)
             p.data = view                                   # parameters now live in the slab
-            name = names.get(id(p), "")
             decay = not (p.dim() == 1 or name.endswith(".bias") or name in skip)
             if decay and self.wd_mask is not None:
                 self.wd_mask[off:off + p.numel()] = 1
@@ -288,7 +299,6 @@ class FlatAdamWEma:
             else:
                 self.param_groups[0 if decay else 1]["params"].append(p)
                 self._group_of.append(0 if decay else 1)
-            self._views.append((name, off, p.shape))
         self.m = torch.zeros_like(self.p)
         self.v = torch.zeros_like(self.p)
         self.ema = [self.p.clone() for _ in self.ema_decays]
@@ -362,19 +372,15 @@ class FlatAdamWEma:
         return not (self._lr_eff(g0) == self._lr_eff(g1) and float(g1["weight_decay"]) == 0.0)
 
     def _group_workspace(self, device):
-        """the buffers of the grouped launch, allocated once and OUTSIDE any stream capture (see _clip_workspace; GraphedStep.capture()
-        calls this first): `group_id`, one byte per element of the padded slab from the parameters' slab offsets (the tail padding goes
-        to group 0), the device table [G, 2] of {lr * lr_scale, weight_decay} and the pinned ring its host side is written into."""
+        """the buffers of the grouped launch, allocated once and OUTSIDE any stream capture (_outside_capture): `group_id`, one byte per
+        element of the padded slab from the parameters' slab offsets (the tail padding goes to group 0), the device table [G, 2] of
+        {lr * lr_scale, weight_decay} and the pinned ring its host side is written into."""
         if self._groups is None:
-            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("FlatAdamWEma: the parameter-group buffers must exist before a step is captured (call _group_workspace first)")
+            _outside_capture("FlatAdamWEma: the parameter-group buffers must exist before a step is captured (call _group_workspace first)")
             from .ring import PinnedRing
             ids = torch.zeros(self.n_pad, dtype=torch.uint8)
-            for gi, (_, off, shape) in zip(self._group_of, self._views):
-                n = 1
-                for d in shape:
-                    n *= d
-                ids[off:off + n] = gi
+            for gi, t in zip(self._group_of, self._layout):
+                ids[t.offset:t.offset + t.numel] = gi
             self._groups = {"group_id": ids.to(device), "table": torch.zeros(len(self.param_groups), 2, dtype=torch.float32, device=device),
                             "ring": PinnedRing(device), "pushed": False}
         return self._groups
@@ -471,8 +477,7 @@ class FlatAdamWEma:
         i = self._ema_index(i, "ema_model")
         if i in self._shadows:
             return self._shadows[i]
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("FlatAdamWEma.ema_model: the first call for a copy allocates its bf16 slab and must come before a step is captured")
+        _outside_capture("FlatAdamWEma.ema_model: the first call for a copy allocates its bf16 slab and must come before a step is captured")
         import copy
         slab = self.ema[i]
         e16 = torch.empty(self.n_pad, dtype=torch.bfloat16, device=slab.device)
@@ -514,8 +519,7 @@ class FlatAdamWEma:
         i = self._ema_index(i, "release_ema_model")
         if i not in self._shadows:
             raise KeyError("FlatAdamWEma.release_ema_model: EMA copy %d has no shadow module (ema_model(%d) was never called, or it was released)" % (i, i))
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("FlatAdamWEma.release_ema_model: not while a step is being captured")
+        _outside_capture("FlatAdamWEma.release_ema_model: not while a step is being captured")
         shadow = self._shadows.pop(i)
         for q in shadow.parameters():
             q.__dict__.pop("_ap_flat16", None)               # (a surviving reference falls back to the keyed casts of the weight bank)
@@ -527,24 +531,33 @@ class FlatAdamWEma:
             check(lib.ap_batched_transpose_bf16(self.p16.data_ptr(), self.p16_t.data_ptr(), self._tr_desc.data_ptr(), self._tr_count,
                                                 self._tr_tiles, ops._stream()), "ap_batched_transpose_bf16")
 
+    def prepare_capture(self, device, clip_grad=None, clip_mode="norm", skip_nonfinite=False, agc=False):
+        """every buffer that a step of these arguments allocates on first use, now: graph.GraphedStep.capture() calls this in front of
+        its capture (_outside_capture).  clip_grad / clip_mode / skip_nonfinite: step()'s; agc: adaptive_clip_grad() runs in front."""
+        if skip_nonfinite:
+            self._guard_workspace(device)
+        if clip_grad is not None and float(clip_grad) > 0 and clip_mode == "norm":
+            self._clip_workspace(device)
+        if agc:
+            self._agc_workspace(device)
+        if self.grouped:
+            self._group_workspace(device)
+
     def _clip_workspace(self, device):
-        """the norm's workspace, allocated OUTSIDE any stream capture: a tensor first allocated while a step is being captured
-        (GraphedStep(clip_grad=...).capture(warmup=0)) would come from that graph's private pool and then be shared with eager steps
-        and other graphs through this cache -- GraphedStep.capture() calls this before it starts capturing"""
+        """the norm's workspace, allocated once and OUTSIDE any stream capture (_outside_capture; a GraphedStep(clip_grad=...)
+        .capture(warmup=0) would otherwise allocate it inside the capture)"""
         if getattr(self, "_sumsq_ws", None) is None:
-            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("FlatAdamWEma: the clip-norm workspace must exist before a step is captured (call _clip_workspace first)")
+            _outside_capture("FlatAdamWEma: the clip-norm workspace must exist before a step is captured (call _clip_workspace first)")
             self._sumsq_ws = torch.empty(lib.ap_sumsq_workspace() // 8, dtype=torch.float64, device=device)
             self._gnorm_sq = torch.zeros(1, dtype=torch.float32, device=device)
 
     def _guard_workspace(self, device):
-        """the buffers of the non-finite guard, allocated once and OUTSIDE any stream capture (see _clip_workspace; GraphedStep.capture()
-        calls this first): the segment table, ONE buffer holding the per-tensor sums of squares (fp64) and non-finite counts (int32) --
-        one read-back for grad_health() --, the ap_guard_state record and the pass's workspace.  The record's applied count starts at
-        `step_count`: a run that turns the guard on after a resume continues Adam's bias corrections where they were."""
+        """the buffers of the non-finite guard, allocated once and OUTSIDE any stream capture (_outside_capture): the segment table, ONE
+        buffer holding the per-tensor sums of squares (fp64) and non-finite counts (int32) -- one read-back for grad_health() --, the
+        ap_guard_state record and the pass's workspace.  The record's applied count starts at `step_count`: a run that turns the guard
+        on after a resume continues Adam's bias corrections where they were."""
         if self._guard is None:
-            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("FlatAdamWEma: the guard's buffers must exist before a step is captured (call _guard_workspace first)")
+            _outside_capture("FlatAdamWEma: the guard's buffers must exist before a step is captured (call _guard_workspace first)")
             offsets, names = grad_segments(self.reducer, self.model)
             n, n_seg = offsets[-1], len(names)
             out = torch.zeros(12 * n_seg, dtype=torch.uint8, device=device)
@@ -580,10 +593,10 @@ class FlatAdamWEma:
 
     # ------------------------------------------------------------------ adaptive gradient clipping (the reference's --clip-mode agc)
     def _agc_workspace(self, device, exclude=None):
-        """the buffers of adaptive_clip_grad, allocated once and OUTSIDE any stream capture (see _clip_workspace; GraphedStep.capture()
-        calls this first): the unit table and skip bytes of agc_units, and ONE buffer holding the two tallies (int32) and the per-unit
-        factors (fp32) -- one read-back for agc_report().  exclude: None keeps the table that exists (the default rule of agc_units when
-        there is none yet); anything else builds the table for that exclusion, again only outside a capture."""
+        """the buffers of adaptive_clip_grad, allocated once and OUTSIDE any stream capture (_outside_capture): the unit table and skip
+        bytes of agc_units, and ONE buffer holding the two tallies (int32) and the per-unit factors (fp32) -- one read-back for
+        agc_report().  exclude: None keeps the table that exists (the default rule of agc_units when there is none yet); anything else
+        builds the table for that exclusion, again only outside a capture."""
         ws = self._agc
         if ws is not None and exclude is None:
             return ws
@@ -593,8 +606,7 @@ class FlatAdamWEma:
             key = tuple(x if isinstance(x, str) else id(x) for x in key)
             if ws is not None and ws["key"] == key:
                 return ws
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("FlatAdamWEma: the AGC unit table and outputs must exist before a step is captured (call _agc_workspace first)")
+        _outside_capture("FlatAdamWEma: the AGC unit table and outputs must exist before a step is captured (call _agc_workspace first)")
         offsets, skip, names = agc_units(self.reducer, self.model, exclude)
         n_units = len(names)
         out = torch.zeros(2 + n_units, dtype=torch.float32, device=device)
@@ -743,19 +755,16 @@ class FlatAdamWEma:
         from .prog.elastic import growth_sources
         if model_source not in ("ema_last", "model"):
             raise ValueError("grow: model_source must be 'ema_last' or 'model'")
-        where = {name: (off, shape) for name, off, shape in self._views}
+        where = {t.name: t for t in self._layout}
         src_of = growth_sources(list(where), old_mask, new_mask)
         with torch.no_grad():
             old = [e.clone() for e in self.ema] if self.ema else [self.p.clone()]
             old_model = self.p.clone() if (model_source == "model" or not self.ema) else old[-1]
-            for name, (off, shape) in where.items():
+            for name, off, n, shape, _ in where.values():
                 sname = src_of.get(name)
                 if sname is None:
                     continue                           # slot inactive in the new stage: untouched
-                soff, sshape = where[sname]
-                n = 1
-                for d in shape:
-                    n *= d
+                soff, sshape = where[sname].offset, where[sname].shape
                 if tuple(sshape) != tuple(shape):
                     raise ValueError("%s <- %s: shapes differ (width growth is a state-dict operation, prog/growth.py)" % (name, sname))
                 self.p[off:off + n].copy_(old_model[soff:soff + n])
@@ -804,10 +813,7 @@ class FlatAdamWEma:
         are views of the EMA slab, floating-point buffers (BatchNorm running stats) the lerp-averaged copies, integer buffers
         (num_batches_tracked) the model's current value -- as ModelEmaV2 keeps them."""
         out = {}
-        for name, off, shape in self._views:
-            n = 1
-            for d in shape:
-                n *= d
+        for name, off, n, shape, _ in self._layout:
             out[name] = self.ema[i][off:off + n].view(shape)
         ema_b = dict(zip((n for n, _ in self._float_buffers), self.ema_buffers[i])) if self.ema_buffers else {}
         for bname, b in self.model.named_buffers():
@@ -819,13 +825,12 @@ class FlatAdamWEma:
         """torch.optim.AdamW layout: {"state": {i: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups": [...]} with parameter indices
         in group order, plus the EMA slabs under "ema" (the reference keeps those in separate ModelEma objects)."""
         state, groups, idx = {}, [], 0
-        offs = {id(p): off for p, (_, off, _) in zip(self.reducer.params, self._views)}
         # Adam's t: once the guard has been used, the APPLIED steps (the device counter), not the calls of step()
         t = self.guard_counts()["applied"] if (self._guard is not None and self._guard["used"]) else self.step_count
         for g in self.param_groups:
             ids = []
             for p in g["params"]:
-                off, n = offs[id(p)], p.numel()
+                off, n = self._slot[id(p)].offset, p.numel()
                 state[idx] = {"step": torch.tensor(float(t)), "exp_avg": self.m[off:off + n].view_as(p).clone(),
                               "exp_avg_sq": self.v[off:off + n].view_as(p).clone()}
                 ids.append(idx)
@@ -835,7 +840,6 @@ class FlatAdamWEma:
                 "ema_buffers": [[b.clone() for b in bufs] for bufs in self.ema_buffers]}
 
     def load_state_dict(self, sd):
-        offs = {id(p): off for p, (_, off, _) in zip(self.reducer.params, self._views)}
         idx = 0
         if len(sd["param_groups"]) != len(self.param_groups):
             raise ValueError("FlatAdamWEma.load_state_dict: the state has %d parameter groups, the optimizer %d" % (len(sd["param_groups"]), len(self.param_groups)))
@@ -849,7 +853,7 @@ class FlatAdamWEma:
                 for p in g["params"]:
                     st = sd["state"].get(idx)
                     if st is not None:
-                        off, n = offs[id(p)], p.numel()
+                        off, n = self._slot[id(p)].offset, p.numel()
                         self.m[off:off + n].copy_(st["exp_avg"].reshape(-1))
                         self.v[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
                         self.step_count = int(st["step"])
@@ -892,12 +896,11 @@ class FlatLambEma(FlatAdamWEma):
         return True
 
     def _lamb_workspace(self, device):
-        """ALL device buffers the LAMB launch adds, allocated once and OUTSIDE any stream capture (see _clip_workspace): the chunk table
+        """ALL device buffers the LAMB launch adds, allocated once and OUTSIDE any stream capture (_outside_capture): the chunk table
         of lamb_chunks and every tensor's first chunk, ONE buffer [3, n_tensors] of wn, un, phi -- one read-back for trust_report() --
         and two fp64 partials per chunk."""
         if self._lamb is None:
-            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("FlatLambEma: the chunk table and the trust outputs must exist before a step is captured (call _lamb_workspace first)")
+            _outside_capture("FlatLambEma: the chunk table and the trust outputs must exist before a step is captured (call _lamb_workspace first)")
             table, names = lamb_chunks(self.reducer, self.model)
             chunks, first = ops.lamb_pack_chunks(table)
             n_chunks, n_tensors = int(table["start"].size), len(names)
@@ -906,11 +909,10 @@ class FlatLambEma(FlatAdamWEma):
                           "ws": torch.zeros(int(lib.ap_lamb_workspace(n_chunks)) // 8, dtype=torch.float64, device=device)}
         return self._lamb
 
-    def _group_workspace(self, device):
-        """the parent's buffers, and the LAMB launch's own with them: graph.GraphedStep.capture() asks for these in front of a capture"""
-        gw = super()._group_workspace(device)
+    def prepare_capture(self, device, **step_args):
+        """the parent's buffers, and the LAMB launch's own with them"""
+        super().prepare_capture(device, **step_args)
         self._lamb_workspace(device)
-        return gw
 
     def trust_report(self):
         """[(parameter name, wn = ||p||, un = ||update||, phi)] per parameter tensor in slab order, as the last APPLIED step measured them
