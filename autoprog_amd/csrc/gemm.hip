@@ -30,6 +30,7 @@
 #include "gemm_ws.h"
 #include "gemm_tn8p.h"
 #include "gemm_tn_fp8.h"
+#include "nt_plan.h"
 #include "tn_plan.h"
 // (the measured-and-rejected kernels of rounds 1 and 2 -- LDS-DMA rings, persistent 256-row tiles, the ring weight-gradient kernel -- and
 // their AP_GEMM_NT_P / _RING / _DMA, AP_GEMM_TN_RING switches live under tools/gemm_lab/rejected/, outside the product library)
@@ -326,7 +327,6 @@ k_gemm_nt(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ B, i
 // 3-9 workgroups walking K serially, one exposed memory latency per 64-deep step: 19-51 us inside the training step for
 // 0.04-0.1 GFLOP.  Here: 64x32 output tile per workgroup (24-72 workgroups), the 8 waves split K into 32-deep chunks, each
 // wave loads its MFMA fragments straight from global memory with up to three chunks in flight, partial sums meet in LDS.
-#define SK_STRIDE 36        // floats per LDS row of a wave's 64x32 partial tile (16-B aligned, spreads the banks)
 __global__ void __launch_bounds__(512)
 k_gemm_nt_skinny(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ B, int ldb, bf16_t* __restrict__ C, int ldc,
                  int M, int N, int K, EpiArgs ep) {
@@ -817,159 +817,87 @@ const unsigned* g8_gelu_table_ptr(hipStream_t st) {
 }
 
 // launch of the persistent 8-phase kernel (gemm8p.h): one instantiation per epilogue flavour of the training step, a generic one
-// for anything else
-template <int NT1, int EF>
+// (EF = -1: the flavour is read from the arguments on the device) for anything else
+template <int NT1, int EF, bool FP8 = false, int BM = 256>
 static int g8_go(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
-    if (const int rc = ap_allow_lds<k_gemm_nt_8p<NT1, EF>>(G8_LDS_BYTES); rc != AP_OK) return rc;
-    hipLaunchKernelGGL((k_gemm_nt_8p<NT1, EF>), dim3(grid), dim3(512), G8_LDS_BYTES, st, ga, ep);
+    AP_LAUNCH_LDS((k_gemm_nt_8p<NT1, EF, FP8, BM>), dim3(grid), dim3(512), G8_LDS_BYTES, st, ga, ep);
     return ap_check_launch();
 }
-// the 224-row instantiations (256 x 192 tiles only): the flavours of the N = 384 products of a transformer block -- plain, row scale,
-// bias (+ row scale) + residual; -> false for any other flavour (the caller then launches 256-row tiles)
-template <int EF>
-static int g8_go224(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
-    if (const int rc = ap_allow_lds<k_gemm_nt_8p<1, EF, false, 224>>(G8_LDS_BYTES); rc != AP_OK) return rc;
-    hipLaunchKernelGGL((k_gemm_nt_8p<1, EF, false, 224>), dim3(grid), dim3(512), G8_LDS_BYTES, st, ga, ep);
-    return ap_check_launch();
+// the instantiations of one tile shape: the first EF of the list that equals the flavour, or is the generic -1, takes the launch -- so -1
+// stands last in a list; a list without it (the 224-row tiles) refuses any other flavour
+template <int NT1, bool FP8, int BM, int... EF>
+static int g8_pick(int flavour, const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
+    int rc = AP_ERR_UNSUPPORTED;
+    (void)(... || ((EF < 0 || EF == flavour) && ((rc = g8_go<NT1, EF, FP8, BM>(ga, ep, grid, st)), true)));
+    return rc;
 }
-static bool g8_has224(const EpiArgs& ep) {
-    const int f = g8_flavour(ep);
-    return f == 0 || f == G8_RS || f == (G8_BIAS | G8_RES) || f == (G8_BIAS | G8_RS | G8_RES);
-}
-static int g8_pick224(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
-    switch (g8_flavour(ep)) {
-        case 0: return g8_go224<0>(ga, ep, grid, st);
-        case G8_RS: return g8_go224<G8_RS>(ga, ep, grid, st);
-        case G8_BIAS | G8_RES: return g8_go224<G8_BIAS | G8_RES>(ga, ep, grid, st);
-        default: return g8_go224<G8_BIAS | G8_RS | G8_RES>(ga, ep, grid, st);
-    }
-}
-template <int NT1>
-static int g8_pick(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
-    switch (g8_flavour(ep)) {
-        case 0: return g8_go<NT1, 0>(ga, ep, grid, st);
-        case G8_BIAS: return g8_go<NT1, G8_BIAS>(ga, ep, grid, st);
-        case G8_RS: return g8_go<NT1, G8_RS>(ga, ep, grid, st);
-        case G8_BIAS | G8_GELU: return g8_go<NT1, G8_BIAS | G8_GELU>(ga, ep, grid, st);
-        case G8_BIAS | G8_GELU | G8_RS: return g8_go<NT1, G8_BIAS | G8_GELU | G8_RS>(ga, ep, grid, st);
-        case G8_BIAS | G8_GELU | G8_GTAB: return g8_go<NT1, G8_BIAS | G8_GELU | G8_GTAB>(ga, ep, grid, st);
-        case G8_BIAS | G8_GELU | G8_RS | G8_GTAB: return g8_go<NT1, G8_BIAS | G8_GELU | G8_RS | G8_GTAB>(ga, ep, grid, st);
-        case G8_BIAS | G8_GELU | G8_GTAB | G8_NOSIDE: return g8_go<NT1, G8_BIAS | G8_GELU | G8_GTAB | G8_NOSIDE>(ga, ep, grid, st);
-        case G8_BIAS | G8_GELU | G8_RS | G8_GTAB | G8_NOSIDE: return g8_go<NT1, G8_BIAS | G8_GELU | G8_RS | G8_GTAB | G8_NOSIDE>(ga, ep, grid, st);
-        case G8_DGELU: return g8_go<NT1, G8_DGELU>(ga, ep, grid, st);
-        case G8_DGELU | G8_RS: return g8_go<NT1, G8_DGELU | G8_RS>(ga, ep, grid, st);
-        case G8_MUL: return g8_go<NT1, G8_MUL>(ga, ep, grid, st);
-        case G8_MUL | G8_RS: return g8_go<NT1, G8_MUL | G8_RS>(ga, ep, grid, st);
-        case G8_MUL8: return g8_go<NT1, G8_MUL8>(ga, ep, grid, st);
-        case G8_MUL8 | G8_RS: return g8_go<NT1, G8_MUL8 | G8_RS>(ga, ep, grid, st);
-        case G8_MUL8 | G8_Q8: return g8_go<NT1, G8_MUL8 | G8_Q8>(ga, ep, grid, st);
-        case G8_MUL8 | G8_RS | G8_Q8: return g8_go<NT1, G8_MUL8 | G8_RS | G8_Q8>(ga, ep, grid, st);
-        case G8_BIAS | G8_RES: return g8_go<NT1, G8_BIAS | G8_RES>(ga, ep, grid, st);
-        case G8_BIAS | G8_RS | G8_RES: return g8_go<NT1, G8_BIAS | G8_RS | G8_RES>(ga, ep, grid, st);
-        default: return g8_go<NT1, -1>(ga, ep, grid, st);
-    }
-}
-// the fp8 instantiations (ap_gemm_nt_fp8: the forward Linear layers of the configs[4] step): the flavours a transformer block's forward uses
-template <int NT1, int EF>
-static int g8_go_fp8(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
-    if (const int rc = ap_allow_lds<k_gemm_nt_8p<NT1, EF, true>>(G8_LDS_BYTES); rc != AP_OK) return rc;
-    hipLaunchKernelGGL((k_gemm_nt_8p<NT1, EF, true>), dim3(grid), dim3(512), G8_LDS_BYTES, st, ga, ep);
-    return ap_check_launch();
-}
-template <int NT1>
-static int g8_pick_fp8(const G8Args& ga, const EpiArgs& ep, int grid, hipStream_t st) {
-    switch (g8_flavour(ep)) {
-        case 0: return g8_go_fp8<NT1, 0>(ga, ep, grid, st);
-        case G8_BIAS: return g8_go_fp8<NT1, G8_BIAS>(ga, ep, grid, st);
-        case G8_BIAS | G8_GELU: return g8_go_fp8<NT1, G8_BIAS | G8_GELU>(ga, ep, grid, st);
-        case G8_BIAS | G8_GELU | G8_RS: return g8_go_fp8<NT1, G8_BIAS | G8_GELU | G8_RS>(ga, ep, grid, st);
-        case G8_BIAS | G8_GELU | G8_GTAB: return g8_go_fp8<NT1, G8_BIAS | G8_GELU | G8_GTAB>(ga, ep, grid, st);
-        case G8_BIAS | G8_GELU | G8_RS | G8_GTAB: return g8_go_fp8<NT1, G8_BIAS | G8_GELU | G8_RS | G8_GTAB>(ga, ep, grid, st);
-        case G8_BIAS | G8_RES: return g8_go_fp8<NT1, G8_BIAS | G8_RES>(ga, ep, grid, st);
-        case G8_BIAS | G8_RS | G8_RES: return g8_go_fp8<NT1, G8_BIAS | G8_RS | G8_RES>(ga, ep, grid, st);
-        default: return g8_go_fp8<NT1, -1>(ga, ep, grid, st);
-    }
-}
-static int g8_launch(int bn, const bf16_t* A, int lda, const bf16_t* B, int ldb, bf16_t* C, int ldc, int M, int N, int K, const EpiArgs& ep, hipStream_t st, bool fp8 = false) {
-    const int n_cu = ap_cu_count();
-    G8Args ga;
-    ga.A = A; ga.lda = lda; ga.B = B; ga.ldb = ldb; ga.C = C; ga.ldc = ldc; ga.M = M; ga.N = N; ga.K = K;
-    ga.tiles_n = (N + bn - 1) / bn; ga.ntiles = ((M + 255) / 256) * ga.tiles_n;
-    const int cap = n_cu & ~7;
-    // 224-row tiles where they put more CUs to work inside ONE round of the persistent grid (a launch of fewer tiles than CUs takes
-    // about one tile's time whatever the number of idle CUs: tools/tile_rounds_probe.py): VOLO-D1's N = 384 products at 25088 rows,
-    // 98 x 2 = 196 tiles of 256 rows -> 112 x 2 = 224 tiles of 224.  AP_GEMM_BM224=0: 256-row tiles everywhere.
-    static int bm224 = -1;
-    if (bm224 < 0) { const char* e = getenv("AP_GEMM_BM224"); bm224 = e ? atoi(e) : 1; }
-    if (bm224 && !fp8 && bn == 192 && g8_has224(ep)) {
-        const int t224 = ((M + 223) / 224) * ga.tiles_n;
-        if (ga.ntiles < cap && t224 <= cap && t224 > ga.ntiles) {
-            ga.ntiles = t224;
-            const int want4 = (t224 + 7) & ~7;
-            return g8_pick224(ga, ep, want4 < cap ? want4 : cap, st);
-        }
-    }
-    const int want = (ga.ntiles + 7) & ~7;        // a multiple of 8: the kernel deals tiles per XCD label
-    const int grid = want < cap ? want : cap;
-    if (fp8) return bn == 192 ? g8_pick_fp8<1>(ga, ep, grid, st) : g8_pick_fp8<2>(ga, ep, grid, st);
-    return bn == 192 ? g8_pick<1>(ga, ep, grid, st) : g8_pick<2>(ga, ep, grid, st);
-}
+// bf16, 256-row tiles: the flavours of the training step and of the forward-only passes ...
+#define G8_FLAVOURS_BF16 0, G8_BIAS, G8_RS, G8_BIAS | G8_GELU, G8_BIAS | G8_GELU | G8_RS, G8_BIAS | G8_GELU | G8_GTAB, G8_BIAS | G8_GELU | G8_RS | G8_GTAB, \
+    G8_BIAS | G8_GELU | G8_GTAB | G8_NOSIDE, G8_BIAS | G8_GELU | G8_RS | G8_GTAB | G8_NOSIDE, G8_DGELU, G8_DGELU | G8_RS, G8_MUL, G8_MUL | G8_RS, G8_MUL8, \
+    G8_MUL8 | G8_RS, G8_MUL8 | G8_Q8, G8_MUL8 | G8_RS | G8_Q8, G8_BIAS | G8_RES, G8_BIAS | G8_RS | G8_RES, -1
+// ... fp8 (ap_gemm_nt_fp8: the forward Linear layers of the configs[4] step): the flavours a transformer block's forward uses; the 224-row
+// list is G8_FLAVOURS_224 (gemm_nt_const.h): nt_plan.h plans such tiles for those flavours only (no generic instantiation)
+#define G8_FLAVOURS_FP8 0, G8_BIAS, G8_BIAS | G8_GELU, G8_BIAS | G8_GELU | G8_RS, G8_BIAS | G8_GELU | G8_GTAB, G8_BIAS | G8_GELU | G8_RS | G8_GTAB, G8_BIAS | G8_RES, \
+    G8_BIAS | G8_RS | G8_RES, -1
 
-// Where the persistent 8-phase kernel is picked (measured INSIDE the training step, tools/instep_8p.sh; profiles/r03_gemm_instep_*):
-// every launch with K % 64 == 0, M >= 4096 and N a multiple of 192 (256 x 192 tiles) or N >= 1024 (256 x 256 tiles, last column tile
-// masked) -- 384 x 1152 plain 38.3 -> 30.7 us, + residual 45.3 -> 41.0, fc1 + GELU 61.5 -> 56.0, qkv 39.0 -> 35.0, the K = 192
-// outlooker shapes 5 - 15 % -- except the gelu' epilogue, whose staged second operand still costs more than it saves (60.6 -> 62.3).
-// AP_GEMM_8P = 0: never; 1 (default): as above; 2: the gelu' launches too.
-static int use_8p(int M, int N, int K, int ldc, const EpiArgs& ep) {          // -> 0 (no), 192 or 256 (block tile width)
-    static int mode = -1;
-    if (mode < 0) { const char* e = getenv("AP_GEMM_8P"); mode = e ? atoi(e) : 1; }
-    if (mode == 0 || (K & 63) || K < 128 || M < 4096 || (N & 7) || (ldc & 7) || (ep.residual && (ep.ldr & 7))) return 0;
-    if (ep.dgelu_of && (mode < 2 || ep.residual)) return 0;
-    if ((ep.mul_by || ep.mul8) && ep.residual) return 0;
-    int bn = N >= 1024 ? 256 : (N % 192 == 0 ? 192 : (N % 256 == 0 ? 256 : 0));
-    if (N >= 384 && N % 192 == 0) {
-        // both widths tile N: the persistent grid walks ceil(tiles / #CU) rounds of tiles, a 256-wide tile costs ~1.3 of a 192-wide one.
-        // N = 1152 (4.5 -> 5 column tiles of 256): 25088 rows 2 x 1.3 against 3 rounds -> 256; the AutoProg stages' 8192 / 18432 rows
-        // (128 / 192 px) one round against one, two against two -> 192 (12.2 against 13.8 us, 21.3 against 25.5); 12800 rows (160 px) one
-        // round of 250 tiles against two of 300 -> 256 (16.3 against 21.5): tools/sweep_nt.py, AP_GEMM_NT_TILE = 20 / 21.
-        const int ncu = ap_cu_count();
-        const int64_t mt = (M + 255) / 256;
-        const int64_t r192 = (mt * (N / 192) + ncu - 1) / ncu, r256 = (mt * ((N + 255) / 256) + ncu - 1) / ncu;
-        bn = (r192 * 10 < r256 * 13) ? 192 : 256;
-        // (N = 768, the D5 widths, at 50176 rows = batch 64: 784 tiles of 192 are 3.06 -> FOUR rounds, 588 of 256 three: 64.2 against 67.1 us
-        // at K = 768, 231 against 241 - 257 at K = 3072; at 48608 rows three rounds of 192: 54.0 against 63.1.  N = 384 / 576 stay on 192.)
+// ---- NT products: which kernel is launched, with which tile and grid, and what is refused is planned by nt_plan.h; here its plans become
+// kernel arguments.  The run-time switches (read once per process), the device's CU count and the GELU table are handed to the planner.
+static const NtSwitches& nt_switches() { static const NtSwitches s = nt_switches_from(getenv); return s; }
+static NtEpi nt_facts(const EpiArgs& ep) {
+    return NtEpi{ep.bias != nullptr, ep.preact != nullptr, ep.dgelu_of != nullptr, ep.mul_by != nullptr, ep.mul8 != nullptr, ep.row_scale != nullptr,
+                 ep.residual != nullptr, ep.q8 != nullptr, ep.q8_scale != nullptr, ep.ldr, ep.gelu, ep.noside};
+}
+template <int EPI>
+static int ws_go(const WsArgs& a, const EpiArgs& ep, int grid, hipStream_t st) {
+    AP_LAUNCH_LDS(k_gemm_nt_ws<EPI>, dim3(grid), dim3(512), WS_LDS_BYTES(EPI), st, a, ep);
+    return ap_check_launch();
+}
+template <int BM_, int BN_, int WM_, int WN_>
+static void nt_tile_go(const NtPlan& p, const bf16_t* A, int lda, const bf16_t* B, int ldb, bf16_t* C, int ldc, int M, int N, int K, const EpiArgs& ep, hipStream_t st) {
+    if (p.lds_epi) hipLaunchKernelGGL((k_gemm_nt<BM_, BN_, WM_, WN_, false>), dim3(p.grid), dim3(WM_ * WN_ * 64), 0, st, A, lda, B, ldb, C, ldc, M, N, K, p.tiles_n, p.ntiles, ep);
+    else hipLaunchKernelGGL((k_gemm_nt<BM_, BN_, WM_, WN_, true>), dim3(p.grid), dim3(WM_ * WN_ * 64), 0, st, A, lda, B, ldb, C, ldc, M, N, K, p.tiles_n, p.ntiles, ep);
+}
+// plan and launch.  K, lda, ldb as the entry point took them: the kernels of an fp8 launch count them in byte PAIRS (their element is 2 bytes)
+static int nt_launch(const bf16_t* A, int lda, const bf16_t* B, int ldb, bf16_t* C, int ldc, int M, int N, int K, EpiArgs& ep, bool fp8, hipStream_t st) {
+    const unsigned* tab = nullptr;
+    const NtPlan p = nt_plan(M, N, K, lda, ldb, ldc, nt_facts(ep), fp8, ap_cu_count(), nt_switches(), [&] { return (tab = g8_gelu_table_ptr(st)) != nullptr; });
+    if (p.status != AP_OK) return p.status;
+    (void)hipGetLastError();
+    if (p.tab) ep.gelu_tab = tab;
+    if (fp8) { lda /= 2; ldb /= 2; K /= 2; }
+    switch (p.family) {
+        case NT_SKINNY:
+            AP_LAUNCH_LDS(k_gemm_nt_skinny, dim3(p.grid, p.grid_y), dim3(512), p.lds_bytes, st, A, lda, B, ldb, C, ldc, M, N, K, ep);
+            break;
+        case NT_8P: {
+            const G8Args ga = {A, lda, B, ldb, C, ldc, M, N, K, p.tiles_n, p.ntiles};
+            if (g8_flavour(ep) != p.flavour) return AP_ERR_LAUNCH;         // (the instantiation is picked by the plan's flavour, the generic kernel reads g8_flavour)
+            if (p.bm == 224) return g8_pick<1, false, 224, G8_FLAVOURS_224>(p.flavour, ga, ep, p.grid, st);
+            if (fp8) return p.bn == 192 ? g8_pick<1, true, 256, G8_FLAVOURS_FP8>(p.flavour, ga, ep, p.grid, st) : g8_pick<2, true, 256, G8_FLAVOURS_FP8>(p.flavour, ga, ep, p.grid, st);
+            return p.bn == 192 ? g8_pick<1, false, 256, G8_FLAVOURS_BF16>(p.flavour, ga, ep, p.grid, st) : g8_pick<2, false, 256, G8_FLAVOURS_BF16>(p.flavour, ga, ep, p.grid, st);
+        }
+        case NT_WS: {
+            const WsArgs a = {A, lda, B, ldb, C, ldc, M, N, p.n_slices, p.n_items, p.per_xcd};
+            return p.ws_epi == 0 ? ws_go<0>(a, ep, p.grid, st) : p.ws_epi == 2 ? ws_go<2>(a, ep, p.grid, st) : ws_go<1>(a, ep, p.grid, st);
+        }
+        case NT_TILE:
+#define NT_CASE(V, ...) case V: nt_tile_go<__VA_ARGS__>(p, A, lda, B, ldb, C, ldc, M, N, K, ep, st); break;
+            switch (p.variant) {
+                NT_TILE_SHAPES(NT_CASE)
+                default:
+                    if (p.prefetch) hipLaunchKernelGGL((k_gemm_nt<128, 128, 2, 2, false, 1, true>), dim3(p.grid), dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, p.tiles_n, p.ntiles, ep);
+                    else nt_tile_go<128, 128, 2, 2>(p, A, lda, B, ldb, C, ldc, M, N, K, ep, st);
+            }
+#undef NT_CASE
+            break;
+        default:                // NT_FP8_TILE
+            hipLaunchKernelGGL((k_gemm_nt<128, 128, 2, 2, false, 1, false, 0, true>), dim3(p.grid), dim3(256), 0, st, A, lda, B, ldb, C, ldc, M, N, K, p.tiles_n, p.ntiles, ep);
+            break;
     }
-    return N < 192 ? 0 : bn;
+    return ap_check_launch();
 }
 
 extern "C" {
-
-// -> 1: not a launch of the weight-stationary kernel (the caller goes on); otherwise the launch's status.  AP_GEMM_WS=0: never
-static int ws_try(const bf16_t* A, int lda, const bf16_t* B, int ldb, bf16_t* C, int ldc, int M, int N, int K, EpiArgs& ep, hipStream_t st) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("AP_GEMM_WS"); on = (e && e[0] == '0') ? 0 : 1; }
-    if (!on || K != WS_K || N % WS_BN || M % WS_BM || M < 16384 || (ldc & 15) || (lda & 7) || (ldb & 7)) return 1;
-    if (ep.dgelu_of || ep.mul_by || ep.row_scale || ep.residual || ep.q8) return 1;
-    int epi = -1;
-    if (ep.gelu == 3 && (ep.preact || ep.noside) && !ep.mul8) {
-        ep.gelu_tab = g8_gelu_table_ptr(st);
-        if (ep.gelu_tab) epi = ep.noside ? 2 : 0;
-    } else if (!ep.gelu && ep.mul8 && !ep.bias) epi = 1;
-    if (epi < 0) return 1;
-    WsArgs a;
-    a.A = A; a.lda = lda; a.W = B; a.ldb = ldb; a.C = C; a.ldc = ldc; a.M = M; a.N = N;
-    a.n_slices = N / WS_BN; a.n_items = M / WS_BM;
-    const int ncu = ap_cu_count();
-    if (a.n_slices > ncu / 8) return 1;
-    a.per_xcd = (ncu / 8) / a.n_slices;                           // tile streams per XCD: 10 for three slices on 32 CUs (two CUs per XCD stay idle)
-    const int grid = ncu & ~7;
-    const int rc = epi == 0 ? ap_allow_lds<k_gemm_nt_ws<0>>(WS_LDS_BYTES(0)) : epi == 2 ? ap_allow_lds<k_gemm_nt_ws<2>>(WS_LDS_BYTES(2)) : ap_allow_lds<k_gemm_nt_ws<1>>(WS_LDS_BYTES(1));
-    if (rc != AP_OK) return rc;
-    if (epi == 0) hipLaunchKernelGGL(k_gemm_nt_ws<0>, dim3(grid), dim3(512), WS_LDS_BYTES(0), st, a, ep);
-    else if (epi == 2) hipLaunchKernelGGL(k_gemm_nt_ws<2>, dim3(grid), dim3(512), WS_LDS_BYTES(2), st, a, ep);
-    else hipLaunchKernelGGL(k_gemm_nt_ws<1>, dim3(grid), dim3(512), WS_LDS_BYTES(1), st, a, ep);
-    return ap_check_launch();
-}
 
 // the epilogue of a launch without ap_gemm_epilogue: everything off, one row per DropPath scale
 static EpiArgs epi_none() {
@@ -977,162 +905,44 @@ static EpiArgs epi_none() {
     ep.rows_per_scale = 1;
     return ep;
 }
-// the fields of ap_gemm_epilogue that every entry point takes (what else it takes, and what it refuses, is the entry point's)
+// the fields of ap_gemm_epilogue that every entry point takes (what else it takes, and what it refuses, is the entry point's or the planner's)
 static void epi_common(EpiArgs& ep, const ap_gemm_epilogue& epi) {
     ep.bias = epi.bias; ep.gelu = epi.gelu; ep.preact = epi.preact_out; ep.dgelu_of = epi.dgelu_of;
     ep.row_scale = epi.row_scale; ep.rows_per_scale = epi.rows_per_scale > 0 ? epi.rows_per_scale : 1;
     ep.residual = epi.residual; ep.ldr = epi.ldr;
+    ep.q8 = epi.q8_out; ep.q8_scale = epi.q8_scale; ep.q8_amax = epi.q8_amax;
 }
 
 int ap_gemm_nt(const ap_bf16* A, int lda, const ap_bf16* B, int ldb, ap_bf16* C, int ldc, int M, int N, int K,
                const ap_gemm_epilogue* epi, ap_stream_t stream) {
     if (!A || !B || !C) return AP_ERR_NULL;
-    if (M <= 0 || N <= 0 || K <= 0 || M > AP_MAX_ROWS) return AP_ERR_SHAPE;          // (tile counts (M + tile - 1) / tile are formed in int)
-    if ((K & 7) || (lda & 7) || (ldb & 7) || lda < K || ldb < K || ldc < N) return AP_ERR_SHAPE;
     EpiArgs ep = epi_none();
-    { const char* e = getenv("AP_GEMM_DBG"); if (e) ep.dbg = atoi(e); }
+    ep.dbg = nt_switches().dbg;                 // AP_GEMM_DBG (ablation aid of k_gemm_nt)
     if (epi) {
         epi_common(ep, *epi);
         ep.mul_by = epi->mul_by; ep.mul8 = epi->mul_by8;
-        if (ep.residual && ep.ldr < N) return AP_ERR_SHAPE;
-        if ((ep.mul_by != nullptr) + (ep.dgelu_of != nullptr) + (ep.mul8 != nullptr) > 1) return AP_ERR_SHAPE;
         // gelu = 4: the value of mode 3 in `out`, no side store (forward-only launches); preact_out is ignored
         if (ep.gelu == 4) { ep.gelu = 3; ep.noside = 1; ep.preact = nullptr; }
-        else if (ep.gelu < 0 || ep.gelu > 3 || (ep.gelu >= 2 && !ep.preact)) return AP_ERR_SHAPE;
-        if (ep.noside && (ep.mul_by || ep.dgelu_of || ep.mul8 || ep.residual || epi->q8_out || !ep.bias)) return AP_ERR_UNSUPPORTED;
-        // q8_out of a bf16 launch (round 5): the output a second time as e4m3 bytes, for the fp8 input-gradient product that consumes it.
-        // Exists in the 8-phase kernel's mul_by8 flavours only (the input gradient of fc2): anything else is refused, not silently skipped
-        if (epi->q8_out) {
-            ep.q8 = epi->q8_out; ep.q8_scale = epi->q8_scale; ep.q8_amax = epi->q8_amax;
-            if (!ep.q8_scale || !ep.mul8 || ep.bias || ep.gelu || ep.residual || (ldc & 15)) return AP_ERR_UNSUPPORTED;
-            if (!use_8p(M, N, K, ldc, ep)) return AP_ERR_UNSUPPORTED;
-        }
     }
-    (void)hipGetLastError();
-    static int skinny = -1;
-    if (skinny < 0) { const char* e = getenv("AP_GEMM_NT_NO_SKINNY"); skinny = (e && e[0] == '1') ? 0 : 1; }
-    if (skinny && M <= 256 && (K & 7) == 0) {          // (K = 1000: the head's input gradient ran on three 128 x 128 workgroups, 31 us, until round 4)
-        const size_t lds = (size_t)8 * 64 * SK_STRIDE * sizeof(float);
-        if (ep.noside) return AP_ERR_UNSUPPORTED;       // (the caller falls back to gelu = 3 with a side buffer)
-        if (const int rc = ap_allow_lds<k_gemm_nt_skinny>((int)lds); rc != AP_OK) return rc;
-        hipLaunchKernelGGL(k_gemm_nt_skinny, dim3((N + 31) / 32, (M + 63) / 64), dim3(512), lds, (hipStream_t)stream, A, lda, B, ldb, C, ldc, M, N, K, ep);
-        return ap_check_launch();
-    }
-    // K = 192 with a GELU-table or a stored-derivative epilogue at many rows (the Outlooker's MLP): the weight-stationary kernel (gemm_ws.h)
-    if (const int rc = ws_try(A, lda, B, ldb, C, ldc, M, N, K, ep, (hipStream_t)stream); rc != 1) return rc;
-    // tile selection (measured on the VOLO-D1 shape list, tools/bench_gemm.py): AP_GEMM_NT_TILE forces a variant
-    static int forced = -1;
-    if (forced < 0) { const char* e = getenv("AP_GEMM_NT_TILE"); forced = e ? atoi(e) : 0; }
-    int variant = forced;
-    if (variant == 0) {
-        // measured on the D1 shape list (tools/bench_gemm.py, AP_GEMM_NT_TILE sweep): narrow/short problems want
-        // small tiles (more workgroups, 4-6 waves/SIMD, no wasted columns at N = 192/486/576), the rest 128x128
-        static int allow192 = -1;
-        if (allow192 < 0) { const char* e = getenv("AP_GEMM_NT_192"); allow192 = (e && e[0] == '1') ? 1 : 0; }
-        // 128x192 tiles (wave tile 64x96: 17 % fewer LDS bytes per FLOP, direct epilogue), AP_GEMM_NT_192=1: faster with
-        // cache-warm operands (33.9 vs 37.2 us on the dfc1 shape when the same buffers are reused back to back) but the training
-        // step, whose operands come from HBM, is 0.3 ms SLOWER with them -> off by default
-        if (allow192 && N % 192 == 0 && N >= 384 && M >= 4096 && !ep.gelu && !ep.dgelu_of && !ep.residual && K >= 384) variant = 10;
-        else if (const int bn8 = use_8p(M, N, K, ldc, ep)) variant = bn8 == 192 ? 20 : 21;   // persistent 8-phase kernel (gemm8p.h)
-        else if (N <= 512 && K <= 256) variant = 4;                              // 64x64
-        else if (N <= 256 || ((N % 128 != 0) && (N % 64 == 0))) variant = 2;     // 128x64
-        else variant = 1;                                                        // 128x128
-    }
-    // epilogue flavour: the LDS-staged one (fully coalesced 16-B rows) wins on 128x128 / 64x64 tiles, the direct one
-    // (64-B row segments, no LDS round trip) on the 128x64 tiles of the N = 576 shapes; AP_GEMM_LDS_EPI=0/1 forces one
-    static int lds_epi_env = -2;
-    if (lds_epi_env == -2) { const char* e = getenv("AP_GEMM_LDS_EPI"); lds_epi_env = e ? (e[0] == '1') : -1; }
-    // tuning aid: AP_GEMM_NT_RULE="N,K,variant[,lds_epi];N,K,variant;..." overrides the choice for exact (N, K) pairs, so that a
-    // candidate can be timed INSIDE the training step (bench.py AP_GEMM_TABLE=1) instead of in a cache-warm microbenchmark
-    int rule_epi = -1;
-    {
-        static int nrules = -1;
-        static int rules[16][4];
-        if (nrules < 0) {
-            nrules = 0;
-            const char* e = getenv("AP_GEMM_NT_RULE");
-            while (e && *e && nrules < 16) {
-                int n_ = 0, k_ = 0, v_ = 0, l_ = -1, used = 0;
-                const int got = sscanf(e, "%d,%d,%d%n", &n_, &k_, &v_, &used);
-                if (got < 3) break;
-                e += used;
-                if (*e == ',') { int u2 = 0; if (sscanf(e, ",%d%n", &l_, &u2) == 1) e += u2; }
-                rules[nrules][0] = n_; rules[nrules][1] = k_; rules[nrules][2] = v_; rules[nrules][3] = l_;
-                ++nrules;
-                if (*e == ';') ++e;
-            }
-        }
-        for (int i = 0; i < nrules; ++i)
-            if (rules[i][0] == N && rules[i][1] == K && forced == 0) { variant = rules[i][2]; rule_epi = rules[i][3]; }
-    }
-    // variants 20 / 21: the persistent 8-phase kernel of gemm8p.h with 256 x 192 / 256 x 256 tiles (whole 8-column chunks only)
-    if ((variant == 20 || variant == 21) && ((K & 63) || (N & 7) || (ldc & 7) || (ep.residual && (ep.ldr & 7)))) variant = 1;
-    // gelu = 4 exists in the table flavours of the 8-phase kernel (and in the weight-stationary kernel above) only: refused AFTER the choice
-    if (ep.noside && ((variant != 20 && variant != 21) || !g8_gelu_table_ptr((hipStream_t)stream))) return AP_ERR_UNSUPPORTED;
-    // q8_out exists in the 8-phase kernel's G8_Q8 flavours only: a forced tile (AP_GEMM_NT_TILE), a rule (AP_GEMM_NT_RULE), AP_GEMM_NT_192 or
-    // the fallback above may have picked a kernel that never writes it -- refused here, AFTER the choice, not silently skipped
-    if (ep.q8 && variant != 20 && variant != 21) return AP_ERR_UNSUPPORTED;
-    if (variant == 20 || variant == 21) {
-        if (ep.gelu == 3) ep.gelu_tab = g8_gelu_table_ptr((hipStream_t)stream);
-        return g8_launch(variant == 20 ? 192 : 256, A, lda, B, ldb, C, ldc, M, N, K, ep, (hipStream_t)stream);
-    }
-    const int lds_epi = rule_epi >= 0 ? rule_epi : (lds_epi_env >= 0 ? lds_epi_env : (variant != 2 && variant != 10));
-#define NT_LAUNCH(TMv, TNv, WMv, WNv)                                                                        \
-    {                                                                                                          \
-        const int tm_ = (M + TMv - 1) / TMv, tn_ = (N + TNv - 1) / TNv, nt_ = tm_ * tn_;                       \
-        if (lds_epi) hipLaunchKernelGGL((k_gemm_nt<TMv, TNv, WMv, WNv, false>), dim3(nt_), dim3(WMv * WNv * 64), 0, (hipStream_t)stream, A, lda, B, ldb, C, ldc, M, N, K, tn_, nt_, ep); \
-        else hipLaunchKernelGGL((k_gemm_nt<TMv, TNv, WMv, WNv, true>), dim3(nt_), dim3(WMv * WNv * 64), 0, (hipStream_t)stream, A, lda, B, ldb, C, ldc, M, N, K, tn_, nt_, ep); \
-    }
-    switch (variant) {
-        case 2: NT_LAUNCH(128, 64, 2, 2) break;
-        case 3: NT_LAUNCH(64, 128, 2, 2) break;
-        case 4: NT_LAUNCH(64, 64, 2, 2) break;
-        case 5: NT_LAUNCH(256, 128, 4, 2) break;
-        case 6: NT_LAUNCH(128, 128, 2, 4) break;
-        case 7: NT_LAUNCH(256, 128, 2, 2) break;
-        case 8: NT_LAUNCH(128, 256, 2, 2) break;
-        case 9: NT_LAUNCH(256, 256, 2, 4) break;
-        case 10: NT_LAUNCH(128, 192, 2, 2) break;
-        case 11: NT_LAUNCH(64, 192, 2, 2) break;
-        default:
-            if (lds_epi && (ep.residual != nullptr) != (ep.dgelu_of != nullptr || ep.mul_by != nullptr) && !(ep.dbg & 2)) {    // epilogue reads ONE more tile: prefetching instantiation
-                const int tm_ = (M + 127) / 128, tn_ = (N + 127) / 128, nt_ = tm_ * tn_;
-                hipLaunchKernelGGL((k_gemm_nt<128, 128, 2, 2, false, 1, true>), dim3(nt_), dim3(256), 0, (hipStream_t)stream, A, lda, B, ldb, C, ldc, M, N, K, tn_, nt_, ep);
-            } else NT_LAUNCH(128, 128, 2, 2)
-            break;
-    }
-#undef NT_LAUNCH
-    return ap_check_launch();
+    return nt_launch(A, lda, B, ldb, C, ldc, M, N, K, ep, false, (hipStream_t)stream);
 }
 
 int ap_gemm_nt_fp8(const unsigned char* A, int lda, const unsigned char* B, int ldb, ap_bf16* C, int ldc, int M, int N, int K,
                    const float* dq_a, const float* dq_b, const ap_gemm_epilogue* epi, ap_stream_t stream) {
     if (!A || !B || !C || !dq_a || !dq_b) return AP_ERR_NULL;
-    if (M <= 0 || N <= 0 || K <= 0 || M > AP_MAX_ROWS) return AP_ERR_SHAPE;          // (tile counts (M + tile - 1) / tile are formed in int)
-    if ((K & 15) || (lda & 15) || (ldb & 15) || lda < K || ldb < K || ldc < N) return AP_ERR_SHAPE;       // 16-byte chunks of e4m3
     EpiArgs ep = epi_none();
     ep.dq_a = dq_a; ep.dq_b = dq_b;
-    if (epi) {
-        epi_common(ep, *epi);
-        if (ep.residual && ep.ldr < N) return AP_ERR_SHAPE;
-        if (ep.gelu < 0 || ep.gelu > 3 || (ep.gelu >= 2 && !ep.preact)) return AP_ERR_SHAPE;
-        ep.q8 = epi->q8_out; ep.q8_scale = epi->q8_scale; ep.q8_amax = epi->q8_amax;
-        if (ep.q8 && (!ep.q8_scale || !ep.gelu)) return AP_ERR_SHAPE;
-    }
-    (void)hipGetLastError();
-    // byte pairs: the kernels' element is 2 bytes.  The persistent 8-phase kernel where the bf16 launch of these dimensions would take it
-    // (K % 128 == 0 here: whole 128-byte K-tiles), the 128 x 128-tile kernel otherwise
-    if ((K & 127) == 0 && !ep.dgelu_of) {
-        const int bn8 = use_8p(M, N, K / 2, ldc, ep);
-        if (bn8 && ep.gelu == 3) ep.gelu_tab = g8_gelu_table_ptr((hipStream_t)stream);
-        if (bn8) return g8_launch(bn8, reinterpret_cast<const bf16_t*>(A), lda / 2, reinterpret_cast<const bf16_t*>(B), ldb / 2, C, ldc, M, N, K / 2, ep,
-                                  (hipStream_t)stream, true);
-    }
-    if (ep.q8) return AP_ERR_UNSUPPORTED;            // the e4m3 side output exists in the 8-phase kernel's row phase only
-    const int tm = (M + 127) / 128, tn = (N + 127) / 128, nt = tm * tn;
-    hipLaunchKernelGGL((k_gemm_nt<128, 128, 2, 2, false, 1, false, 0, true>), dim3(nt), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const bf16_t*>(A), lda / 2, reinterpret_cast<const bf16_t*>(B), ldb / 2, C, ldc, M, N, K / 2, tn, nt, ep);
-    return ap_check_launch();
+    if (epi) epi_common(ep, *epi);
+    return nt_launch(reinterpret_cast<const bf16_t*>(A), lda, reinterpret_cast<const bf16_t*>(B), ldb, C, ldc, M, N, K, ep, true, (hipStream_t)stream);
+}
+
+// does a launch of these dimensions emit its output a second time as e4m3 (q8_out)?  The plan of the canonical launch under the process's
+// switches -- bf16: mul_by8 + q8 (the input gradient of fc2), fp8: bias + gelu + q8 (fc1's forward); operands with lda = ldb = K
+int ap_gemm_nt_q8_ok(int M, int N, int K, int ldc, int fp8) {
+    NtEpi e = {};
+    e.q8 = e.q8_scale = true;
+    if (fp8) { e.bias = e.preact = true; e.gelu = 1; } else e.mul8 = true;
+    return nt_plan(M, N, K, K, K, ldc, e, fp8 != 0, ap_cu_count(), nt_switches(), [] { return true; }).status == AP_OK;
 }
 
 static bool patch_map_device(const ap_patch_map* map, PatchMap& pm) {

@@ -43,13 +43,12 @@
 #pragma once
 #include "common.h"
 #include "gemm_epi.h"
+#include "gemm_nt_const.h"       // the G8_* flavour bits, G8_LDS_BYTES
 #include <type_traits>
 
 #ifndef G8_NT_STORE
 #define G8_NT_STORE 1          // the epilogue's row stores bypass L2 allocation (nontemporal): the outputs are read by the NEXT kernel, behind an L2 write-back anyway
 #endif
-#define G8_LDS_BYTES 163840                    // all of the CU's LDS: two K-tile buffers + the epilogue staging region
-
 #define G8_GLB(p) ((const __attribute__((address_space(1))) void*)(p))
 #define G8_LDS(p) ((__attribute__((address_space(3))) void*)(p))
 
@@ -78,7 +77,6 @@ struct G8Args {
 // epilogue flavour of an instantiation (EF >= 0: bits known at compile time; EF < 0: read from the arguments at run time).  The
 // generic epilogue is ~25 KB of code that a CU runs once or twice per launch, cold: an instantiation per flavour of the training
 // step keeps what is fetched to what is used (2.8 us -> see DESIGN.md on the 25088 x 384 x 1152 launch).
-enum { G8_BIAS = 1, G8_GELU = 2, G8_DGELU = 4, G8_RS = 8, G8_RES = 16, G8_MUL = 32, G8_MUL8 = 64, G8_GTAB = 128, G8_Q8 = 256, G8_NOSIDE = 512 };
 __host__ __device__ inline int g8_flavour(const EpiArgs& ep) {
     return (ep.bias ? G8_BIAS : 0) | (ep.gelu ? G8_GELU : 0) | (ep.dgelu_of ? G8_DGELU : 0) | (ep.row_scale ? G8_RS : 0) | (ep.residual ? G8_RES : 0) |
            (ep.mul_by ? G8_MUL : 0) | (ep.mul8 ? G8_MUL8 : 0) | ((ep.gelu == 3 && ep.gelu_tab) ? G8_GTAB : 0) |

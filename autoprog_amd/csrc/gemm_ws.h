@@ -33,19 +33,11 @@
 #pragma once
 #include "common.h"
 #include "gemm_epi.h"
+#include "gemm_nt_const.h"       // WS_K, WS_BN, WS_BM and the LDS layout constants
 
 #ifndef WS_ABL
 #define WS_ABL 0          // timing-only ablations (results WRONG): 1 no global stores, 2 no MFMAs, 4 no table lookups, 8 no A loads after the first
 #endif
-#define WS_K 192
-#define WS_BN 192
-#define WS_BM 64
-#define WS_ROWB 384                               // bytes of an LDS row (192 bf16)
-#define WS_LDS_W (WS_BN * WS_ROWB)                // 73728
-#define WS_LDS_A (WS_BM * WS_ROWB)                // 24576: the two groups' 32-row halves
-// EPI 0: bf16 staging + the 16 KB table; EPI 1: fp32 staging (the multiply by the stored derivative happens on the fp32 accumulator value,
-// rounded once -- as in the 8-phase kernel)
-#define WS_LDS_BYTES(EPI) (WS_LDS_A + ((EPI) != 1 ? WS_LDS_A + 16384 : 2 * WS_LDS_A))
 
 __device__ __forceinline__ int ws_key(int r) { return ((r >> 1) & 1) | (((r >> 2) & 3) << 1); }
 // byte offset of 16-byte chunk c (0 .. 23) of row r

@@ -316,11 +316,21 @@ def mlp_fused(x, wa, wb, backward=False, bias1=None, bias2=None, row_scale_hidde
     return out, hid, codes
 
 
+_q8_ok = {}         # (M, N, K, ldc, fp8) -> ap_gemm_nt_q8_ok (a pure function of the shape in one process: one foreign call per shape, not per launch)
+
+
+def _gemm_nt_q8_ok(M, N, K, fp8):
+    key = (M, N, K, round_up(N, 8), fp8)            # (the ldc of gemm_nt / gemm_nt_fp8 when they allocate `out`)
+    ok = _q8_ok.get(key)
+    if ok is None:
+        ok = _q8_ok[key] = bool(lib.ap_gemm_nt_q8_ok(*key))
+    return ok
+
+
 def gemm_nt_emits_q8(M, N, K, mul_by):
     """can a bf16 gemm_nt launch of these dimensions write its output a second time as e4m3 (q8=)?  The mul_by8 flavours of the 8-phase
-    kernel (the input gradient of fc2): see ap_gemm_nt / use_8p() in csrc/gemm.hip"""
-    return (mul_by is not None and mul_by.dtype == torch.uint8 and K % 64 == 0 and K >= 128 and M >= 4096 and N % 16 == 0
-            and (N >= 1024 or N % 192 == 0 or N % 256 == 0) and os.environ.get("AP_GEMM_8P", "1") != "0")
+    kernel (the input gradient of fc2): the library's own launch plan answers (csrc/nt_plan.h)"""
+    return mul_by is not None and mul_by.dtype == torch.uint8 and _gemm_nt_q8_ok(M, N, K, 0)
 
 
 def gemm_nt(a, b, n=None, k=None, bias=None, gelu=False, preact_out=None, dgelu_of=None, row_scale=None,
@@ -496,8 +506,8 @@ def quantize_fp8_now(x):
 
 
 def gemm_nt_fp8_emits(M, N, K):
-    """can this launch also emit its GELU output as e4m3 (q8)?  -- the 8-phase kernel's launches: see use_8p() in csrc/gemm.hip"""
-    return K % 128 == 0 and K >= 256 and M >= 4096 and N % 8 == 0 and N >= 192 and (N >= 1024 or N % 192 == 0 or (N % 256 == 0 and N >= 192)) and os.environ.get("AP_GEMM_8P", "1") != "0"
+    """can this launch also emit its GELU output as e4m3 (q8)?  -- the 8-phase kernel's launches: the library's own launch plan answers"""
+    return _gemm_nt_q8_ok(M, N, K, 1)
 
 
 def gemm_nt_fp8(a8, b8, dq_a, dq_b, n=None, bias=None, gelu=False, preact_out=None, residual=None, row_scale=None, rows_per_scale=1,

@@ -158,6 +158,10 @@ typedef struct ap_gemm_epilogue {
 } ap_gemm_epilogue;
 int ap_gemm_nt(const ap_bf16* A, int lda, const ap_bf16* B, int ldb, ap_bf16* C, int ldc,
                int M, int N, int K, const ap_gemm_epilogue* epi, ap_stream_t stream);
+/* Would a launch of these dimensions emit q8_out?  1 / 0: the launch plan (csrc/nt_plan.h) of the canonical q8 launch under the process's
+ * switches on the current device -- fp8 = 0: ap_gemm_nt with mul_by8 + q8_out, fp8 = 1: ap_gemm_nt_fp8 (K in bytes) with bias + gelu + q8_out;
+ * lda = ldb = K.  Nothing is launched.  (An added symbol: the ABI version stays 7.) */
+int ap_gemm_nt_q8_ok(int M, int N, int K, int ldc, int fp8);
 /* ---- (ABI version 7) the MLP of a block in ONE launch: Mlp.forward, models/volo.py:147-167 (fc1 -> GELU -> fc2) with the residual add and
  * DropPath scale of its call sites (:143 Outlooker, :233 Transformer), and -- the same kernel, backward = 1 -- the two input-gradient products
  * of its backward pass.  The hidden activation never makes the trip to memory and back between the two products; it still LEAVES (the weight

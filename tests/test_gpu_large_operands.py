@@ -477,7 +477,7 @@ def test_wide_chain_autograd_pass(lib, rec):
 
 # ======================================================================================================================== B. ap_gemm_nt
 def mirror_use_8p(M, N, K, ncu):
-    """csrc/gemm.hip use_8p for a launch without dgelu_of / a residual beside mul_by -> 0, 192 or 256 (the block tile width)"""
+    """csrc/nt_plan.h nt_use_8p for a launch without dgelu_of / a residual beside mul_by -> 0, 192 or 256 (the block tile width)"""
     if (K & 63) or K < 128 or M < 4096 or (N & 7):
         return 0
     bn = 256 if N >= 1024 else (192 if N % 192 == 0 else (256 if N % 256 == 0 else 0))
@@ -490,7 +490,7 @@ def mirror_use_8p(M, N, K, ncu):
 
 def same_path_rows_8p(M, N, K, period):
     """the smallest whole number of periods at which the dispatch picks the tile width it picks for M rows and fills the persistent grid
-    (fewer tiles than CUs may take the 224-row instantiation, csrc/gemm.hip g8_launch) -> (rows, tile width)"""
+    (fewer tiles than CUs may take the 224-row instantiation, csrc/nt_plan.h nt_plan) -> (rows, tile width)"""
     ncu = torch.cuda.get_device_properties(0).multi_processor_count
     bn = mirror_use_8p(M, N, K, ncu)
     assert bn, "not a launch of the 8-phase kernel"

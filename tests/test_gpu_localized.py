@@ -11,7 +11,7 @@ tests/test_gpu_kernels.py holds each kernel to a whole-tensor rel-L2; here every
 The two outputs must be bit-identical (the weight gradients' fp32 atomics: within TOL_F32), every tile within its bound, every element
 finite and every guard element unchanged.  The GEMM and attention cases run the guarded launch once more behind ops.poison_lds: a kernel
 that pads its tile from LDS it never wrote is the same class of bug.  Shapes are the smallest at which ap_gemm_nt's dispatch
-(csrc/gemm.hip: use_8p, g8_launch, ws_try, the variant choice in ap_gemm_nt) still selects the path named in the case id with a ragged edge.
+(csrc/nt_plan.h: nt_use_8p, the 224-row rule, the weight-stationary rule and the variant choice of nt_plan) still selects the path named in the case id with a ragged edge.
 
 Every pointer handed to a kernel lies inside an allocation of the test: an out-of-bounds store lands in memory the test owns and inspects.
 Each comparison prints one `TILED` line (whole rel, worst tile and its origin, bit identity): profiles/tiled_parity.txt is that output.
@@ -197,15 +197,15 @@ GEMM_CASES = [
     ("128x64-direct-epilogue", 257, 576, 264, _ALL, 8),               # N % 128 != 0, N % 64 == 0
     ("128x128", 257, 392, 264, _ALL + ("mulby",), 8),                 # bias_res_rs / mulby: the prefetching instantiation (residual xor mul_by)
     ("128x128-ragged-N", 257, 390, 264, _ALL + ("mulby",), 8),        # the prefetched 16-byte chunk of residual / mul_by straddles column N
-    ("8p-192-224rows", 4097, 192, 128, ("plain", "bias_res_rs"), 8),  # 19 tiles of 224 rows > 17 of 256: g8_launch takes the 224-row instantiation
-    ("8p-192-256rows", 4097, 192, 128, ("gelu8",), 8),                # (no 224-row instantiation of this flavour: g8_has224)
+    ("8p-192-224rows", 4097, 192, 128, ("plain", "bias_res_rs"), 8),  # 19 tiles of 224 rows > 17 of 256: nt_plan takes the 224-row instantiation
+    ("8p-192-256rows", 4097, 192, 128, ("gelu8",), 8),                # (no 224-row instantiation of this flavour: nt_has224)
     ("8p-192-224rows", 4100, 384, 1152, ("plain", "bias_res_rs"), 8),
     ("8p-192-256rows", 4100, 384, 1152, ("gelu8",), 8),
     ("8p-256-masked-last-column-tile", 4097, 1032, 128, _ALL, 8),     # N >= 1024: 256-wide tiles, the fifth holds 8 columns
     ("8p-256-second-tile-per-workgroup", 8193, 2056, 128, ("plain", "bias_res_rs"), 8),   # 33 x 9 = 297 tiles on at most 256 workgroups
     # 256-row x 192 tiles by default: fewer than #CU tiles of 256 rows but MORE than #CU of 224 (2 * 129 = 258 > 256 >= 2 * 113): the smallest such M at N = 384
     ("8p-192-256rows-224-does-not-fit", 28673, 384, 128, ("plain",), 8),
-    # K = 192, M >= 16384, M % 64 == 0, N % 192 == 0: ldc % 16 == 0 keeps ws_try's choice (ldc = N + 16)
+    # K = 192, M >= 16384, M % 64 == 0, N % 192 == 0: ldc % 16 == 0 keeps nt_plan's choice of the weight-stationary kernel (ldc = N + 16)
     ("weight-stationary-ldc16", 16384 + 64, 576, 192, ("gelu8", "mul8"), 16),
 ]
 GEMM_PARAMS = [pytest.param(p, M, N, K, f, e, id="%s-%dx%dx%d-%s" % (p, M, N, K, f)) for (p, M, N, K, fl, e) in GEMM_CASES for f in fl]
