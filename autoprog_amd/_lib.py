@@ -165,6 +165,7 @@ _SIGNATURES["ap_bn_relu_bwd_act"] = (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P
 _SIGNATURES["ap_bn_relu_bwd_partials"] = (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _L, _I, _P, ctypes.c_size_t, _P])
 _SIGNATURES["ap_mhsa_fwd_fp8"] = (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P])
 _SIGNATURES["ap_gemm_nt_fp8"] = (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P, POINTER(GemmEpilogue), _P])
+_SIGNATURES["ap_mhsa_fwd_emits_fp8"] = (_I, [_I, _I])                  # (N, hd): csrc/attn_plan.h's plan of the ap_mhsa_fwd_fp8 launch
 _SIGNATURES["ap_gemm_nt_q8_ok"] = (_I, [_I, _I, _I, _I, _I])          # (M, N, K, ldc, fp8): csrc/nt_plan.h's plan of the canonical q8 launch
 _SIGNATURES["ap_gemm_nt_patch"] = (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P, POINTER(PatchMap), _I, _P])
 _SIGNATURES["ap_gemm_nt_patch_bn"] = (_I, [_P, POINTER(BnInput), _P, _I, _P, _I, _I, _I, _I, _P, POINTER(PatchMap), _I, _P])

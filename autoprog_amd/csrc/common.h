@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/autoprog_hip.h"
+#include "switches.h"
 
 typedef unsigned short bf16_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -103,6 +104,8 @@ static inline int ap_check_launch() {
     return e == hipSuccess ? AP_OK : AP_ERR_LAUNCH;
 }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// the run-time switches (switches.h), read from the environment once per process, on first use
+inline const ApSwitches& ap_switches() { static const ApSwitches s = ap_switches_from(getenv); return s; }
 
 // ---- what a launcher has to know about the CURRENT device, asked once per device (a process may drive several) and never per process
 #define AP_MAXDEV 64

@@ -17,7 +17,6 @@
 // 70 us at 6 TB/s: the kernel is bound by neither until the MFMA issue rate of 4 waves per CU is reached.
 #include "common.h"
 #include "gemm_epi.h"
-#include <cstdlib>
 #include <type_traits>
 
 #ifndef AP_EXPERIMENTS
@@ -670,11 +669,7 @@ int ap_conv3x3_c64_pack(const float* w_oihw, ap_bf16* w_fwd, ap_bf16* w_bwd, ap_
     return ap_check_launch();
 }
 
-static int cv_grid(int ntiles) {
-    static int grid_cap = 0;
-    if (grid_cap == 0) { const char* e = getenv("AP_CONV_GRID"); grid_cap = e ? atoi(e) : 256; if (grid_cap < 1) grid_cap = 256; }
-    return ntiles < grid_cap ? ntiles : grid_cap;
-}
+static int cv_grid(int ntiles) { const int cap = ap_switches().conv_grid; return ntiles < cap ? ntiles : cap; }
 
 int ap_conv3x3_c64_stat_rows(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
@@ -697,9 +692,7 @@ int ap_conv3x3_c64_bn(const ap_bf16* x, const ap_bn_input* bn_in, const ap_bf16*
     const int ntiles = (int)nt64;
     (void)hipGetLastError();
     const int grid = cv_grid(ntiles);
-    static int waves = 0;
-    if (waves == 0) { const char* e = getenv("AP_CONV_WAVES"); waves = (e && atoi(e) == 4) ? 4 : 8; }
-    if (waves == 8) {
+    if (ap_switches().conv_waves == 8) {
         const BnIn bn = bn_in ? BnIn{bn_in->mean, bn_in->rstd, bn_in->gamma, bn_in->beta} : BnIn{nullptr, nullptr, nullptr, nullptr};
         if (bn_in && stats) AP_LAUNCH_LDS((k_conv3x3_c64<true, 0, true, 8>), dim3(grid), dim3(512), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats, bn);
         else if (bn_in) AP_LAUNCH_LDS((k_conv3x3_c64<false, 0, true, 8>), dim3(grid), dim3(512), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats, bn);
@@ -714,11 +707,9 @@ int ap_conv3x3_c64_bn(const ap_bf16* x, const ap_bn_input* bn_in, const ap_bf16*
         return ap_check_launch();
     }
 #if AP_EXPERIMENTS             // ablation instantiations (DESIGN.md "Convolution kernels, by ablation"): make EXTRA=-DAP_EXPERIMENTS=1, AP_CONV_ABL=bits
-    static int abl = -1;
-    if (abl < 0) { const char* e = getenv("AP_CONV_ABL"); abl = e ? atoi(e) : 0; }
 #define CV_ABL_LAUNCH(A) case A: hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_c64<false, A>), hipFuncAttributeMaxDynamicSharedMemorySize, CV_LDS_BYTES); \
         hipLaunchKernelGGL((k_conv3x3_c64<false, A>), dim3(grid), dim3(256), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats); return ap_check_launch();
-    switch (abl) { CV_ABL_LAUNCH(1) CV_ABL_LAUNCH(2) CV_ABL_LAUNCH(3) CV_ABL_LAUNCH(4) CV_ABL_LAUNCH(7) CV_ABL_LAUNCH(8) CV_ABL_LAUNCH(11) default: break; }
+    switch (ap_switches().conv_abl) { CV_ABL_LAUNCH(1) CV_ABL_LAUNCH(2) CV_ABL_LAUNCH(3) CV_ABL_LAUNCH(4) CV_ABL_LAUNCH(7) CV_ABL_LAUNCH(8) CV_ABL_LAUNCH(11) default: break; }
 #endif
     if (stats) AP_LAUNCH_LDS((k_conv3x3_c64<true>), dim3(grid), dim3(256), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats);
     else AP_LAUNCH_LDS((k_conv3x3_c64<false>), dim3(grid), dim3(256), CV_LDS_BYTES, (hipStream_t)stream, x, w_packed, y, H, W, tiles_x, tiles_y, ntiles, stats);
@@ -741,11 +732,7 @@ int ap_conv3x3_c64_bwd_stats(const ap_bf16* dz, const ap_bf16* w_packed_bwd, ap_
     return ap_check_launch();
 }
 
-static int cw_grid(int ntiles) {
-    static int cap = 0;
-    if (cap == 0) { const char* e = getenv("AP_CONV_WGRAD_GRID"); cap = e ? atoi(e) : 512; if (cap < 1) cap = 512; }
-    return ntiles < cap ? ntiles : cap;
-}
+static int cw_grid(int ntiles) { const int cap = ap_switches().conv_wgrad_grid; return ntiles < cap ? ntiles : cap; }
 
 size_t ap_conv3x3_c64_wgrad_workspace(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
@@ -771,19 +758,15 @@ int ap_conv3x3_c64_wgrad_bn(const ap_bf16* x, const ap_bn_input* bn_in, const ap
     (void)hipGetLastError();
     constexpr int PTR = CW_PTR;
     constexpr int P_LDS = (PTR * CW_T + (PTR + 2) * CW_PW) * CV_C * 2;
-    static int use_p = -1;
-    if (use_p < 0) { const char* e = getenv("AP_CONV_WGRAD_P"); use_p = e ? atoi(e) : 1; }
-    if (use_p || bn_in) {       // the prefetching kernel: at most 256 workgroups on CW_PTR x 16 = 16 x 16 tiles (the only one with the BatchNorm input transform)
+    if (ap_switches().conv_wgrad_p || bn_in) {       // the prefetching kernel: at most 256 workgroups on CW_PTR x 16 = 16 x 16 tiles (the only one with the BatchNorm input transform)
         const int tyy = (H + PTR - 1) / PTR;
         const int64_t np = (int64_t)B * tiles_x * tyy;
         ntiles = (int)np;
         const int gp = cw_grid(ntiles < 256 ? ntiles : 256);     // (under AP_CONV_WGRAD_GRID too: the workspace is sized by cw_grid)
         if ((size_t)gp * CV_WELEMS * sizeof(float) > ws_bytes) return AP_ERR_SHAPE;
         grid = gp;
-        static int waves = 0;
-        if (waves == 0) { const char* e = getenv("AP_CONV_WAVES"); waves = (e && atoi(e) == 4) ? 4 : 8; }
         const BnIn bn = bn_in ? BnIn{bn_in->mean, bn_in->rstd, bn_in->gamma, bn_in->beta} : BnIn{nullptr, nullptr, nullptr, nullptr};
-        if (waves == 8) {
+        if (ap_switches().conv_waves == 8) {
             if (bn_in) AP_LAUNCH_LDS((k_conv3x3_c64_wgrad_p<PTR, true, 8>), dim3(grid), dim3(512), P_LDS, (hipStream_t)stream, x, dy, static_cast<float*>(workspace), H, W, tiles_x, tyy, ntiles, bn);
             else AP_LAUNCH_LDS((k_conv3x3_c64_wgrad_p<PTR, false, 8>), dim3(grid), dim3(512), P_LDS, (hipStream_t)stream, x, dy, static_cast<float*>(workspace), H, W, tiles_x, tyy, ntiles, bn);
         } else if (bn_in) {

@@ -20,7 +20,6 @@
 // 2 * 9 * 128 * 128 FLOP per pixel: 947 GFLOP per call at B = 64, 224 x 224 (the D5 stem at 448 px).
 #include "common.h"
 #include "gemm_epi.h"
-#include <cstdlib>
 
 #define C8_C 128
 #define C8_T 16
@@ -220,8 +219,7 @@ k_conv3x3_c128(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp, bf16
 extern "C" {
 
 static int c8_grid(int ntiles) {
-    static int forced = -1;
-    if (forced < 0) { const char* e = getenv("AP_CONV128_GRID"); forced = e ? atoi(e) : 0; }
+    const int forced = ap_switches().conv128_grid;
     const int cap = forced >= 1 ? forced : ap_cu_count();
     return ntiles < cap ? ntiles : cap;
 }

@@ -14,7 +14,6 @@
 // pixel axis is the reduction axis, fragments come from transposed LDS reads; per-workgroup slabs, ordered reduction (no atomics).
 #include "common.h"
 #include "gemm_epi.h"
-#include <cstdlib>
 
 #define S_CO 64
 #define S_CI 16
@@ -310,12 +309,7 @@ k_conv7_wgrad_reduce(const float* __restrict__ slab, int nslab, float* __restric
 
 extern "C" {
 
-static int s7_grid(int ntiles, const char* env, int dflt) {
-    const char* e = getenv(env);
-    int cap = e ? atoi(e) : dflt;
-    if (cap < 1) cap = dflt;
-    return ntiles < cap ? ntiles : cap;
-}
+static int s7_grid(int ntiles, int cap) { return ntiles < cap ? ntiles : cap; }
 static int s7_tiles(int B, int H, int W, int tr, int tw, int* tx, int* ty) {
     *tx = (W + tw - 1) / tw; *ty = (H + tr - 1) / tr;
     const int64_t nt = (int64_t)B * *tx * *ty;
@@ -332,7 +326,7 @@ int ap_conv7_pack(const float* w_oihw, ap_bf16* w_packed, ap_stream_t stream) {
 int ap_conv7_s2d_stat_rows(int B, int H, int W) {
     int tx, ty;
     const int nt = (B > 0 && H > 0 && W > 0) ? s7_tiles(B, H, W, S_TR, S_TW, &tx, &ty) : 0;
-    return nt > 0 ? s7_grid(nt, "AP_CONV7_GRID", 512) : 0;
+    return nt > 0 ? s7_grid(nt, ap_switches().conv7_grid) : 0;
 }
 
 int ap_conv7_s2d(const ap_bf16* xs, const ap_bf16* w_packed, ap_bf16* y, int B, int H, int W, float* stats, ap_stream_t stream) {
@@ -345,7 +339,7 @@ int ap_conv7_s2d_ld(const ap_bf16* xs, const ap_bf16* w_packed, ap_bf16* y, int 
     int tx, ty;
     const int nt = s7_tiles(B, H, W, S_TR, S_TW, &tx, &ty);
     if (nt < 0) return AP_ERR_SHAPE;
-    const int grid = s7_grid(nt, "AP_CONV7_GRID", 512);
+    const int grid = s7_grid(nt, ap_switches().conv7_grid);
     (void)hipGetLastError();
     if (stats) AP_LAUNCH_LDS((k_conv7_s2d<true>), dim3(grid), dim3(256), S_LDS_BYTES, (hipStream_t)stream, xs, w_packed, y, H, W, tx, ty, nt, stats, ldy);
     else AP_LAUNCH_LDS((k_conv7_s2d<false>), dim3(grid), dim3(256), S_LDS_BYTES, (hipStream_t)stream, xs, w_packed, y, H, W, tx, ty, nt, stats, ldy);
@@ -355,7 +349,7 @@ int ap_conv7_s2d_ld(const ap_bf16* xs, const ap_bf16* w_packed, ap_bf16* y, int 
 size_t ap_conv7_s2d_wgrad_workspace(int B, int H, int W) {
     int tx, ty;
     const int nt = (B > 0 && H > 0 && W > 0) ? s7_tiles(B, H, W, SW_T, SW_T, &tx, &ty) : 0;
-    return nt > 0 ? (size_t)s7_grid(nt, "AP_CONV7_WGRAD_GRID", 512) * SW_SLAB * sizeof(float) : 0;
+    return nt > 0 ? (size_t)s7_grid(nt, ap_switches().conv7_wgrad_grid) * SW_SLAB * sizeof(float) : 0;
 }
 
 int ap_conv7_s2d_wgrad(const ap_bf16* xs, const ap_bf16* dz, float* dw_oihw, int B, int H, int W, void* workspace, size_t ws_bytes,
@@ -370,7 +364,7 @@ int ap_conv7_s2d_wgrad_ld(const ap_bf16* xs, const ap_bf16* dz, int lddz, float*
     int tx, ty;
     const int nt = s7_tiles(B, H, W, SW_T, SW_T, &tx, &ty);
     if (nt < 0 || ws_bytes < ap_conv7_s2d_wgrad_workspace(B, H, W)) return AP_ERR_SHAPE;
-    const int grid = s7_grid(nt, "AP_CONV7_WGRAD_GRID", 512);
+    const int grid = s7_grid(nt, ap_switches().conv7_wgrad_grid);
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_conv7_s2d_wgrad, dim3(grid), dim3(256), SW_LDS_BYTES, (hipStream_t)stream, xs, dz, static_cast<float*>(workspace), H, W, tx, ty, nt, lddz);
     int rc = ap_check_launch();

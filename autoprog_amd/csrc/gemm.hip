@@ -803,8 +803,7 @@ const unsigned* g8_gelu_table_ptr(hipStream_t st) {
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return nullptr; }
     std::lock_guard<std::mutex> lock(mu);
     if (state[dev] == 0) {
-        const char* e = getenv("AP_GELU_TABLE");
-        if (e && e[0] == '0') { state[dev] = -1; return nullptr; }
+        if (!ap_switches().gelu_table) { state[dev] = -1; return nullptr; }
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
         if (cs != hipStreamCaptureStatusNone) return nullptr;
@@ -983,10 +982,9 @@ int ap_gemm_nt_patch_bn(const ap_bf16* A, const ap_bn_input* a_bn, const ap_bf16
 
 // ---- weight gradients: what is launched and how it is cut and placed is planned by tn_plan.h; here its plans become kernel arguments.
 // The run-time switches and the device's CU count are read here and handed to the planner.
-static int tn_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-static int tn_8p_enabled() { static const int v = tn_env("AP_GEMM_TN_8P", 1); return v; }
+static int tn_8p_enabled() { return ap_switches().tn_8p; }
 static int tn_capacity() {               // resident workgroups of the 128 x 128-tile kernels, two per CU (AP_GEMM_TN_GROUP_BLOCKS forces a number)
-    static const int forced = tn_env("AP_GEMM_TN_GROUP_BLOCKS", 0);
+    const int forced = ap_switches().tn_group_blocks;
     return forced > 0 ? forced : 2 * ap_cu_count();
 }
 
@@ -995,8 +993,7 @@ int ap_gemm_tn_acc(const ap_bf16* A, int lda, const ap_bf16* B, int ldb, float* 
     if (!A || !B || !C) return AP_ERR_NULL;
     if (M <= 0 || N1 <= 0 || N2 <= 0 || M > AP_MAX_ROWS) return AP_ERR_SHAPE;
     if ((lda & 7) || (ldb & 7) || lda < N1 || ldb < N2 || ldc < N2) return AP_ERR_SHAPE;
-    static const int target_blocks = tn_env("AP_GEMM_TN_BLOCKS", 384);            // measured optimum: atomics vs parallelism
-    const TnItemPlan p = tn_single_plan(M, N1, N2, target_blocks);
+    const TnItemPlan p = tn_single_plan(M, N1, N2, ap_switches().tn_blocks);
     const int blocks = p.t1 * p.t2 * p.splits;
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_gemm_tn, dim3(blocks), dim3(256), 0, (hipStream_t)stream, A, lda, B, ldb, C, ldc, M, N1, N2, p.sps, colsum_A, p.t1, p.t2, blocks);
@@ -1081,10 +1078,9 @@ static int tn_grouped_128(const ap_tn_problem* problems, int count, const ap_ln_
         if (problems[0].b_bn) hipLaunchKernelGGL(k_gemm_tn_patch<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grp.p[0], bbn);
         else hipLaunchKernelGGL(k_gemm_tn_patch<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grp.p[0], bbn);
     } else {
-        static const int place = tn_env("AP_GEMM_TN_PLACE", 1);
         const int cap = 2 * ap_cu_count() / 8;                                                                  // resident workgroups per XCD
         TnMap map; int mblocks = 0;
-        if (place && tn128_place(plan, cap, map, mblocks)) {
+        if (ap_switches().tn_place && tn128_place(plan, cap, map, mblocks)) {
             TnLn ln; int lblocks = 0;
             tn_ln_table(ln_items, ln_count, ln, lblocks);           // (checked by the entry point)
             ln.first = mblocks;

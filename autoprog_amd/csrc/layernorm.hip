@@ -7,7 +7,7 @@
 // Rows are grid-strided so every lane keeps the same channels and accumulates dgamma/dbeta in
 // registers; those are reduced through LDS per block and added with fp32 atomics.
 #include "common.h"
-#include <cstdlib>
+#include "ln_plan.h"
 
 template <int V, int U>
 __global__ void __launch_bounds__(256)
@@ -539,33 +539,6 @@ k_ln_bwd_reduce(const float* __restrict__ partial, int nblocks, int C2, float* _
     }
 }
 
-// lane-group width G (8..64) and chunks per lane V (1..4) with G*V >= C/8 and the fewest idle lanes; ties go to the
-// narrower group (more rows per wave in flight).  C = 384 -> (16,3), 192 -> (8,3), 768 -> (32,3), 256 -> (8,4), 1000 -> (32,4)
-static int pick_group(int C, int* V) {
-    const int nch = C / 8;
-    int bestG = 64, bestV = 4, best_waste = 1 << 30;
-    for (int G = 8; G <= 64; G <<= 1)
-        for (int v = 1; v <= 4; ++v) {
-            if (G * v < nch) continue;
-            const int waste = G * v - nch;
-            if (waste < best_waste) { best_waste = waste; bestG = G; bestV = v; }
-        }
-    *V = bestV;
-    return bestG;
-}
-
-// backward keeps 3 operand rows per row in registers next to the dgamma/dbeta accumulators: one chunk per lane and a
-// wide group (G >= C/8) with 4 rows unrolled measured faster there (22.7 vs 27.4 us at 25088 x 384) than the
-// no-idle-lane mapping above, whose register footprint halves the occupancy
-static int pick_group_wide(int C, int* V) {
-    const int nch = C / 8;
-    int G = 16;
-    while (G < 64 && G < nch) G <<= 1;
-    const int v = (nch + G - 1) / G;
-    *V = v <= 1 ? 1 : (v <= 2 ? 2 : 4);
-    return G;
-}
-
 extern "C" {
 
 int ap_layernorm_fwd(const ap_bf16* x, const float* gamma, const float* beta, ap_bf16* y, float* mean, float* rstd,
@@ -577,32 +550,14 @@ int ap_layernorm_fwd_fp8(const ap_bf16* x, const float* gamma, const float* beta
                          float* q_amax, float* mean, float* rstd, int64_t rows, int C, float eps, ap_stream_t stream) {
     if (!x || !gamma || !beta || !y || !mean || !rstd) return AP_ERR_NULL;
     if (y8 && !q_scale) return AP_ERR_NULL;
-    if (C <= 0 || (C & 7)) return AP_ERR_SHAPE;
-    if (C > 2048) return AP_ERR_UNSUPPORTED;
-    if (rows <= 0) return AP_OK;
-    static int rpg = 0, wide = -1;
-    if (rpg == 0) { const char* e = getenv("AP_LN_FWD_RPG"); rpg = e ? atoi(e) : 1; if (rpg < 1) rpg = 1;       // one row per lane group and workgroup: 10.3 vs 10.7 us at 25088 x 384 (4: 11.4, 8: 15.3)
-                    const char* w = getenv("AP_LN_FWD_WIDE"); wide = w ? atoi(w) : 0; }
-    int V; const int G = wide ? pick_group_wide(C, &V) : pick_group(C, &V);
-    const int gpb = 256 / G;
-    int64_t grid = ceil_div64(rows, (int64_t)gpb * rpg);
-    if (grid > 256 * 8) grid = 256 * 8;
-    if (grid < 1) grid = 1;
-    const size_t lds = (size_t)2 * C * sizeof(float);
-    hipStream_t s = (hipStream_t)stream;
+    const LnPlan p = ln_fwd_plan(rows, C, ap_switches(), y8 != nullptr);
+    if (p.status != AP_OK || !p.grid) return p.status;
+    using Kernel = void (*)(const bf16_t*, const float*, const float*, bf16_t*, float*, float*, int64_t, int, int, float, unsigned char*, const float*, float*);
+    static const Kernel lp[3] = {k_ln_fwd_lp<1>, k_ln_fwd_lp<2>, k_ln_fwd_lp<3>};                             // [V - 1]
+    static const Kernel plain[4] = {k_ln_fwd<1, 4>, k_ln_fwd<2, 4>, k_ln_fwd<3, 2>, k_ln_fwd<4, 2>};          // [V - 1]: U of ln_fwd_plan
     (void)hipGetLastError();
-    static int lp = -1;
-    if (lp < 0) { const char* e = getenv("AP_LN_FWD_LP"); lp = e ? atoi(e) : 1; }
-    if (lp && V <= 3) {          // the low-register forward (the widths it was measured on: 192, 384, 768)
-        if (V == 1) hipLaunchKernelGGL((k_ln_fwd_lp<1>), dim3((int)grid), dim3(256), lds, s, x, gamma, beta, y, mean, rstd, rows, C, G, eps, y8, q_scale, q_amax);
-        else if (V == 2) hipLaunchKernelGGL((k_ln_fwd_lp<2>), dim3((int)grid), dim3(256), lds, s, x, gamma, beta, y, mean, rstd, rows, C, G, eps, y8, q_scale, q_amax);
-        else hipLaunchKernelGGL((k_ln_fwd_lp<3>), dim3((int)grid), dim3(256), lds, s, x, gamma, beta, y, mean, rstd, rows, C, G, eps, y8, q_scale, q_amax);
-        return ap_check_launch();
-    }
-    if (V == 1) hipLaunchKernelGGL((k_ln_fwd<1, 4>), dim3((int)grid), dim3(256), lds, s, x, gamma, beta, y, mean, rstd, rows, C, G, eps, y8, q_scale, q_amax);
-    else if (V == 2) hipLaunchKernelGGL((k_ln_fwd<2, 4>), dim3((int)grid), dim3(256), lds, s, x, gamma, beta, y, mean, rstd, rows, C, G, eps, y8, q_scale, q_amax);
-    else if (V == 3) hipLaunchKernelGGL((k_ln_fwd<3, 2>), dim3((int)grid), dim3(256), lds, s, x, gamma, beta, y, mean, rstd, rows, C, G, eps, y8, q_scale, q_amax);
-    else hipLaunchKernelGGL((k_ln_fwd<4, 2>), dim3((int)grid), dim3(256), lds, s, x, gamma, beta, y, mean, rstd, rows, C, G, eps, y8, q_scale, q_amax);
+    hipLaunchKernelGGL(p.family == LN_FWD_LP ? lp[p.V - 1] : plain[p.V - 1], dim3(p.grid), dim3(p.block), p.lds_bytes, (hipStream_t)stream,
+                       x, gamma, beta, y, mean, rstd, rows, C, p.G, eps, y8, q_scale, q_amax);
     return ap_check_launch();
 }
 
@@ -640,69 +595,60 @@ k_ln_bwd_reduce_batched(LnReduceBatch bt) {
     }
 }
 
-static thread_local int* g_ln_defer_blocks = nullptr;       // set by ap_layernorm_bwd_partial around its call of ap_layernorm_bwd
-static thread_local LnPool g_ln_pool = {nullptr, 0, 0, 0, 0, 0u, 0u};     // set by ap_layernorm_bwd_partial_pool likewise
-
 size_t ap_layernorm_bwd_workspace(int64_t rows, int C) {
     (void)rows;
-    return (size_t)1024 * 2 * (size_t)C * sizeof(float);
+    return (size_t)LN_MAX_PARTIAL * 2 * (size_t)C * sizeof(float);
+}
+
+// the three backward entry points: dx and the partial rows of dgamma / dbeta in one launch; then the reduction into dgamma / dbeta, or
+// (n_partial) the number of partial rows for a caller that batches the reduction.  pool: the average pool's gradient rides in
+struct LnBwdArgs { const bf16_t *dy, *x; const float *gamma, *mean, *rstd; const bf16_t* dres; bf16_t* dx; float *dgamma, *dbeta; int64_t rows; int C;
+                   void* workspace; size_t ws_bytes; const LnPool* pool; int* n_partial; };
+static int ln_bwd(const LnBwdArgs& a, hipStream_t s) {
+    if (!a.dy || !a.x || !a.gamma || !a.mean || !a.rstd || !a.dx || !a.workspace) return AP_ERR_NULL;
+    if (a.ws_bytes < ap_layernorm_bwd_workspace(a.rows, a.C)) return AP_ERR_SHAPE;
+    const LnPlan p = ln_bwd_plan(a.rows, a.C, ap_switches(), a.pool != nullptr);
+    if (p.status != AP_OK || !p.grid) return p.status;
+    float* partial = static_cast<float*>(a.workspace);
+    using Kernel = void (*)(const bf16_t*, const bf16_t*, const float*, const float*, const float*, const bf16_t*, bf16_t*, float*, int64_t, int, int);
+    using KernelPf = void (*)(const bf16_t*, const bf16_t*, const float*, const float*, const float*, const bf16_t*, bf16_t*, float*, int64_t, int, int, LnPool);
+    static const struct { int V, U, OCC, pool; KernelPf kernel; } pipelined[] = {             // the instantiations of ln_bwd_plan
+        {1, 2, 1, 1, k_ln_bwd_pf<1, 2, 1, true>}, {1, 2, 4, 0, k_ln_bwd_pf<1, 2, 4>}, {1, 4, 1, 0, k_ln_bwd_pf<1, 4>}, {1, 2, 1, 0, k_ln_bwd_pf<1, 2>},
+        {2, 2, 1, 0, k_ln_bwd_pf<2, 2>}, {2, 1, 1, 0, k_ln_bwd_pf<2, 1>}};
+    static const Kernel plain[4] = {k_ln_bwd<1, 4>, k_ln_bwd<2, 2>, k_ln_bwd<3, 2>, k_ln_bwd<4, 1>};         // [V - 1]: U of ln_bwd_plan
+    (void)hipGetLastError();
+    if (p.family == LN_BWD) {
+        hipLaunchKernelGGL(plain[p.V - 1], dim3(p.grid), dim3(p.block), p.lds_bytes, s, a.dy, a.x, a.gamma, a.mean, a.rstd, a.dres, a.dx, partial, a.rows, a.C, p.G);
+    } else {
+        KernelPf kernel = nullptr;
+        for (const auto& k : pipelined) if (k.V == p.V && k.U == p.U && k.OCC == p.OCC && k.pool == p.pool) kernel = k.kernel;
+        if (!kernel) return AP_ERR_UNSUPPORTED;
+        hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.lds_bytes, s, a.dy, a.x, a.gamma, a.mean, a.rstd, a.dres, a.dx, partial, a.rows, a.C, p.G,
+                           a.pool ? *a.pool : LnPool{nullptr, 0, 0, 0, 0, 0u, 0u});
+    }
+    if (const int rc = ap_check_launch(); rc != AP_OK) return rc;
+    if (a.n_partial) { *a.n_partial = p.n_partial; return AP_OK; }
+    hipLaunchKernelGGL(k_ln_bwd_reduce, dim3((2 * a.C + 31) / 32), dim3(1024), 0, s, partial, p.n_partial, 2 * a.C, a.dgamma, a.dbeta, a.C);
+    return ap_check_launch();
 }
 
 int ap_layernorm_bwd(const ap_bf16* dy, const ap_bf16* x, const float* gamma, const float* mean, const float* rstd,
                      const ap_bf16* dres, ap_bf16* dx, float* dgamma, float* dbeta, int64_t rows, int C,
                      void* workspace, size_t ws_bytes, ap_stream_t stream) {
-    if (!dy || !x || !gamma || !mean || !rstd || !dx || !dgamma || !dbeta || !workspace) return AP_ERR_NULL;
-    if (ws_bytes < ap_layernorm_bwd_workspace(rows, C)) return AP_ERR_SHAPE;
-    float* partial = static_cast<float*>(workspace);
-    if (C <= 0 || (C & 7)) return AP_ERR_SHAPE;
-    if (C > 2048) return AP_ERR_UNSUPPORTED;
-    if (rows <= 0) return AP_OK;
-    int V; const int G = pick_group_wide(C, &V);
-    const int gpb = 256 / G;
-    int64_t grid = ceil_div64(rows, gpb);
-    static int grid_cap = 0;
-    if (grid_cap == 0) { const char* e = getenv("AP_LN_BWD_GRID"); grid_cap = e ? atoi(e) : 768; if (grid_cap < 1 || grid_cap > 1024) grid_cap = 768; }   // 3 blocks per CU measured best (20.7 vs 23.5 us at 1024)
-    if (grid > grid_cap) grid = grid_cap;   // bounds the dgamma/dbeta partial rows (workspace holds 1024)
-    if (V >= 2 && grid > 512 && !getenv("AP_LN_BWD_GRID")) grid = 512;      // 768-wide rows (DeiT-Base, VOLO-D5): 19.6 us at two workgroups per CU, 24.3 at three
-    const size_t lds = (size_t)2 * 4 * C * sizeof(float);
-    hipStream_t s = (hipStream_t)stream;
-    (void)hipGetLastError();
-    // (5 rows per trip instead of 4 -- every lane group of the VOLO-D1 launch then finishes its 8 or 9 rows in two trips instead of three for
-    // a sixth of them -- measured equal, 17.5 vs 17.7 us: the trips are not what the launch waits for)
-    static int pf = -1;             // AP_LN_BWD_PF: 0 = the trip-by-trip kernel of rounds 1 - 4; 1 = pipelined, half the rows per trip (the same registers in flight);
-    if (pf < 0) { const char* e = getenv("AP_LN_BWD_PF"); pf = e ? atoi(e) : 1; }        //               2 = pipelined with the old rows per trip (twice the registers)
-    if (g_ln_pool.grad) {           // the average pool's gradient rides in (pipelined kernel, one chunk per lane: C <= 512)
-        if (!pf || V != 1) return AP_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL((k_ln_bwd_pf<1, 2, 1, true>), dim3((int)grid), dim3(256), lds, s, dy, x, gamma, mean, rstd, dres, dx, partial, rows, C, G, g_ln_pool);
-    } else
-    if (pf && V <= 2) {             // (four chunks per lane: two register sets do not fit 256 registers)
-        if (V == 1 && pf == 3) hipLaunchKernelGGL((k_ln_bwd_pf<1, 2, 4>), dim3((int)grid), dim3(256), lds, s, dy, x, gamma, mean, rstd, dres, dx, partial, rows, C, G);
-        else if (V == 1) { if (pf == 2) hipLaunchKernelGGL((k_ln_bwd_pf<1, 4>), dim3((int)grid), dim3(256), lds, s, dy, x, gamma, mean, rstd, dres, dx, partial, rows, C, G);
-                      else hipLaunchKernelGGL((k_ln_bwd_pf<1, 2>), dim3((int)grid), dim3(256), lds, s, dy, x, gamma, mean, rstd, dres, dx, partial, rows, C, G); }
-        else { if (pf == 2) hipLaunchKernelGGL((k_ln_bwd_pf<2, 2>), dim3((int)grid), dim3(256), lds, s, dy, x, gamma, mean, rstd, dres, dx, partial, rows, C, G);
-               else hipLaunchKernelGGL((k_ln_bwd_pf<2, 1>), dim3((int)grid), dim3(256), lds, s, dy, x, gamma, mean, rstd, dres, dx, partial, rows, C, G); }
-    } else
-    if (V == 1) hipLaunchKernelGGL((k_ln_bwd<1, 4>), dim3((int)grid), dim3(256), lds, s, dy, x, gamma, mean, rstd, dres, dx, partial, rows, C, G);
-    else if (V == 2) hipLaunchKernelGGL((k_ln_bwd<2, 2>), dim3((int)grid), dim3(256), lds, s, dy, x, gamma, mean, rstd, dres, dx, partial, rows, C, G);
-    else if (V == 3) hipLaunchKernelGGL((k_ln_bwd<3, 2>), dim3((int)grid), dim3(256), lds, s, dy, x, gamma, mean, rstd, dres, dx, partial, rows, C, G);
-    else hipLaunchKernelGGL((k_ln_bwd<4, 1>), dim3((int)grid), dim3(256), lds, s, dy, x, gamma, mean, rstd, dres, dx, partial, rows, C, G);
-    int rc = ap_check_launch();
-    if (rc != AP_OK) return rc;
-    if (g_ln_defer_blocks) { *g_ln_defer_blocks = (int)grid; return AP_OK; }      // ap_layernorm_bwd_partial: the caller batches the reduction
-    hipLaunchKernelGGL(k_ln_bwd_reduce, dim3((2 * C + 31) / 32), dim3(1024), 0, s, partial, (int)grid, 2 * C, dgamma, dbeta, C);
-    return ap_check_launch();
+    if (!dgamma || !dbeta) return AP_ERR_NULL;
+    return ln_bwd(LnBwdArgs{dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, rows, C, workspace, ws_bytes, nullptr, nullptr}, (hipStream_t)stream);
+}
+
+static int ln_bwd_partial(const LnBwdArgs& a, hipStream_t s) {
+    if (!a.n_partial) return AP_ERR_NULL;
+    *a.n_partial = 0;
+    return ln_bwd(a, s);
 }
 
 int ap_layernorm_bwd_partial(const ap_bf16* dy, const ap_bf16* x, const float* gamma, const float* mean, const float* rstd,
                              const ap_bf16* dres, ap_bf16* dx, int64_t rows, int C, void* workspace, size_t ws_bytes, int* n_partial,
                              ap_stream_t stream) {
-    if (!n_partial) return AP_ERR_NULL;
-    float dummy = 0.f;                                   // dgamma / dbeta are not touched on this path
-    g_ln_defer_blocks = n_partial;
-    *n_partial = 0;
-    const int rc = ap_layernorm_bwd(dy, x, gamma, mean, rstd, dres, dx, &dummy, &dummy, rows, C, workspace, ws_bytes, stream);
-    g_ln_defer_blocks = nullptr;
-    return rc;
+    return ln_bwd_partial(LnBwdArgs{dy, x, gamma, mean, rstd, dres, dx, nullptr, nullptr, rows, C, workspace, ws_bytes, nullptr, n_partial}, (hipStream_t)stream);
 }
 
 int ap_layernorm_bwd_partial_pool(const ap_bf16* dy, const ap_bf16* pool_grad, int B, int H, int W, const ap_bf16* x, const float* gamma,
@@ -717,10 +663,7 @@ int ap_layernorm_bwd_partial_pool(const ap_bf16* dy, const ap_bf16* pool_grad, i
     p.magic_hw = (unsigned)(0xFFFFFFFFu / hw) + 1u;                  // exact for rows < 2^32 / (H W)
     p.magic_w = (unsigned)(0xFFFFFFFFu / (unsigned)W) + 1u;
     if ((uint64_t)B * hw >= (uint64_t)(0xFFFFFFFFu / hw)) return AP_ERR_UNSUPPORTED;
-    g_ln_pool = p;
-    const int rc = ap_layernorm_bwd_partial(dy, x, gamma, mean, rstd, dres, dx, (int64_t)B * H * W, C, workspace, ws_bytes, n_partial, stream);
-    g_ln_pool.grad = nullptr;
-    return rc;
+    return ln_bwd_partial(LnBwdArgs{dy, x, gamma, mean, rstd, dres, dx, nullptr, nullptr, (int64_t)B * H * W, C, workspace, ws_bytes, &p, n_partial}, (hipStream_t)stream);
 }
 
 int ap_layernorm_bwd_reduce_batched(const ap_ln_reduce* items, int count, ap_stream_t stream) {

@@ -17,7 +17,7 @@
 // transposed reads.
 #include "common.h"
 #include "attn_frag.h"
-#include <cstdlib>
+#include "attn_plan.h"
 
 
 // Stage NTILES token-major operands ([N, HD] slices with row stride ld[i]) into their LDS tiles.  ALL global loads of a thread
@@ -149,7 +149,6 @@ k_mhsa_fwd(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, float* __re
 // loaders: they fetch the NEXT item's K and V rows and write them to the other K/V buffer in LDS while the others compute, so an item
 // starts on operands that are already there (k_mhsa_fwd stages K/V per workgroup and relies on co-resident workgroups for overlap).
 // One LDS-only barrier per item (s_waitcnt lgkmcnt(0); s_barrier): nothing waits for the Q prefetch or the output stores.
-#define FP_LOADERS 3
 template <int NT>
 __global__ void __launch_bounds__(1024)
 k_mhsa_fwd_p(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, float* __restrict__ lse, int N, int heads, float scale,
@@ -469,8 +468,6 @@ k_mhsa_bwd(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out, const
 // (s_waitcnt lgkmcnt(0); s_barrier): nothing waits for the prefetch or for the result stores.
 // B = 128, N = 196, 12 heads: 52 us against 66 us (k_mhsa_bwd); by phase: barriers + launch 10, arithmetic 31 (VALU-bound: 56 exp, fma,
 // mul, cvt each per wave and item, on the SIMD that holds 4 of the 13 compute waves), exposed loader work + result stores 11.
-#define DS_STR 232               // dS^T row stride (bf16): 224 queries + 8 of padding (464 B: conflict-free transposed reads)
-#define DS_LOADERS 3
 template <int NP>                // query-tile pairs (NT == 2 NP): the phase-1 loop is unrolled, every LDS address is a base + constant
 __global__ void __launch_bounds__(1024)
 k_mhsa_bwd_ds(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out, const bf16_t* __restrict__ dout,
@@ -825,132 +822,96 @@ k_class_attn_bwd(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kv, co
     }
 }
 
-#define MHSA_FWD_CASE(NTV, HDV) case NTV: hipLaunchKernelGGL((k_mhsa_fwd<NTV, HDV>), grid, dim3(256), lds, s, qkv, out, lse, N, heads, scale, out_row_scale); break;
-#define MHSA_FWD_SWITCH(HDV)                                                                     \
-    switch (nt) { MHSA_FWD_CASE(2, HDV) MHSA_FWD_CASE(4, HDV) MHSA_FWD_CASE(6, HDV) MHSA_FWD_CASE(8, HDV)  \
-                  MHSA_FWD_CASE(10, HDV) MHSA_FWD_CASE(12, HDV) MHSA_FWD_CASE(14, HDV)             \
-                  default: hipLaunchKernelGGL((k_mhsa_fwd<16, HDV>), grid, dim3(256), lds, s, qkv, out, lse, N, heads, scale, out_row_scale); break; }
-
-// N <= 256 with head_dim 32 / 64: one workgroup holds the whole head in LDS (kernels above); anything else (448-px inputs,
-// head_dim 48 of VOLO-D4/D5) goes to the key/query-blocked kernels of mhsa_flash.hip.  AP_MHSA_FLASH=1 forces the blocked path
-// (parity tests run both on the same inputs).
-static bool mhsa_use_flash(int N, int hd) {
-    static int force = -1;
-    if (force < 0) { const char* e = getenv("AP_MHSA_FLASH"); force = (e && e[0] == '1') ? 1 : 0; }
-    return force || N > 256 || hd == 48;
+// ---- which kernel takes a shape, with which instantiation, grid and LDS is planned by attn_plan.h; here its plans become launches
+static MhsaPlan mhsa_plan_here(int dir, int B, int N, int heads, int hd, bool want_fp8 = false) {
+    return mhsa_plan(dir, B, N, heads, hd, ap_cu_count(), ap_switches(), want_fp8);
 }
+#define MHSA_FWD_CASE(NTV, HDV) case NTV: hipLaunchKernelGGL((k_mhsa_fwd<NTV, HDV>), grid, dim3(p.block), p.lds_bytes, s, qkv, out, lse, N, heads, scale, out_row_scale); break;
+#define MHSA_FWD_SWITCH(HDV)                                                                     \
+    switch (p.nt) { MHSA_FWD_CASE(2, HDV) MHSA_FWD_CASE(4, HDV) MHSA_FWD_CASE(6, HDV) MHSA_FWD_CASE(8, HDV) MHSA_FWD_CASE(10, HDV)  \
+                    MHSA_FWD_CASE(12, HDV) MHSA_FWD_CASE(14, HDV) MHSA_FWD_CASE(16, HDV) default: return AP_ERR_UNSUPPORTED; }
 
 extern "C" {
+
+int ap_mhsa_fwd_emits_fp8(int N, int hd) { return mhsa_plan_here(ATTN_FWD, 1, N, 1, hd, true).status == AP_OK; }
 
 int ap_mhsa_fwd_fp8(const ap_bf16* qkv, ap_bf16* out, unsigned char* out8, const float* q_scale, float* q_amax, float* lse, int B, int N,
                     int heads, int hd, float scale, const float* out_row_scale, ap_stream_t stream) {
     if (!qkv || !out || !lse || !out8 || !q_scale) return AP_ERR_NULL;
-    if (B <= 0 || N <= 0 || heads <= 0) return AP_ERR_SHAPE;
-    if (hd != 32 && hd != 48 && hd != 64) return AP_ERR_UNSUPPORTED;
-    if (!mhsa_use_flash(N, hd)) return AP_ERR_UNSUPPORTED;          // the e4m3 side output exists in the blocked kernel only
+    const MhsaPlan p = mhsa_plan_here(ATTN_FWD, B, N, heads, hd, true);
+    if (p.status != AP_OK) return p.status;
     return ap_mhsa_flash_fwd(qkv, out, lse, B, N, heads, hd, scale, out_row_scale, (hipStream_t)stream, out8, q_scale, q_amax);
 }
 
 int ap_mhsa_fwd(const ap_bf16* qkv, ap_bf16* out, float* lse, int B, int N, int heads, int hd, float scale, const float* out_row_scale,
                 ap_stream_t stream) {
     if (!qkv || !out || !lse) return AP_ERR_NULL;
-    if (B <= 0 || N <= 0 || heads <= 0) return AP_ERR_SHAPE;
-    if (hd != 32 && hd != 48 && hd != 64) return AP_ERR_UNSUPPORTED;
-    if (mhsa_use_flash(N, hd)) return ap_mhsa_flash_fwd(qkv, out, lse, B, N, heads, hd, scale, out_row_scale, (hipStream_t)stream);
-    const int nt = 2 * ((N + 31) / 32);
-    const dim3 grid(B * heads);
-    const size_t lds = (size_t)2 * nt * 16 * hd * sizeof(bf16_t);
+    const MhsaPlan p = mhsa_plan_here(ATTN_FWD, B, N, heads, hd);
+    if (p.status != AP_OK) return p.status;
     hipStream_t s = (hipStream_t)stream;
+    if (p.family == MHSA_FLASH) return ap_mhsa_flash_fwd(qkv, out, lse, B, N, heads, hd, scale, out_row_scale, s);
+    const dim3 grid(p.grid);
     (void)hipGetLastError();
-    // head_dim 32 and 7 .. 13 query tiles: the persistent kernel with loader waves (AP_MHSA_FWD_P=0: one workgroup per (image, head))
-    static int use_p = -1;
-    if (use_p < 0) { const char* e = getenv("AP_MHSA_FWD_P"); use_p = e ? atoi(e) : 1; }
-    const int p_cu = ap_cu_count() & ~7;                                       // whole XCD groups (xcd_remap)
-    const int nq = (N + 15) / 16;
-    if (hd == 32 && use_p && nq >= 7 && nq <= 16 - FP_LOADERS && p_cu >= 8) {
-        const int items = B * heads;
-        const dim3 gp(items < p_cu ? items : p_cu);
-        const size_t lds_p = 2 * lds;
-#define FP_LAUNCH(NTV) hipLaunchKernelGGL((k_mhsa_fwd_p<NTV>), gp, dim3(1024), lds_p, s, qkv, out, lse, N, heads, scale, out_row_scale, items)
-        switch (nt) { case 8: FP_LAUNCH(8); break; case 10: FP_LAUNCH(10); break; case 12: FP_LAUNCH(12); break; default: FP_LAUNCH(14); break; }
+    if (p.family == MHSA_FWD_P) {
+#define FP_LAUNCH(NTV) case NTV: hipLaunchKernelGGL((k_mhsa_fwd_p<NTV>), grid, dim3(p.block), p.lds_bytes, s, qkv, out, lse, N, heads, scale, out_row_scale, p.items); break;
+        switch (p.nt) { FP_LAUNCH(8) FP_LAUNCH(10) FP_LAUNCH(12) FP_LAUNCH(14) default: return AP_ERR_UNSUPPORTED; }
 #undef FP_LAUNCH
         return ap_check_launch();
     }
-    if (hd != 32 && nt >= 14) {                                                // the two instantiations whose head does not fit 64 KB
-        if (const int rc = nt == 14 ? ap_allow_lds<k_mhsa_fwd<14, 64>>(96 * 1024) : ap_allow_lds<k_mhsa_fwd<16, 64>>(96 * 1024); rc != AP_OK) return rc;
+    if (p.lds_optin) {
+        if (const int rc = p.nt == 14 ? ap_allow_lds<k_mhsa_fwd<14, 64>>(p.lds_optin) : ap_allow_lds<k_mhsa_fwd<16, 64>>(p.lds_optin); rc != AP_OK) return rc;
     }
-    if (hd == 32) { MHSA_FWD_SWITCH(32) } else { MHSA_FWD_SWITCH(64) }
+    if (p.hdt == 32) { MHSA_FWD_SWITCH(32) } else { MHSA_FWD_SWITCH(64) }
     return ap_check_launch();
 }
 
-size_t ap_mhsa_bwd_workspace(int B, int N, int heads, int hd) {
-    if (B <= 0 || N <= 0 || heads <= 0) return 0;
-    return mhsa_use_flash(N, hd) ? ap_mhsa_flash_bwd_ws(B, N, heads) : 0;
-}
+size_t ap_mhsa_bwd_workspace(int B, int N, int heads, int hd) { return mhsa_plan_here(ATTN_BWD, B, N, heads, hd).ws_bytes; }
 
 int ap_mhsa_bwd(const ap_bf16* qkv, const ap_bf16* out, const ap_bf16* dout, const float* lse, ap_bf16* dqkv,
                 int B, int N, int heads, int hd, float scale, void* workspace, size_t ws_bytes, ap_stream_t stream) {
     if (!qkv || !out || !dout || !lse || !dqkv) return AP_ERR_NULL;
-    if (B <= 0 || N <= 0 || heads <= 0) return AP_ERR_SHAPE;
-    if (hd != 32 && hd != 48 && hd != 64) return AP_ERR_UNSUPPORTED;
-    if (mhsa_use_flash(N, hd)) {
-        if (!workspace) return AP_ERR_NULL;
-        if (ws_bytes < ap_mhsa_flash_bwd_ws(B, N, heads)) return AP_ERR_SHAPE;
-        return ap_mhsa_flash_bwd(qkv, out, dout, lse, dqkv, B, N, heads, hd, scale, (float*)workspace, (hipStream_t)stream);
-    }
-    const int nt = 2 * ((N + 31) / 32);
-    const dim3 grid(B * heads);
-    const size_t lds = (size_t)4 * nt * 16 * hd * sizeof(bf16_t) + (size_t)2 * nt * 16 * sizeof(float);
+    const MhsaPlan p = mhsa_plan_here(ATTN_BWD, B, N, heads, hd);
+    if (p.status != AP_OK) return p.status;
     hipStream_t s = (hipStream_t)stream;
-    (void)hipGetLastError();
-    // default for head_dim 32 and 8 .. 13 token tiles (N = 113 .. 208): dS through LDS, loader waves (AP_MHSA_BWD_DS=0: the two-pass kernel)
-    static int use_ds = -1;
-    if (use_ds < 0) { const char* e = getenv("AP_MHSA_BWD_DS"); use_ds = e ? atoi(e) : 1; }
-    int ds_cu = ap_cu_count();
-    if (ds_cu >= 8) ds_cu &= ~7;                                               // whole XCD groups (xcd_remap)
-    {
-        const int ntile = (N + 15) / 16;
-        const size_t lds_ds = lds + (size_t)2 * nt * 16 * sizeof(float) + (size_t)ntile * 16 * DS_STR * sizeof(bf16_t);
-        if (hd == 32 && use_ds && ntile <= 16 - DS_LOADERS && ntile >= 7 && nt * 16 * 4 <= 5 * 64 * DS_LOADERS && nt * 16 <= DS_STR - 8 &&
-            lds_ds <= (size_t)160 * 1024) {
-            const int items = B * heads;
-            const dim3 gds(items < ds_cu ? items : ds_cu);
-#define DS_LAUNCH(NP) if (const int rc = ap_allow_lds<k_mhsa_bwd_ds<NP>>(160 * 1024); rc != AP_OK) return rc; \
-                      hipLaunchKernelGGL(k_mhsa_bwd_ds<NP>, gds, dim3(1024), lds_ds, s, qkv, out, dout, lse, dqkv, N, heads, scale, nt, items)
-            switch (nt / 2) { case 4: DS_LAUNCH(4); break; case 5: DS_LAUNCH(5); break; case 6: DS_LAUNCH(6); break; default: DS_LAUNCH(7); break; }
-#undef DS_LAUNCH
-            return ap_check_launch();
-        }
+    if (p.family == MHSA_FLASH) {
+        if (!workspace) return AP_ERR_NULL;
+        if (ws_bytes < p.ws_bytes) return AP_ERR_SHAPE;
+        return ap_mhsa_flash_bwd(qkv, out, dout, lse, dqkv, B, N, heads, hd, scale, (float*)workspace, s);
     }
-    if (const int rc = hd == 32 ? ap_allow_lds<k_mhsa_bwd<32>>(160 * 1024) : ap_allow_lds<k_mhsa_bwd<64>>(160 * 1024); rc != AP_OK) return rc;
-    if (hd == 32) hipLaunchKernelGGL(k_mhsa_bwd<32>, grid, dim3(512), lds, s, qkv, out, dout, lse, dqkv, N, heads, scale, nt);
-    else hipLaunchKernelGGL(k_mhsa_bwd<64>, grid, dim3(512), lds, s, qkv, out, dout, lse, dqkv, N, heads, scale, nt);
+    const dim3 grid(p.grid);
+    (void)hipGetLastError();
+    if (p.family == MHSA_BWD_DS) {
+#define DS_LAUNCH(NP) case NP: if (const int rc = ap_allow_lds<k_mhsa_bwd_ds<NP>>(p.lds_optin); rc != AP_OK) return rc; \
+        hipLaunchKernelGGL(k_mhsa_bwd_ds<NP>, grid, dim3(p.block), p.lds_bytes, s, qkv, out, dout, lse, dqkv, N, heads, scale, p.nt, p.items); break;
+        switch (p.nt / 2) { DS_LAUNCH(4) DS_LAUNCH(5) DS_LAUNCH(6) DS_LAUNCH(7) default: return AP_ERR_UNSUPPORTED; }
+#undef DS_LAUNCH
+        return ap_check_launch();
+    }
+    if (const int rc = p.hdt == 32 ? ap_allow_lds<k_mhsa_bwd<32>>(p.lds_optin) : ap_allow_lds<k_mhsa_bwd<64>>(p.lds_optin); rc != AP_OK) return rc;
+    if (p.hdt == 32) hipLaunchKernelGGL(k_mhsa_bwd<32>, grid, dim3(p.block), p.lds_bytes, s, qkv, out, dout, lse, dqkv, N, heads, scale, p.nt);
+    else hipLaunchKernelGGL(k_mhsa_bwd<64>, grid, dim3(p.block), p.lds_bytes, s, qkv, out, dout, lse, dqkv, N, heads, scale, p.nt);
     return ap_check_launch();
 }
 
 int ap_class_attn_fwd(const ap_bf16* q, const ap_bf16* kv, const ap_bf16* kv_cls, ap_bf16* out, float* probs, int B, int N, int heads, int hd,
                       float scale, ap_stream_t stream) {
     if (!q || !kv || !out || !probs) return AP_ERR_NULL;
-    if (B <= 0 || N <= 0 || heads <= 0) return AP_ERR_SHAPE;
-    if (hd != 32 && hd != 48 && hd != 64) return AP_ERR_UNSUPPORTED;
-    const size_t lds = ((size_t)((N + 63) & ~63) + 64 * 32) * sizeof(float);          // KS * HDP = 2048 floats for both PARTS
-    if (lds > 64 * 1024) return AP_ERR_UNSUPPORTED;
+    const MhsaPlan p = class_attn_plan(B, N, heads, hd);
+    if (p.status != AP_OK) return p.status;
     (void)hipGetLastError();
-    if (hd == 32) hipLaunchKernelGGL(k_class_attn_fwd<4>, dim3(B * heads), dim3(256), lds, (hipStream_t)stream, q, kv, out, probs, N, heads, hd, scale, kv_cls);
-    else hipLaunchKernelGGL(k_class_attn_fwd<8>, dim3(B * heads), dim3(256), lds, (hipStream_t)stream, q, kv, out, probs, N, heads, hd, scale, kv_cls);
+    if (p.hdt == 32) hipLaunchKernelGGL(k_class_attn_fwd<4>, dim3(p.grid), dim3(p.block), p.lds_bytes, (hipStream_t)stream, q, kv, out, probs, N, heads, hd, scale, kv_cls);
+    else hipLaunchKernelGGL(k_class_attn_fwd<8>, dim3(p.grid), dim3(p.block), p.lds_bytes, (hipStream_t)stream, q, kv, out, probs, N, heads, hd, scale, kv_cls);
     return ap_check_launch();
 }
 
 int ap_class_attn_bwd(const ap_bf16* q, const ap_bf16* kv, const ap_bf16* kv_cls, const float* probs, const ap_bf16* dout, ap_bf16* dq, ap_bf16* dkv,
                       ap_bf16* dkv_cls, int B, int N, int heads, int hd, float scale, ap_stream_t stream) {
     if (!q || !kv || !probs || !dout || !dq || !dkv || ((kv_cls == nullptr) != (dkv_cls == nullptr))) return AP_ERR_NULL;
-    if (B <= 0 || N <= 0 || heads <= 0) return AP_ERR_SHAPE;
-    if (hd != 32 && hd != 48 && hd != 64) return AP_ERR_UNSUPPORTED;
-    const size_t lds = ((size_t)((N + 63) & ~63) + 64 * 32) * sizeof(float);
-    if (lds > 64 * 1024) return AP_ERR_UNSUPPORTED;
+    const MhsaPlan p = class_attn_plan(B, N, heads, hd);
+    if (p.status != AP_OK) return p.status;
     (void)hipGetLastError();
-    if (hd == 32) hipLaunchKernelGGL(k_class_attn_bwd<4>, dim3(B * heads), dim3(256), lds, (hipStream_t)stream, q, kv, probs, dout, dq, dkv, N, heads, hd, scale, kv_cls, dkv_cls);
-    else hipLaunchKernelGGL(k_class_attn_bwd<8>, dim3(B * heads), dim3(256), lds, (hipStream_t)stream, q, kv, probs, dout, dq, dkv, N, heads, hd, scale, kv_cls, dkv_cls);
+    if (p.hdt == 32) hipLaunchKernelGGL(k_class_attn_bwd<4>, dim3(p.grid), dim3(p.block), p.lds_bytes, (hipStream_t)stream, q, kv, probs, dout, dq, dkv, N, heads, hd, scale, kv_cls, dkv_cls);
+    else hipLaunchKernelGGL(k_class_attn_bwd<8>, dim3(p.grid), dim3(p.block), p.lds_bytes, (hipStream_t)stream, q, kv, probs, dout, dq, dkv, N, heads, hd, scale, kv_cls, dkv_cls);
     return ap_check_launch();
 }
 

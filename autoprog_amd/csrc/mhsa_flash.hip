@@ -398,8 +398,6 @@ int ap_mhsa_flash_fwd(const bf16_t* qkv, bf16_t* out, float* lse, int B, int N, 
     return ap_check_launch();
 }
 
-size_t ap_mhsa_flash_bwd_ws(int B, int N, int heads) { return (size_t)B * heads * N * sizeof(float); }
-
 int ap_mhsa_flash_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, int B, int N, int heads, int hd,
                       float scale, float* delta, hipStream_t s) {
     const int64_t rows = (int64_t)B * N;

@@ -38,7 +38,6 @@
 #include "common.h"
 #include "gemm_epi.h"
 #include <type_traits>
-#include <cstdlib>
 
 #define MF_GLB(p) ((const __attribute__((address_space(1))) void*)(p))
 #define MF_LDS(p) ((__attribute__((address_space(3))) void*)(p))
@@ -1032,8 +1031,7 @@ const unsigned* g8_gelu_table_ptr(hipStream_t st) {
 
 template <int C, bool BWD, bool LN = false, bool RES = false, bool INFER = false>
 static int mf_launch(const MlpArgs& a, hipStream_t st) {
-    static int version = 0;                  // AP_MLP_FUSED_V = 1: the one-wave-per-SIMD kernel; default 2: producer / consumer waves
-    if (!version) { const char* e = getenv("AP_MLP_FUSED_V"); version = (e && e[0] == '1') ? 1 : 2; }
+    const int version = ap_switches().mlp_fused_v;      // AP_MLP_FUSED_V = 1: the one-wave-per-SIMD kernel; default 2: producer / consumer waves
     if (version == 1 && (LN || INFER)) return AP_ERR_UNSUPPORTED;
     // (refused by the runtime: AP_ERR_UNSUPPORTED, on which the caller takes the two launches)
     if (const int rc = version == 1 ? ap_allow_lds<k_mlp_fused<C, BWD>>(MF_LDS_BYTES) : ap_allow_lds<k_mlp_fused2<C, BWD, LN, RES, INFER>>(M2_LDS_BYTES); rc != AP_OK) return rc;

@@ -13,8 +13,7 @@
 // versa).  dlogits uses one lane per (window, row p): dP = <dY[src p], V[src q]>,
 // dA = s*P*(dP - sum_q P*dP).
 #include "common.h"
-#include <cstdlib>
-#include <algorithm>
+#include "attn_plan.h"
 
 // acc += a.lo*b.lo + a.hi*b.hi on packed bf16 pairs, fp32 accumulate.  Inline asm: hipcc (ROCm 7.2) miscompiles
 // __builtin_amdgcn_fdot2_f32_bf16 on elements of a 4 x u32 vector (every call reads element 0; tools/probe/dot2.hip)
@@ -26,9 +25,6 @@ __device__ __forceinline__ float dot2_bf16(unsigned a, unsigned b, float acc) {
 // gfx940+ and gets none (seen in round 4: a v_pk_mul_f32 scheduled right behind the last v_dot2c of a chain read the accumulator
 // one term short -- dlogits 4.5 % off).  Close every chain with this before its sum is used.
 __device__ __forceinline__ void dot2_done(float& acc) { asm volatile("s_nop 2" : "+v"(acc)); }
-#define OHD 32          // head dim handled by these kernels
-#define OKK 9           // 3x3 slots
-#define OPP 81
 
 // stage pixel rows [y0, y0+rows) x cols [-1, pw-1) of one head (32 channels) into LDS, zero outside the image
 // LDS layout is CHUNK-major: 16-B chunk c (8 channels) of pixel pix lives at (c*npix + pix)*16 B, so lanes
@@ -91,12 +87,6 @@ __device__ __forceinline__ void stage_probs(float* P, const bf16_t* logits, int 
     }
 }
 
-// chunk stride (in pixels) of the CHUNK-major patch image, padded so the four chunks of a pixel start 16 banks apart
-__device__ __host__ __forceinline__ int pad_npix(int npix) { return npix + ((4 - (npix & 15)) & 15); }
-// row stride (pixels) of the persistent kernels' LDS patch: the smallest value >= pw that is 3 (mod 4) -- see k_outlook_p
-__device__ __host__ __forceinline__ int olk_pws(int pw) { return pw + ((3 - pw) & 3); }
-
-#define OGT 256         // threads per workgroup of the two kernels below
 // One lane per (output pixel, 8-channel chunk): 16x the lanes of the former one-lane-per-quad mapping (which left
 // ~2 waves per SIMD on the whole chip with a 2600-FMA serial loop each).  Pixels are processed by PARITY CLASS
 // (y&1, x&1): a class has a uniform number of contributing windows (1, 2, 2, 4), so a wave never diverges.
@@ -247,7 +237,6 @@ k_outlook_dlogits(const bf16_t* __restrict__ v, const bf16_t* __restrict__ dy, c
 // ds_read_b64_tr_b16 per 16 channels from the pixel-major patch; Z_w (bf16, 9 x 32) overwrites P_w's slot -- the wave that owns the
 // window reads P before it writes Z.  TP = true folds dY with the transposed probabilities (dV).
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-#define OPZ 288                  // bf16 elements of a window's P / Z slot (9 x 32)
 #define OPR 24                   // k_outlook_p: stride (bf16 elements) of the 16-element P rows inside a slot.  48 bytes: consecutive rows start 12 banks
                                  // apart, so the 16 rows a 16-byte store (or the 9 an 8-byte operand read) touches per cycle are disjoint; at 32 bytes
                                  // rows r and r + 8 shared their banks.  9 (+ 1 zero) rows x 48 bytes fit the 576-byte slot.
@@ -726,81 +715,26 @@ k_outlook_p(OlkArgs a) {
     }
 }
 
-// geometry of a persistent launch: the tallest strip (<= 3 window rows) whose tables fit the instantiation and whose LDS image leaves
-// `wgs` workgroups per CU; -> SR (0: this shape stays on the one-item-per-workgroup kernels)
-static int olk_pick(int H, int W, bool bwd, int T, int NSU, int NPU, size_t& lds) {
-    const int h = (H + 1) / 2, w = (W + 1) / 2, pw = 2 * w + 1;
-    if (w > 32) return 0;
-    static int sr_env = -1;
-    if (sr_env < 0) { const char* e = getenv("AP_OUTLOOK_SR"); sr_env = e ? atoi(e) : 0; }
-    for (int SR = std::min(sr_env > 0 ? sr_env : 3, h); SR >= 1; --SR) {
-        const int npix = (2 * SR + 3) * pw;
-        if (npix * 4 > NSU * T || (SR + 1) * w * OKK > NPU * T) continue;
-        const int npixl = (2 * SR + 3) * olk_pws(pw);
-        lds = (size_t)npixl * OHD * 2 + (size_t)(SR + 1) * w * OPZ * 2;
-        if (bwd) lds += (size_t)pad_npix(npixl) * OHD * 2 + (((size_t)SR * w * OPP * 2 + 15) & ~(size_t)15);
-        if (lds <= 80 * 1024) return SR;
-    }
-    return 0;
-}
-
+// ---- which kernel takes a shape, with which strip height, grid and LDS is planned by attn_plan.h (outlook_plan); here its plans become launches
 template <int T, int NSU, int NPU, bool BWD>
-static int olk_launch(const OlkArgs& a0, int SR, size_t lds, hipStream_t s) {
-    OlkArgs a = a0;
-    const int h = (a.H + 1) / 2, w = (a.W + 1) / 2;
-    a.SR = SR; a.nstrips = (h + SR - 1) / SR; a.nitems = a.B * a.nstrips * a.heads;
-    a.wp_shift = w <= 16 ? 4 : 5;
-    const int ncu = ap_cu_count();
-    if (const int rc = ap_allow_lds<k_outlook_p<T, NSU, NPU, BWD>>(160 * 1024); rc != AP_OK) return rc;
-    const int per_cu = std::max(1, std::min((int)(160 * 1024 / lds), 2048 / T));
-    int grid = std::min(a.nitems, ncu * per_cu);
-    grid = std::max(8, grid & ~7);                      // a multiple of 8: the XCD-contiguous item walk
-    if (grid > a.nitems) grid = a.nitems;
-    hipLaunchKernelGGL((k_outlook_p<T, NSU, NPU, BWD>), dim3((unsigned)grid), dim3(T), lds, s, a);
+static int olk_launch(OlkArgs a, const OutlookPlan& p, hipStream_t s) {
+    a.SR = p.sr; a.nstrips = p.nstrips; a.nitems = p.nitems; a.wp_shift = p.wp_shift;
+    if (const int rc = ap_allow_lds<k_outlook_p<T, NSU, NPU, BWD>>(p.lds_optin); rc != AP_OK) return rc;
+    hipLaunchKernelGGL((k_outlook_p<T, NSU, NPU, BWD>), dim3((unsigned)p.grid), dim3(T), p.lds_bytes, s, a);
     return ap_check_launch();
 }
-
-static int gather_launch(bool tp, const bf16_t* in, const bf16_t* logits, int ldl, bf16_t* out, int B, int H, int W, int heads,
-                         float scale, hipStream_t s) {
-    const int h = (H + 1) / 2, w = (W + 1) / 2;
-    const int pw = 2 * w + 1;
-    // strips of SR window rows: a strip re-stages 3 halo pixel rows and one halo window row, so taller strips waste
-    // less; 4 rows keep ~3000 workgroups x 256 lanes in flight at 28x28 / B = 128 and 3 workgroups per CU (LDS)
-    auto lds_of = [&](int sr) { return (size_t)pad_npix((2 * sr + 3) * pw) * OHD * 2 + (size_t)(sr + 1) * w * OPP * 4; };
-    static int sr_env = -1;
-    if (sr_env < 0) { const char* e = getenv("AP_OUTLOOK_SR"); sr_env = e ? atoi(e) : 0; }
-    int SR = sr_env > 0 ? sr_env : 4; if (SR > h) SR = h;
-    while (SR > 1 && lds_of(SR) > 78 * 1024) --SR;
-    if (lds_of(SR) > 160 * 1024) return AP_ERR_UNSUPPORTED;
-    const int nstrips = (h + SR - 1) / SR;
-    const dim3 grid((unsigned)(B * nstrips * heads));
+// tp: the probabilities transposed (the backward's dV from dY)
+static int gather_launch(bool tp, const OutlookPlan& p, const bf16_t* in, const bf16_t* logits, int ldl, bf16_t* out, int H, int W, int heads, float scale, hipStream_t s) {
+    using Kernel = void (*)(const bf16_t*, const bf16_t*, int, bf16_t*, int, int, int, float, int, int);
+    static const Kernel kernels[2][2] = {{k_outlook_gather_mfma<true>, k_outlook_gather_mfma<false>}, {k_outlook_gather<true>, k_outlook_gather<false>}};     // [family][!tp]
     (void)hipGetLastError();
-    static int use_mfma = -1;
-    if (use_mfma < 0) { const char* e = getenv("AP_OUTLOOK_MFMA"); use_mfma = e ? atoi(e) : 1; }
-    if (use_mfma) {
-        auto lds_m = [&](int sr) { return (size_t)(2 * sr + 3) * pw * OHD * 2 + (size_t)(sr + 1) * w * OPZ * 2; };
-        int SRm = sr_env > 0 ? sr_env : 3; if (SRm > h) SRm = h;       // 3 window rows: 50.4 us forward at 28 x 28 / B = 128 (4: 58.6, 2: 50.3)
-        while (SRm > 1 && lds_m(SRm) > 78 * 1024) --SRm;
-        if (lds_m(SRm) <= 160 * 1024) {
-            const int ns = (h + SRm - 1) / SRm;
-            const dim3 gm((unsigned)(B * ns * heads));
-            if (const int rc = tp ? ap_allow_lds<k_outlook_gather_mfma<true>>(160 * 1024) : ap_allow_lds<k_outlook_gather_mfma<false>>(160 * 1024); rc != AP_OK) return rc;
-            if (tp) hipLaunchKernelGGL(k_outlook_gather_mfma<true>, gm, dim3(OGT), lds_m(SRm), s, in, logits, ldl, out, H, W, heads, scale, SRm, ns);
-            else hipLaunchKernelGGL(k_outlook_gather_mfma<false>, gm, dim3(OGT), lds_m(SRm), s, in, logits, ldl, out, H, W, heads, scale, SRm, ns);
-            return ap_check_launch();
-        }
+    if (p.family == OLK_GATHER_MFMA) {
+        if (const int rc = tp ? ap_allow_lds<k_outlook_gather_mfma<true>>(p.lds_optin) : ap_allow_lds<k_outlook_gather_mfma<false>>(p.lds_optin); rc != AP_OK) return rc;
+    } else if (p.lds_optin) {
+        if (const int rc = tp ? ap_allow_lds<k_outlook_gather<true>>(p.lds_optin) : ap_allow_lds<k_outlook_gather<false>>(p.lds_optin); rc != AP_OK) return rc;
     }
-    if (tp) hipLaunchKernelGGL(k_outlook_gather<true>, grid, dim3(OGT), lds_of(SR), s, in, logits, ldl, out, H, W, heads, scale, SR, nstrips);
-    else hipLaunchKernelGGL(k_outlook_gather<false>, grid, dim3(OGT), lds_of(SR), s, in, logits, ldl, out, H, W, heads, scale, SR, nstrips);
+    hipLaunchKernelGGL(kernels[p.family == OLK_GATHER][!tp], dim3((unsigned)p.grid), dim3(p.block), p.lds_bytes, s, in, logits, ldl, out, H, W, heads, scale, p.sr, p.nstrips);
     return ap_check_launch();
-}
-
-// AP_OUTLOOK_P: 1 (default) the persistent kernels with 512-thread workgroups (256 where a shape's tables do not fit 512 threads);
-// 2 the 256-thread instantiations; 0 the one-item-per-workgroup kernels of rounds 1-3
-static int olk_mode() {
-    static int m = -1;
-    if (m < 0) { const char* e = getenv("AP_OUTLOOK_P"); m = e ? atoi(e) : 1; }
-    return m;
 }
 
 extern "C" {
@@ -810,13 +744,12 @@ int ap_outlook_fwd(const ap_bf16* v, const ap_bf16* logits, int ldl, ap_bf16* y,
     if (!v || !logits || !y) return AP_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0 || heads <= 0 || ldl < heads * OPP) return AP_ERR_SHAPE;
     if (hd != OHD) return AP_ERR_UNSUPPORTED;
-    if (olk_mode()) {
-        size_t lds = 0;
-        OlkArgs a = {v, nullptr, logits, y, nullptr, ldl, B, H, W, heads, 0, 0, 0, 0, scale};
-        if (olk_mode() == 1) { if (const int SR = olk_pick(H, W, false, 512, 3, 1, lds)) return olk_launch<512, 3, 1, false>(a, SR, lds, (hipStream_t)stream); }
-        if (const int SR = olk_pick(H, W, false, 256, 5, 2, lds)) return olk_launch<256, 5, 2, false>(a, SR, lds, (hipStream_t)stream);
-    }
-    return gather_launch(false, v, logits, ldl, y, B, H, W, heads, scale, (hipStream_t)stream);
+    const OutlookPlan p = outlook_plan(ATTN_FWD, B, H, W, heads, ap_cu_count(), ap_switches());
+    if (p.status != AP_OK) return p.status;
+    const OlkArgs a = {v, nullptr, logits, y, nullptr, ldl, B, H, W, heads, 0, 0, 0, 0, scale};
+    if (p.family == OLK_P512) return olk_launch<512, 3, 1, false>(a, p, (hipStream_t)stream);
+    if (p.family == OLK_P256) return olk_launch<256, 5, 2, false>(a, p, (hipStream_t)stream);
+    return gather_launch(false, p, v, logits, ldl, y, H, W, heads, scale, (hipStream_t)stream);
 }
 
 int ap_outlook_bwd(const ap_bf16* v, const ap_bf16* logits, int ldl, const ap_bf16* dy, ap_bf16* dv, ap_bf16* dlogits,
@@ -824,26 +757,15 @@ int ap_outlook_bwd(const ap_bf16* v, const ap_bf16* logits, int ldl, const ap_bf
     if (!v || !logits || !dy || !dv || !dlogits) return AP_ERR_NULL;
     if (B <= 0 || H <= 0 || W <= 0 || heads <= 0 || ldl < heads * OPP) return AP_ERR_SHAPE;
     if (hd != OHD) return AP_ERR_UNSUPPORTED;
-    if (olk_mode()) {
-        size_t lds = 0;
-        OlkArgs a = {v, dy, logits, dv, dlogits, ldl, B, H, W, heads, 0, 0, 0, 0, scale};
-        if (olk_mode() == 1) { if (const int SR = olk_pick(H, W, true, 512, 3, 1, lds)) return olk_launch<512, 3, 1, true>(a, SR, lds, (hipStream_t)stream); }
-        if (const int SR = olk_pick(H, W, true, 256, 5, 2, lds)) return olk_launch<256, 5, 2, true>(a, SR, lds, (hipStream_t)stream);
-    }
-    int rc = gather_launch(true, dy, logits, ldl, dv, B, H, W, heads, scale, (hipStream_t)stream);
-    if (rc != AP_OK) return rc;
-    const int h = (H + 1) / 2, w = (W + 1) / 2;
-    const int pw = 2 * w + 1;
-    auto lds_of = [&](int sr) { return 2 * ((size_t)pad_npix((2 * sr + 1) * pw) * OHD * 2) + (size_t)sr * w * OPP * 4; };
-    static int srw_env = -1;
-    if (srw_env < 0) { const char* e = getenv("AP_OUTLOOK_SRW"); srw_env = e ? atoi(e) : 0; }
-    int SRW = srw_env > 0 ? srw_env : 4; if (SRW > h) SRW = h;
-    while (SRW > 1 && lds_of(SRW) > 78 * 1024) --SRW;
-    if (lds_of(SRW) > 160 * 1024) return AP_ERR_UNSUPPORTED;
-    const int nstrips = (h + SRW - 1) / SRW;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_outlook_dlogits, dim3((unsigned)(B * nstrips * heads)), dim3(OGT), lds_of(SRW), (hipStream_t)stream,
-                       v, dy, logits, ldl, dlogits, H, W, heads, scale, SRW, nstrips);
+    const OutlookPlan p = outlook_plan(ATTN_BWD, B, H, W, heads, ap_cu_count(), ap_switches());
+    if (p.status != AP_OK) return p.status;
+    const OlkArgs a = {v, dy, logits, dv, dlogits, ldl, B, H, W, heads, 0, 0, 0, 0, scale};
+    if (p.family == OLK_P512) return olk_launch<512, 3, 1, true>(a, p, (hipStream_t)stream);
+    if (p.family == OLK_P256) return olk_launch<256, 5, 2, true>(a, p, (hipStream_t)stream);
+    if (const int rc = gather_launch(true, p, dy, logits, ldl, dv, H, W, heads, scale, (hipStream_t)stream); rc != AP_OK) return rc;
+    if (p.dl_optin) { if (const int rc = ap_allow_lds<k_outlook_dlogits>(p.dl_optin); rc != AP_OK) return rc; }
+    hipLaunchKernelGGL(k_outlook_dlogits, dim3((unsigned)p.dl_grid), dim3(OGT), p.dl_lds, (hipStream_t)stream,
+                       v, dy, logits, ldl, dlogits, H, W, heads, scale, p.dl_sr, p.dl_nstrips);
     return ap_check_launch();
 }
 

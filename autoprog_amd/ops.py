@@ -701,10 +701,15 @@ def avgpool2_bwd_acc(dpooled, dx):
 
 
 # ------------------------------------------------------------------------------------- mhsa
+_mhsa_fp8_ok = {}   # (N, hd) -> ap_mhsa_fwd_emits_fp8 (a pure function of the shape in one process: one foreign call per shape)
+
+
 def mhsa_emits_fp8(N, hd):
-    """does mhsa_fwd(fp8=...) have the e4m3 side output for this shape?  (the key/query-blocked kernel: mhsa_use_flash in csrc/mhsa.hip)"""
-    e = os.environ.get("AP_MHSA_FLASH")
-    return (e == "1") if e is not None else (N > 256 or hd == 48)
+    """does mhsa_fwd(fp8=...) have the e4m3 side output for this shape?  (the key/query-blocked kernel: mhsa_plan in csrc/attn_plan.h)"""
+    ok = _mhsa_fp8_ok.get((N, hd))
+    if ok is None:
+        ok = _mhsa_fp8_ok[(N, hd)] = bool(lib.ap_mhsa_fwd_emits_fp8(N, hd))
+    return ok
 
 
 def mhsa_fwd(qkv, B, N, heads, scale, out_row_scale=None, fp8=None):

@@ -311,6 +311,9 @@ int ap_mhsa_fwd(const ap_bf16* qkv, ap_bf16* out, float* lse, int B, int N, int 
  * operand of an fp8 output projection (configs[4]).  The key/query-blocked kernel only (N > 256 or head_dim 48): AP_ERR_UNSUPPORTED else */
 int ap_mhsa_fwd_fp8(const ap_bf16* qkv, ap_bf16* out, unsigned char* out8, const float* q_scale, float* q_amax, float* lse, int B, int N,
                     int heads, int hd, float scale, const float* out_row_scale, ap_stream_t stream);
+/* Would ap_mhsa_fwd_fp8 take this shape?  1 / 0: the launch plan (csrc/attn_plan.h) under the process's switches (AP_MHSA_FLASH=1 sends every
+ * shape to the blocked kernel).  Nothing is launched.  (An added symbol: the ABI version stays 7.) */
+int ap_mhsa_fwd_emits_fp8(int N, int hd);
 size_t ap_mhsa_bwd_workspace(int B, int N, int heads, int hd);
 int ap_mhsa_bwd(const ap_bf16* qkv, const ap_bf16* out, const ap_bf16* dout, const float* lse,
                 ap_bf16* dqkv, int B, int N, int heads, int hd, float scale,

@@ -46,18 +46,18 @@ CASES = [(25088, 384, 384, "", 0), (25088, 384, 384, "bias", 0), (25088, 384, 38
 GUARD = 0x5A
 
 
-def bind(path):
+def bind(path, names=("ap_gemm_nt", "ap_gemm_nt_fp8")):
     from autoprog_amd._lib import _SIGNATURES
     lib = ctypes.CDLL(path)
-    for name in ("ap_gemm_nt", "ap_gemm_nt_fp8"):
+    for name in names:
         getattr(lib, name).restype, getattr(lib, name).argtypes = _SIGNATURES[name]
     return lib
 
 
-def libraries(args):
+def libraries(args, names=("ap_gemm_nt", "ap_gemm_nt_fp8")):
     from autoprog_amd._lib import LIB_PATH
     parent = os.path.join(os.path.abspath(args.parent_tree), "autoprog_amd", "libautoprog_hip.so") if args.parent_tree else None
-    return bind(LIB_PATH), (bind(parent) if parent else None)
+    return bind(LIB_PATH, names), (bind(parent, names) if parent else None)
 
 
 def make_case(M, N, K, spec, fp8):
@@ -142,19 +142,20 @@ def cmd_run(args):
     return 0
 
 
-def launches(path):
-    """(kernel name, grid, workgroup, LDS bytes) of the library's own kernels in a rocprofv3 kernel trace, in dispatch order"""
+def launches(path, ours=("k_gemm_nt", "k_build_gelu_table")):
+    """(kernel name, grid, workgroup, LDS bytes) of the library's own kernels (`ours`: parts of their names) in a rocprofv3 kernel trace, in
+    dispatch order"""
     with open(path, newline="") as f:
         rows = list(csv.DictReader(f))
     key = "Dispatch_Id" if rows and "Dispatch_Id" in rows[0] else "Start_Timestamp"
     rows.sort(key=lambda r: int(r[key]))
     cols = [c for c in rows[0] if c.startswith(("Grid_Size", "Workgroup_Size", "LDS_Block_Size"))] if rows else []
     assert not rows or len(cols) >= 7, "unexpected columns: %s" % list(rows[0])
-    return [(r["Kernel_Name"],) + tuple(int(r[c]) for c in cols) for r in rows if "k_gemm_nt" in r["Kernel_Name"] or "k_build_gelu_table" in r["Kernel_Name"]]
+    return [(r["Kernel_Name"],) + tuple(int(r[c]) for c in cols) for r in rows if any(k in r["Kernel_Name"] for k in ours)]
 
 
-def cmd_traces(args):
-    a, b = launches(args.head_csv), launches(args.parent_csv)
+def cmd_traces(args, ours=("k_gemm_nt", "k_build_gelu_table")):
+    a, b = launches(args.head_csv, ours), launches(args.parent_csv, ours)
     bad = [(i, x, y) for i, (x, y) in enumerate(zip(a, b)) if x != y]
     for i, x, y in bad[:10]:
         print("launch %d differs:\n  head   %s\n  parent %s" % (i, x, y))
